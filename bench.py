@@ -12,7 +12,11 @@ HBM, outputs left in HBM.  Scenes are independent, so ranks own disjoint env sli
 data path has no collective (weak scaling: per-GPU batch fixed); torch.distributed (RCCL) only
 carries the barrier and the max-over-ranks of the timing.
 
-Prints ONE JSON line (rank 0): metric/value/unit + roofline + cpu_baseline.
+A plain run sets up, warms up (--warmup steps), times exactly --steps steps in one bracketed block and
+prints ONE JSON line (rank 0): metric/value/unit/ms_per_step + the roofline of that block.
+--full adds what takes runs of its own: the short-block repeats (a block under --min-block-seconds is
+repeated and the median reported), per-launch event timing, the other kernels of the path (`also`) and the
+CPU baseline.  --dump-outputs DIR writes the outputs of the last timed step as DIR/<name>.npy.
 """
 import argparse
 import configparser
@@ -208,6 +212,28 @@ REFERENCE_PYTHON = {
 }
 
 MFMA_BF16_PEAK_TFLOPS = 2500.0  # MI355X_MICROARCH.md: dense bf16 MFMA peak
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, outs):
+    """The step outputs `outs` (torch tensors, as step_device filled them) as <path>/<name>.npy: float32 arrays stay
+    float32, every other dtype (float64 values, uint8 masks and codes) is written as float64.  Past DUMP_LIMIT_BYTES a
+    fixed seeded sample of envs is written instead, its sorted indices as env_index.npy."""
+    host = {k: v.cpu().numpy() for k, v in outs.items()}
+    host = {k: a.astype(np.float32 if a.dtype == np.float32 else np.float64) for k, a in host.items()}
+    E = len(next(iter(host.values())))
+    per_env = sum(a.nbytes for a in host.values()) / E
+    if per_env * E > DUMP_LIMIT_BYTES:
+        keep = int(DUMP_LIMIT_BYTES // (per_env + 8))
+        idx = np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+        host = {k: a[idx] for k, a in host.items()}
+        host["env_index"] = idx.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, a in host.items():
+        np.save(os.path.join(path, k + ".npy"), a)
+    return sorted(host)
 
 
 def ebc_scene_slice(batch, n):
@@ -412,10 +438,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="metric", choices=sorted(WORKLOADS))
     ap.add_argument("--envs", type=int, default=None, help="envs per GPU (default: workload's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also the short-block repeats, per-launch event timing, the look-ahead / value-network side "
+                         "measurements and the CPU baseline (a plain run times its --steps steps and nothing else)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write rank 0's outputs of the last timed step as DIR/<name>.npy (float32 / float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--min-block-seconds", type=float, default=0.05,
-                    help="a K-step block shorter than this is repeated after a clock warm-up; the median is reported")
-    ap.add_argument("--no-also", action="store_true", help="skip the look-ahead / value-network side measurements")
+                    help="with --full: a K-step block shorter than this is repeated after a clock warm-up; the median "
+                         "is reported")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the look-ahead / value-network side "
+                                                           "measurements")
     ap.add_argument("--human-policy", default="orca", choices=["orca", "linear"],
                     help="diagnostic only: the headline metric is ORCA")
     ap.add_argument("--rehearsal-gpu-ranks", type=int, default=0,
@@ -518,8 +551,8 @@ def main():
     n_blocks = 1
     from ebcsim import shard as _sh
     # every rank takes the same decision: the first block's time is max-reduced BEFORE it is compared
-    first_max, _ = _sh.job_rate(first[0], 0.0, device=dev if backend == "nccl" else None)
-    if first_max < args.min_block_seconds:
+    first_max = _sh.job_rate(first[0], 0.0, device=dev if backend == "nccl" else None)[0] if args.full else None
+    if args.full and first_max < args.min_block_seconds:
         # A K-step block shorter than ~50 ms is over before the chip has left its idle clock (round 1:
         # 20 steps = 0.43 ms read 17 % low).  Keep stepping untimed for >= 0.3 s, then repeat the same
         # bracketed K-step block an odd number of times and report the MEDIAN block: `steps` and
@@ -541,9 +574,12 @@ def main():
     elapsed, stream_ms = float(bt[mid]), blocks[mid][1]
     block_spread = (float(bt.min()), float(bt.max()))
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outs)
+
     # per-launch kernel duration: HIP events around every launch, in a separate untimed pass
     kernel_ms = None
-    if on_gpu:
+    if on_gpu and args.full:
         env.timing(True)
         for _ in range(min(args.steps, 200)):
             step()
@@ -551,7 +587,7 @@ def main():
         env.timing(False)
 
     also = None
-    if rank == 0 and world == 1 and not args.no_also and args.human_policy == "orca":
+    if args.full and rank == 0 and world == 1 and not args.no_also and args.human_policy == "orca":
         also = also_kernels(env, batch, dev, scene_config(args.workload))
 
     from ebcsim import shard
@@ -629,7 +665,7 @@ def main():
         }
         if also is not None:
             line["also"] = also
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(params, batch)
         print(json.dumps(line), flush=True)
     if collective:

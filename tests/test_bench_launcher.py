@@ -80,6 +80,37 @@ def test_parent_does_not_touch_the_gpu_before_spawning():
     assert "os.exec" not in src
 
 
+def test_dump_outputs_writes_float_arrays_within_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs' writer: float32 stays float32, masks and codes become float64 of the same values; past the size
+    limit a fixed seeded sample of envs (the same on every call), its indices beside it."""
+    import numpy as np
+    import torch
+    import bench
+    E = 64
+    outs = {"reward": torch.arange(E, dtype=torch.float64), "done": torch.ones(E, dtype=torch.uint8),
+            "info": torch.arange(E, dtype=torch.uint8) % 5, "obs_rotated": torch.randn(E, 4, 5)}
+    names = bench.dump_outputs(str(tmp_path / "all"), outs)
+    assert names == ["done", "info", "obs_rotated", "reward"]
+    for k in names:
+        a = np.load(str(tmp_path / "all" / (k + ".npy")))
+        assert a.dtype == (np.float32 if k == "obs_rotated" else np.float64)
+        np.testing.assert_array_equal(a, outs[k].numpy())
+    limit = 3200  # 104 B per env (3 x 8 + 80): 64 envs do not fit
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", limit)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), outs) == ["done", "env_index", "info", "obs_rotated", "reward"]
+    idx = np.load(str(tmp_path / "s1" / "env_index.npy")).astype(np.int64)
+    assert 0 < len(idx) < E and (np.diff(idx) > 0).all()
+    total = 0
+    for k in ("done", "env_index", "info", "obs_rotated", "reward"):
+        a, b = np.load(str(tmp_path / "s1" / (k + ".npy"))), np.load(str(tmp_path / "s2" / (k + ".npy")))
+        np.testing.assert_array_equal(a, b)
+        if k != "env_index":
+            np.testing.assert_array_equal(a, outs[k].numpy()[idx])
+        total += a.nbytes
+    assert total <= limit
+
+
 def _free_port():
     import socket
     with socket.socket() as s:
@@ -96,12 +127,12 @@ def test_bench_rank_through_rccl_on_one_rank():
     env = dict(os.environ, EBCSIM_FORCE_COLLECTIVES="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=_free_port(), RANK="0",
                LOCAL_RANK="0", WORLD_SIZE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "5",
-                        "--no-also", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-also", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads(r.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["steps"] == 50 and line["value"] > 1e8
-    plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--no-also",
-                            "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
+    plain = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "50", "--warmup", "5", "--full",
+                            "--no-also", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600)
     ref = json.loads(plain.stdout.strip().splitlines()[-1])
     assert abs(line["value"] / ref["value"] - 1) < 0.2  # the same job with and without the group
 
@@ -131,3 +162,26 @@ def test_multi_rank_rehearsal_of_config4_on_one_gpu():
     assert line["ranks_on_gpu"] == 2 and line["roofline"]["achieved"] > 0 and line["scaling"] == "weak"
     assert line["ranks_with_gpu_open"] == 2  # the host-only rank really stayed off the card
     assert line["units_per_step"] == n * 16384 * 5
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_repeatable_outputs(tmp_path):
+    """A plain run times exactly --steps steps in one block and measures nothing else; two runs with the same arguments
+    start from the same inputs, so the outputs of their last timed step agree."""
+    import subprocess
+    import numpy as np
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "200", "--warmup", "10",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["steps"] == 200 and line["timed_blocks"] == 1 and line["ms_per_step"] > 0
+        assert "also" not in line and "cpu_baseline" not in line
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == ["done.npy", "info.npy", "obs_rotated.npy", "reward.npy"]
+    for n in names:
+        a, b = np.load(str(tmp_path / "a" / n)), np.load(str(tmp_path / "b" / n))
+        assert a.dtype in (np.float32, np.float64) and len(a) == lines[0]["config"]["envs_per_gpu"]
+        np.testing.assert_allclose(a, b, rtol=0, atol=1e-5 if a.dtype == np.float32 else 1e-9, err_msg=n)

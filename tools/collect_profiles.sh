@@ -21,7 +21,7 @@ done
 python3 $root/profiles/summarize_pmc.py $out/p*/*counter_collection.csv > $out/pmc.json
 python3 $root/tools/traffic_from_pmc.py $out/pmc.json metric 4096 10 "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes, tools/collect_profiles.sh $tag), bench.py --steps 300" > $out/traffic_metric.json
 cd $root
-python3 bench.py --steps 500 --warmup 20 > $out/bench_default.jsonl 2>$out/bench_default.err
+python3 bench.py --full --steps 500 --warmup 20 > $out/bench_default.jsonl 2>$out/bench_default.err
 if [ -f eb-cadrl_amd/lib/libebcsim_trace.so ]; then
   EBCSIM_LIB=$root/eb-cadrl_amd/lib/libebcsim_trace.so python3 tools/wave_timeline.py metric > $out/wave_timeline.txt 2>&1
 fi
