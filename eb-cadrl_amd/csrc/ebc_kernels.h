@@ -2086,7 +2086,8 @@ __global__ __launch_bounds__(64) void scene_gen_kernel(EbcSceneGen c, const uint
   const size_t k = (size_t)r * N, q = (size_t)r * (S ? S : 1);
   const SceneRow o = {d.n_humans + r, d.px + k, d.py + k, d.vx + k, d.vy + k, d.gx + k, d.gy + k, d.radius + k, d.v_pref + k,
                       d.type + k, d.n_static + r, d.spx + q, d.spy + q, d.sradius + q,
-                      d.grid ? d.grid + (size_t)r * G * 2 : nullptr, d.robot + (size_t)r * 9};
+                      d.grid ? d.grid + (size_t)r * G * 2 : nullptr, d.robot + (size_t)r * 9,
+                      d.poly ? d.poly + q * 8 : nullptr, d.n_poly ? d.n_poly + r : nullptr};
   const int st = generate_scene_row(c, seeds ? seeds[r] : seed0 + (uint32_t)r, mt + r, (size_t)n, o, N, S, G);
   if (st) atomicOr(status, st);
 }

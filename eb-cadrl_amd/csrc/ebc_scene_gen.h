@@ -167,6 +167,8 @@ struct SceneRow {
   double *spx, *spy, *sradius;
   uint64_t *grid;  // [G][2] of this scene, or nullptr
   double *robot;   // [9]
+  double *poly = nullptr;   // [S][4][2] obstacle_vertices (scene_generator.py:109-328), or nullptr
+  int *n_poly = nullptr;    // polygons written to `poly`
 };
 
 struct SceneGenCore {
@@ -296,6 +298,16 @@ struct SceneGenCore {
     return true;
   }
 
+  // one obstacle's polygon, in scene.py's vertex order (xm + hx, ym + hy), (xm - hx, ym + hy), (xm - hx, ym - hy),
+  // (xm + hx, ym - hy) — the vertices the angular local map reads (ebc_local_map.h)
+  EBC_HD void polygon(int &np, double xm, double ym, double hx, double hy) const {
+    if (!o.poly || np >= S) return;
+    double *v = o.poly + (size_t)np * 8;
+    v[0] = xm + hx; v[1] = ym + hy; v[2] = xm - hx; v[3] = ym + hy;
+    v[4] = xm - hx; v[5] = ym - hy; v[6] = xm + hx; v[7] = ym - hy;
+    ++np;
+  }
+
   // returns 0, or EBC_GEN_STATIC_OVERFLOW
   EBC_HD int run() {
     int slot = 0;
@@ -316,7 +328,7 @@ struct SceneGenCore {
       for (int q = 0; q < G * 2; ++q) o.grid[q] = 0;
     const double res = c.map_resolution, reach = c.robot_radius + c.discomfort_dist;
     const long lo = (long)(-G / 2.0), hi = (long)(G / 2.0);  // randint(-max_loc / 2.0, max_loc / 2.0): int() truncates
-    int ns = 0, status = 0;
+    int ns = 0, status = 0, np = 0;
     for (int q = 0; q < c.num_circles; ++q) {
       long lx = 0, ly = 0;
       double rad = 0, xm = 0, ym = 0;
@@ -331,6 +343,7 @@ struct SceneGenCore {
       const long d = py_round(2 * rad / res);
       rasterize(py_round(lx + G / 2.0), py_round(ly + G / 2.0), d, d);
       if (!rows_of(d, d, xm, ym, rad, rad, ns)) status = EBC_GEN_STATIC_OVERFLOW;
+      polygon(np, xm, ym, rad, rad);
     }
     for (int q = 0; q < c.num_walls; ++q) {
       long lx = 0, ly = 0, xd = 1, yd = 1;
@@ -354,8 +367,10 @@ struct SceneGenCore {
       const long d0 = py_round(xd / res), d1 = py_round(yd / res);
       rasterize(py_round(lx + G / 2.0), py_round(ly + G / 2.0), d0, d1);
       if (!rows_of(d0, d1, xm, ym, xd / 2.0, yd / 2.0, ns)) status = EBC_GEN_STATIC_OVERFLOW;
+      polygon(np, xm, ym, xd / 2.0, yd / 2.0);
     }
     if (o.n_static) *o.n_static = ns;
+    if (o.n_poly) *o.n_poly = np;
     for (int q = ns; q < S; ++q) o.spx[q] = o.spy[q] = o.sradius[q] = 0;
     return status;
   }

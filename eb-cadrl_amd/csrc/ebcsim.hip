@@ -13,6 +13,7 @@
 
 #include "ebc_host.h"
 #include "ebc_kernels.h"
+#include "ebc_local_map_kernel.h"
 
 namespace {
 
@@ -41,6 +42,12 @@ struct Handle {
   unsigned epoch = 0;  // fused ORCA steps launched so far (StepGrid::epoch)
   std::vector<void *> pool_allocs;   // pool arrays (re-allocated by ebc_set_scene_pool)
   uint64_t *pool_grid_alloc = nullptr;
+  // angular local map (ebc_local_map_config): polygons per scene slot, [E + P][S][4][2] and a count per slot
+  bool lm_on = false;
+  ebc::LocalMapCfg lm = {};
+  double *lm_poly = nullptr;
+  int *lm_npoly = nullptr;
+  std::vector<uint8_t> lm_set;  // per slot: its polygons were written since the slot's scene was
   // staging for host-location calls
   void *stage = nullptr;
   size_t stage_bytes = 0;
@@ -446,6 +453,77 @@ int validate_scene(const Handle *h, const EbcScene *sc, const int32_t *ids, int 
   return EBC_OK;
 }
 
+// ---- angular local map storage: slot r of [E + P] holds r's polygons at lm_poly + r * S1 * 8
+size_t lm_s1(const Handle *h) { return h->s.S ? (size_t)h->s.S : 1; }
+
+// (Re)allocate the polygon storage for E + P slots, keeping the first `keep` slots' contents and marks.
+int lm_alloc(Handle *h, int slots, int keep) {
+  double *poly = nullptr;
+  int *npoly = nullptr;
+  const size_t S1 = lm_s1(h);
+  HIP_TRY(hipMalloc(&poly, (size_t)slots * S1 * 8 * sizeof(double) + 16));
+  HIP_TRY(hipMalloc(&npoly, (size_t)slots * sizeof(int) + 16));
+  HIP_TRY(hipMemset(npoly, 0, (size_t)slots * sizeof(int) + 16));
+  if (keep > 0 && h->lm_poly) {
+    HIP_TRY(hipMemcpy(poly, h->lm_poly, (size_t)keep * S1 * 8 * sizeof(double), hipMemcpyDeviceToDevice));
+    HIP_TRY(hipMemcpy(npoly, h->lm_npoly, (size_t)keep * sizeof(int), hipMemcpyDeviceToDevice));
+  }
+  if (h->lm_poly) (void)hipFree(h->lm_poly);
+  if (h->lm_npoly) (void)hipFree(h->lm_npoly);
+  h->lm_poly = poly;
+  h->lm_npoly = npoly;
+  h->lm_set.resize((size_t)slots, 0);
+  for (size_t r = (size_t)keep; r < h->lm_set.size(); ++r) h->lm_set[r] = 0;
+  return EBC_OK;
+}
+
+// Polygons rows -> slots (slot of row r = slots[r], or first + r); kind: where `poly` / `npoly` live.
+int lm_upload(Handle *h, const int *slots, int first, int n, const double *poly, const int *npoly, hipMemcpyKind kind) {
+  const size_t row = lm_s1(h) * 8 * sizeof(double);
+  if (!slots) {
+    HIP_TRY(hipMemcpy((char *)h->lm_poly + (size_t)first * row, poly, (size_t)n * row, kind));
+    HIP_TRY(hipMemcpy(h->lm_npoly + first, npoly, (size_t)n * sizeof(int), kind));
+  } else {
+    for (int r = 0; r < n; ++r) {
+      HIP_TRY(hipMemcpy((char *)h->lm_poly + (size_t)slots[r] * row, (const char *)poly + (size_t)r * row, row, kind));
+      HIP_TRY(hipMemcpy(h->lm_npoly + slots[r], npoly + r, sizeof(int), kind));
+    }
+  }
+  for (int r = 0; r < n; ++r) h->lm_set[(size_t)(slots ? slots[r] : first + r)] = 1;
+  return EBC_OK;
+}
+
+// Every slot an env can reach holds polygons: its own ebc_reset slot and every pool scene.
+int lm_ready(const Handle *h, const char *what) {
+  if (!h->lm_on) return fail(EBC_ERR_STATE, std::string(what) + " before ebc_local_map_config");
+  if (h->s.S == 0) return EBC_OK;  // no scene of this handle can hold an obstacle
+  const int E = h->s.E;
+  for (int e = 0; e < E; ++e)
+    if (!h->lm_set[(size_t)e])
+      return fail(EBC_ERR_STATE, std::string(what) + ": env " + std::to_string(e) +
+                                     " has no obstacles for its ebc_reset scene (ebc_set_obstacles)");
+  for (size_t r = (size_t)E; r < h->lm_set.size(); ++r)
+    if (!h->lm_set[r])
+      return fail(EBC_ERR_STATE, std::string(what) + ": pool scene " + std::to_string(r - E) +
+                                     " has no obstacles (ebc_set_obstacle_pool)");
+  return EBC_OK;
+}
+
+int launch_local_map(Handle *h, int next, int robot_policy, const double *robot_action, double *out) {
+  ebc::LocalMapIO io;
+  io.c = h->lm;
+  io.poly = h->lm_poly;
+  io.n_poly = h->lm_npoly;
+  io.S = (int)lm_s1(h);
+  io.next = next;
+  io.robot_policy = robot_policy;
+  io.robot_action = robot_action;
+  io.out = out;
+  hipLaunchKernelGGL(ebc::local_map_kernel, dim3((unsigned)h->s.E), dim3(EBC_WAVE), 0, h->stream, h->p, h->s, io);
+  HIP_TRY(hipGetLastError());
+  return EBC_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -572,6 +650,8 @@ int ebc_destroy(void *handle) {
   (void)hipStreamSynchronize(h->stream);
   for (void *ptr : h->allocs) (void)hipFree(ptr);
   for (void *ptr : h->pool_allocs) (void)hipFree(ptr);
+  if (h->lm_poly) (void)hipFree(h->lm_poly);
+  if (h->lm_npoly) (void)hipFree(h->lm_npoly);
   if (h->stage) (void)hipFree(h->stage);
   for (hipEvent_t ev : h->ev) (void)hipEventDestroy(ev);
   if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
@@ -663,6 +743,8 @@ static int reset_impl(Handle *h, const int32_t *env_ids, const EbcScene *sc, hip
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->faulted = false;
   }
+  if (h->lm_on)  // the scenes changed: their polygons come with ebc_set_obstacles (or the generator)
+    for (int r = 0; r < n; ++r) h->lm_set[(size_t)ids[r]] = 0;
   h->has_reset = true;
   return EBC_OK;
 }
@@ -681,12 +763,22 @@ static int pool_impl(Handle *h, const EbcScene *sc, int stride, hipMemcpyKind ki
   if (stride < 0) return fail(EBC_ERR_INVALID, "stride");
   HIP_TRY(hipStreamSynchronize(h->stream));
   const int P = sc->n, E = s.E;
+  bool old_pool_set = true;  // every polygon a running env can be moved from is known
+  for (size_t r = (size_t)E; h->lm_on && r < h->lm_set.size(); ++r) old_pool_set = old_pool_set && h->lm_set[r];
   if (h->has_reset) {  // running episodes keep their maps: into the envs' own slots before the old slots are freed
+    if (h->lm_on)  // the polygons first: rehome_grid_kernel rewrites grid_scene
+      hipLaunchKernelGGL(ebc::rehome_poly_kernel, dim3((unsigned)E), dim3(64), 0, h->stream, h->s, h->lm_poly, h->lm_npoly,
+                         (int)lm_s1(h));
     hipLaunchKernelGGL(ebc::rehome_grid_kernel, dim3((unsigned)E), dim3(256), 0, h->stream, h->s, h->pool_grid_alloc);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(h->stream));
   }
   if ((rc = alloc_pool(h, P)) != EBC_OK) return rc;  // keeps the E reset slots
+  if (h->lm_on) {  // so does the polygon storage; the pool's polygons are unset until written
+    if ((rc = lm_alloc(h, E + P, E)) != EBC_OK) return rc;
+    if (!old_pool_set)
+      for (int e = 0; e < E; ++e) h->lm_set[(size_t)e] = 0;
+  }
   ebc::ScenePool &pl = s.pool;
   if (sc->grid) pl.grid = h->pool_grid_alloc;
   const size_t N = s.N, S = s.S ? s.S : 1;
@@ -721,6 +813,8 @@ namespace {
 struct GenBatch {  // n generated scenes in device memory, freed with the object
   std::vector<void *> allocs;
   EbcScene sc;  // device pointers
+  double *poly = nullptr;  // [n][S][4][2] and [n]: written when local maps are configured
+  int *n_poly = nullptr;
   ~GenBatch() {
     for (void *ptr : allocs) (void)hipFree(ptr);
   }
@@ -773,6 +867,10 @@ int generate_batch(Handle *h, const EbcSceneGen *gen, uint32_t seed0, const uint
   G_(n_humans, n); G_(px, nN); G_(py, nN); G_(vx, nN); G_(vy, nN); G_(gx, nN); G_(gy, nN); G_(radius, nN); G_(v_pref, nN);
   G_(type, nN); G_(n_static, n); G_(spx, nS); G_(spy, nS); G_(sradius, nS); G_(robot, (size_t)n * 9);
   if (with_grid) G_(grid, (size_t)n * G * 2);
+  if (h->lm_on && S > 0) {
+    G_(poly, nS * 8);
+    G_(n_poly, n);
+  }
 #undef G_
   if (rc == EBC_OK) rc = get(&mt, (size_t)n * 624);
   if (rc == EBC_OK) rc = get(&status, 1);
@@ -798,6 +896,8 @@ int generate_batch(Handle *h, const EbcSceneGen *gen, uint32_t seed0, const uint
   sc.spx = d.spx; sc.spy = d.spy; sc.sradius = d.sradius;
   sc.grid = d.grid;
   sc.robot = d.robot;
+  b.poly = d.poly;
+  b.n_poly = d.n_poly;
   return EBC_OK;
 }
 }  // namespace
@@ -833,7 +933,9 @@ int ebc_generate_reset(void *handle, const EbcSceneGen *gen, uint32_t seed0, con
   if ((rc = generate_batch(h, gen, seed0, seeds, n, b)) != EBC_OK) return rc;
   std::vector<int32_t> ids(n);
   for (int r = 0; r < n; ++r) ids[r] = first + r;
-  return reset_impl(h, ids.data(), &b.sc, hipMemcpyDeviceToDevice);
+  if ((rc = reset_impl(h, ids.data(), &b.sc, hipMemcpyDeviceToDevice)) != EBC_OK) return rc;
+  if (b.poly) return lm_upload(h, nullptr, first, n, b.poly, b.n_poly, hipMemcpyDeviceToDevice);
+  return EBC_OK;
 }
 
 int ebc_generate_pool(void *handle, const EbcSceneGen *gen, uint32_t seed0, const uint32_t *seeds, int n, int stride) {
@@ -842,7 +944,9 @@ int ebc_generate_pool(void *handle, const EbcSceneGen *gen, uint32_t seed0, cons
   if (rc) return rc;
   GenBatch b;
   if ((rc = generate_batch(h, gen, seed0, seeds, n, b)) != EBC_OK) return rc;
-  return pool_impl(h, &b.sc, stride, hipMemcpyDeviceToDevice);
+  if ((rc = pool_impl(h, &b.sc, stride, hipMemcpyDeviceToDevice)) != EBC_OK) return rc;
+  if (b.poly) return lm_upload(h, nullptr, h->s.E, n, b.poly, b.n_poly, hipMemcpyDeviceToDevice);
+  return EBC_OK;
 }
 
 int ebc_set_human_actions(void *handle, int location, const double *act) {
@@ -1073,14 +1177,13 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
   return EBC_OK;
 }
 
-int ebc_step(void *handle, const EbcStepArgs *a) {
-  Handle *h;
-  int rc = check_handle(handle, &h);
-  if (rc) return rc;
+// ebc_step, and with `local_map` (ebc_step_with_map) the map of every env's post-step state, enqueued first
+static int step_impl(Handle *h, const EbcStepArgs *a, double *local_map, const char *what) {
+  int rc;
   if (!a || a->struct_size != sizeof(EbcStepArgs)) return fail(EBC_ERR_INVALID, "EbcStepArgs.struct_size");
-  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_step before ebc_reset");
-  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_step: the handle reported a mailbox fault; ebc_reset re-arms it");
-  if ((rc = refuse_capture(h, "ebc_step")) != EBC_OK) return rc;
+  if (!h->has_reset) return fail(EBC_ERR_STATE, std::string(what) + " before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, std::string(what) + ": the handle reported a mailbox fault; ebc_reset re-arms it");
+  if ((rc = refuse_capture(h, what)) != EBC_OK) return rc;
   if (a->human_policy < EBC_HUMAN_EXTERNAL || a->human_policy > EBC_HUMAN_CACHED)
     return fail(EBC_ERR_INVALID, "human_policy");
   if (a->robot_policy == EBC_ROBOT_LINEAR && h->p.robot_kinematics != EBC_HOLONOMIC)
@@ -1090,8 +1193,10 @@ int ebc_step(void *handle, const EbcStepArgs *a) {
   if (a->robot_policy != EBC_ROBOT_EXTERNAL && a->robot_policy != EBC_ROBOT_LINEAR)
     return fail(EBC_ERR_INVALID, "robot_policy");
   if ((a->flags & EBC_FLAG_BORDER) && !a->border) return fail(EBC_ERR_INVALID, "border is NULL");
+  if (local_map && (rc = lm_ready(h, what)) != EBC_OK) return rc;
   const DevState &s = h->s;
   const size_t E = s.E, N = s.N, R = s.N + s.S, T = h->T;
+  double *d_map = local_map;
   StepIO io;
   memset(&io, 0, sizeof(io));
   io.robot_policy = a->robot_policy;
@@ -1106,7 +1211,8 @@ int ebc_step(void *handle, const EbcStepArgs *a) {
     io.human_action = a->human_action; io.ob = a->ob; io.obs_rotated = a->obs_rotated;
   } else {
     const size_t need = pad256(E * 2 * 8) * 2 + pad256(E * 8) * 2 + pad256(E) * 2 + pad256(E * 3 * 8) +
-                        pad256(E * N * 2 * 8) + pad256(E * R * 5 * 8) + pad256(E * R * T * 4) + 4096;
+                        pad256(E * N * 2 * 8) + pad256(E * R * 5 * 8) + pad256(E * R * T * 4) + 4096 +
+                        (local_map ? pad256(E * h->lm.dim * 8) : 0);
     if ((rc = ensure_stage(h, need)) != EBC_OK) return rc;
     if ((rc = st.in(a->robot_policy == EBC_ROBOT_EXTERNAL ? a->robot_action : nullptr, E * 2,
                     &io.robot_action)) != EBC_OK)
@@ -1116,7 +1222,10 @@ int ebc_step(void *handle, const EbcStepArgs *a) {
     io.robot_action_out = st.out(a->robot_action_out, E * 2);
     io.human_action = st.out(a->human_action, E * N * 2); io.ob = st.out(a->ob, E * R * 5);
     io.obs_rotated = st.out(a->obs_rotated, E * R * T);
+    d_map = st.out(local_map, E * h->lm.dim);
   }
+  // the map reads the pre-step state (and the slot it runs, before a restart rewrites it): launched first
+  if (d_map && (rc = launch_local_map(h, 1, io.robot_policy, io.robot_action, d_map)) != EBC_OK) return rc;
   hipEvent_t e0 = nullptr, e1 = nullptr;
   if (h->timing) {
     if (h->ev_used + 2 > h->ev.size()) {
@@ -1133,6 +1242,114 @@ int ebc_step(void *handle, const EbcStepArgs *a) {
   if ((rc = launch_step(h, io, a->human_policy)) != EBC_OK) return rc;
   if (h->timing) HIP_TRY(hipEventRecord(e1, h->stream));
   if (a->location != EBC_DEVICE) return st.finish();
+  return EBC_OK;
+}
+
+int ebc_step(void *handle, const EbcStepArgs *a) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  return step_impl(h, a, nullptr, "ebc_step");
+}
+
+int ebc_step_with_map(void *handle, const EbcStepArgs *a, double *local_map) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!local_map) return fail(EBC_ERR_INVALID, "ebc_step_with_map: local_map is NULL");
+  return step_impl(h, a, local_map, "ebc_step_with_map");
+}
+
+int ebc_local_map_config(void *handle, const EbcLocalMapParams *lp) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!lp || lp->struct_size != sizeof(EbcLocalMapParams)) return fail(EBC_ERR_INVALID, "EbcLocalMapParams.struct_size");
+  if (lp->dim <= 0) return fail(EBC_ERR_INVALID, "local map dim");
+  if (lp->dim > EBC_LM_MAX_DIM) return fail(EBC_ERR_UNSUPPORTED, "local map dim > 128");
+  if (!(lp->max_range > 0) || !std::isfinite(lp->max_range)) return fail(EBC_ERR_INVALID, "local map max_range");
+  if (!(lp->angle_max > lp->angle_min) || !std::isfinite(lp->angle_min) || !std::isfinite(lp->angle_max))
+    return fail(EBC_ERR_INVALID, "local map angle_min / angle_max");
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  if (!h->lm_on) {
+    if ((rc = lm_alloc(h, h->s.E + h->s.pool.P, 0)) != EBC_OK) return rc;
+    h->lm_on = true;
+  }
+  h->lm = ebc::local_map_cfg(lp->dim, lp->max_range, lp->angle_min, lp->angle_max, lp->normalize ? 1 : 0);
+  return EBC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+// The polygons of n scenes: rectangles with axis-aligned sides (the generator's and every saved scene's), <= S of them.
+int validate_obstacles(const Handle *h, const EbcObstacles *o) {
+  if (!o || o->struct_size != sizeof(EbcObstacles)) return fail(EBC_ERR_INVALID, "EbcObstacles.struct_size");
+  if (o->n <= 0 || !o->n_poly || !o->vertices) return fail(EBC_ERR_INVALID, "EbcObstacles: n, n_poly, vertices");
+  const size_t S1 = lm_s1(h);
+  for (int r = 0; r < o->n; ++r) {
+    if (o->n_poly[r] < 0 || o->n_poly[r] > h->s.S)
+      return fail(EBC_ERR_INVALID, "EbcObstacles: scene " + std::to_string(r) + " has more than max_static polygons");
+    for (int q = 0; q < o->n_poly[r]; ++q) {
+      const double *v = o->vertices + ((size_t)r * S1 + q) * 8;
+      bool finite = true;
+      for (int k = 0; k < 8; ++k) finite = finite && std::isfinite(v[k]);
+      // v0 -> v1 -> v2 -> v3: sides alternately horizontal and vertical, in either order, none of length 0
+      const bool hv = v[1] == v[3] && v[2] == v[4] && v[5] == v[7] && v[6] == v[0];
+      const bool vh = v[0] == v[2] && v[3] == v[5] && v[4] == v[6] && v[7] == v[1];
+      const bool open = v[0] != v[4] && v[1] != v[5];
+      if (!finite || !(hv || vh) || !open)
+        return fail(EBC_ERR_INVALID, "EbcObstacles: polygon " + std::to_string(q) + " of scene " + std::to_string(r) +
+                                         " is not an axis-aligned 4-vertex rectangle");
+    }
+  }
+  return EBC_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ebc_set_obstacles(void *handle, const int32_t *env_ids, const EbcObstacles *o) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!h->lm_on) return fail(EBC_ERR_STATE, "ebc_set_obstacles before ebc_local_map_config");
+  if ((rc = validate_obstacles(h, o)) != EBC_OK) return rc;
+  if (o->n > h->s.E) return fail(EBC_ERR_INVALID, "EbcObstacles.n > n_envs");
+  for (int r = 0; env_ids && r < o->n; ++r)
+    if (env_ids[r] < 0 || env_ids[r] >= h->s.E) return fail(EBC_ERR_INVALID, "env id out of range");
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return lm_upload(h, env_ids, 0, o->n, o->vertices, o->n_poly, hipMemcpyHostToDevice);
+}
+
+int ebc_set_obstacle_pool(void *handle, const EbcObstacles *o) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!h->lm_on) return fail(EBC_ERR_STATE, "ebc_set_obstacle_pool before ebc_local_map_config");
+  if ((rc = validate_obstacles(h, o)) != EBC_OK) return rc;
+  if (h->s.pool.P == 0 || o->n != h->s.pool.P)
+    return fail(EBC_ERR_INVALID, "ebc_set_obstacle_pool: n must equal the installed pool's size");
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  return lm_upload(h, nullptr, h->s.E, o->n, o->vertices, o->n_poly, hipMemcpyHostToDevice);
+}
+
+int ebc_local_map(void *handle, int location, double *out) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!out) return fail(EBC_ERR_INVALID, "ebc_local_map: out is NULL");
+  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_local_map before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_local_map: the handle reported a mailbox fault; ebc_reset re-arms it");
+  if ((rc = lm_ready(h, "ebc_local_map")) != EBC_OK) return rc;
+  double *d_out = out;
+  Stager st{h};
+  if (location != EBC_DEVICE) {
+    if ((rc = ensure_stage(h, pad256((size_t)h->s.E * h->lm.dim * 8) + 1024)) != EBC_OK) return rc;
+    d_out = st.out(out, (size_t)h->s.E * h->lm.dim);
+  }
+  if ((rc = launch_local_map(h, 0, EBC_ROBOT_EXTERNAL, nullptr, d_out)) != EBC_OK) return rc;
+  if (location != EBC_DEVICE) return st.finish();
   return EBC_OK;
 }
 

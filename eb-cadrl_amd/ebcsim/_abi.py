@@ -128,6 +128,19 @@ class EbcStateView(C.Structure):
     ]
 
 
+class EbcLocalMapParams(C.Structure):
+    """include/ebcsim.h: get_local_map_angular's parameters (simulator/env.py:80-84), angles in radians."""
+    _fields_ = [("struct_size", C.c_uint32), ("dim", C.c_int32), ("max_range", C.c_double), ("angle_min", C.c_double),
+                ("angle_max", C.c_double), ("normalize", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EbcObstacles(C.Structure):
+    """include/ebcsim.h: n scenes' obstacle polygons, n_poly [n] int32, vertices [n][S][4][2] float64 (host)."""
+    _fields_ = [("struct_size", C.c_uint32), ("n", C.c_int32), ("n_poly", _pd), ("vertices", _pd)]
+
+
+LOCAL_MAP_MAX_DIM = 128
+
 MLP_IN_FRAGMENTS = 1
 MLP_GENERAL_KERNEL = 1
 

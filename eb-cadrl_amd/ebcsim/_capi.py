@@ -35,6 +35,11 @@ SYMBOLS = {
     "ebc_generate_scenes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_generate_reset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int]),
     "ebc_generate_pool": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int]),
+    "ebc_local_map_config": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ebc_set_obstacles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_set_obstacle_pool": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ebc_local_map": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ebc_step_with_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_il_targets": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double,
                                  C.c_void_p, C.c_void_p]),
     "ebc_dims": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),

@@ -79,6 +79,8 @@ class BatchedEnv:
             if len(ids) != scene.n:
                 raise ValueError("len(env_ids) != scene.n")
         _capi.check(self._L.ebc_reset(self._h, _np_ptr(ids), C.addressof(sc)))
+        if self.map_dim and scene.n_poly is not None:
+            self.set_obstacles(scene, ids)
         if not hasattr(self, "n_static_host"):
             self.n_static_host = np.zeros(self.E, dtype=np.int64)
         if self.S:
@@ -97,7 +99,60 @@ class BatchedEnv:
         keep = []
         sc = self._scene_struct(scene, keep)
         _capi.check(self._L.ebc_set_scene_pool(self._h, C.addressof(sc), int(self.E if stride is None else stride)))
+        if self.map_dim and scene.n_poly is not None:
+            self.set_obstacle_pool(scene)
         self._note_rows(scene)
+
+    # ------------------------------------------------------------------ angular local map (get_local_map_angular,
+    # simulator/env.py:468-628): ebc_local_map_config, then polygons per scene slot (reset / set_scene_pool pass them on)
+    map_dim = 0
+
+    def configure_local_map(self, dim, max_range, angle_min, angle_max, normalize=True):
+        """angle_min / angle_max in radians (the [map] keys times pi, env.py:80-84)."""
+        p = _abi.EbcLocalMapParams()
+        p.struct_size = C.sizeof(p)
+        p.dim, p.max_range, p.angle_min, p.angle_max = int(dim), float(max_range), float(angle_min), float(angle_max)
+        p.normalize = 1 if normalize else 0
+        _capi.check(self._L.ebc_local_map_config(self._h, C.addressof(p)))
+        self.map_dim = int(dim)
+
+    def _obstacles(self, scene, keep):
+        if scene.n_poly is None:
+            raise ValueError("the scene batch carries no obstacle polygons (SceneBatch.from_scenes fills them)")
+        n_poly = np.ascontiguousarray(scene.n_poly, dtype=np.int32)
+        poly = np.ascontiguousarray(scene.poly, dtype=np.float64)
+        if poly.shape != (scene.n, max(self.S, 1), 4, 2):
+            raise ValueError("poly must be [n][%d][4][2]" % max(self.S, 1))
+        keep += [n_poly, poly]
+        o = _abi.EbcObstacles()
+        o.struct_size = C.sizeof(o)
+        o.n, o.n_poly, o.vertices = scene.n, n_poly.ctypes.data, poly.ctypes.data
+        return o
+
+    def set_obstacles(self, scene, env_ids=None):
+        """The polygons of the listed envs' reset scenes (ebc_set_obstacles); reset() calls it when maps are on."""
+        keep = []
+        o = self._obstacles(scene, keep)
+        ids = None if env_ids is None else np.ascontiguousarray(env_ids, dtype=np.int32)
+        _capi.check(self._L.ebc_set_obstacles(self._h, _np_ptr(ids), C.addressof(o)))
+
+    def set_obstacle_pool(self, scene):
+        """The polygons of the installed pool's scenes (ebc_set_obstacle_pool)."""
+        keep = []
+        o = self._obstacles(scene, keep)
+        _capi.check(self._L.ebc_set_obstacle_pool(self._h, C.addressof(o)))
+
+    def local_map(self):
+        """get_local_map_angular of every env's current state, float64 [E, dim] (ebc_local_map)."""
+        out = np.zeros((self.E, self.map_dim))
+        _capi.check(self._L.ebc_local_map(self._h, _abi.HOST, out.ctypes.data))
+        return out
+
+    def local_map_device(self, out):
+        """The same into a torch CUDA float64 [E, dim] tensor (enqueued on the handle's stream)."""
+        if out.dtype.itemsize != 8 or out.numel() != self.E * self.map_dim or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float64 [E, %d] tensor" % self.map_dim)
+        _capi.check(self._L.ebc_local_map(self._h, _abi.DEVICE, out.data_ptr()))
 
     # ------------------------------------------------------------------ scenes generated on the device
     # (SceneGenerator.generate_random_scene, scene_generator.py:330-378; gen = scene.gen_struct(cfg, phase))
@@ -156,7 +211,8 @@ class BatchedEnv:
         _capi.check(self._L.ebc_set_human_actions(self._h, _abi.HOST, a.ctypes.data))
 
     def step(self, robot_action=None, human_policy=_abi.HUMAN_ORCA,
-             robot_policy=_abi.ROBOT_EXTERNAL, flags=0, border=None, outputs=None):
+             robot_policy=_abi.ROBOT_EXTERNAL, flags=0, border=None, outputs=None, local_map=False):
+        """local_map=True: also out["local_map"] [E, dim], the map of the post-step state (ebc_step_with_map)."""
         E, N, R, T = self.E, self.N, self.R, self.T
         out = dict(reward=np.zeros(E), done=np.zeros(E, np.uint8), info=np.zeros(E, np.uint8),
                    dmin=np.zeros((E, 3)), dist_to_goal=np.zeros(E),
@@ -179,7 +235,11 @@ class BatchedEnv:
         args.flags = int(flags)
         for k, v in out.items():
             setattr(args, k, v.ctypes.data)
-        _capi.check(self._L.ebc_step(self._h, C.addressof(args)))
+        if local_map:
+            out["local_map"] = np.zeros((E, self.map_dim))
+            _capi.check(self._L.ebc_step_with_map(self._h, C.addressof(args), out["local_map"].ctypes.data))
+        else:
+            _capi.check(self._L.ebc_step(self._h, C.addressof(args)))
         return out
 
     def lookahead(self, actions, human_policy=_abi.HUMAN_ORCA, flags=0, border=None,
@@ -293,14 +353,15 @@ class BatchedEnv:
                       dist_to_goal=((E,), torch.float64),
                       robot_action_out=((E, 2), torch.float64),
                       human_action=((E, N, 2), torch.float64), ob=((E, R, 5), torch.float64),
-                      obs_rotated=((E, R, T), torch.float32))
+                      obs_rotated=((E, R, T), torch.float32), local_map=((E, self.map_dim), torch.float64))
         return {k: torch.zeros(shapes[k][0], dtype=shapes[k][1], device=dev) for k in keys}
 
     def step_device(self, outputs, robot_action=None, human_policy=_abi.HUMAN_ORCA,
                     robot_policy=_abi.ROBOT_EXTERNAL, flags=0):
         """Enqueue one step; `outputs`/`robot_action` are torch CUDA tensors (not copied).  The
         argument block is cached per (tensor addresses, policies, flags): a training loop that
-        re-uses its buffers pays one ctypes call per step."""
+        re-uses its buffers pays one ctypes call per step.  A "local_map" output [E, dim] makes it
+        ebc_step_with_map."""
         key = (tuple((k, t.data_ptr()) for k, t in outputs.items()),
                None if robot_action is None else robot_action.data_ptr(),
                int(human_policy), int(robot_policy), int(flags))
@@ -319,11 +380,19 @@ class BatchedEnv:
                     raise ValueError("robot_action must be contiguous")
                 args.robot_action = robot_action.data_ptr()
             for k, t in outputs.items():
+                if k == "local_map":
+                    if t.dtype.itemsize != 8 or t.numel() != self.E * self.map_dim or not t.is_contiguous():
+                        raise ValueError("local_map must be a contiguous float64 [E, %d] tensor" % self.map_dim)
+                    continue
                 setattr(args, k, t.data_ptr())
             if len(cache) > 64:
                 cache.clear()
             cache[key] = args
-        rc = self._L.ebc_step(self._h, C.addressof(args))
+        m = outputs.get("local_map")
+        if m is not None:
+            rc = self._L.ebc_step_with_map(self._h, C.addressof(args), m.data_ptr())
+        else:
+            rc = self._L.ebc_step(self._h, C.addressof(args))
         if rc:
             _capi.check(rc)
 

@@ -54,6 +54,7 @@ class EntityBasedCollisionAvoidance(object):
         self._device = device
         self._backend = None
         self._backend_key = None
+        self._device_map = False
         self.time_step = None
         self.time_limit = None
         self.robot = None
@@ -115,10 +116,26 @@ class EntityBasedCollisionAvoidance(object):
                 self._backend = BatchedEnv(params, 1, n_humans, n_static, device=self._device)
             self._params = params
             self._backend_key = key
+            # the angular local map on the device when the backend has it (the CPU tests' oracle backends do not:
+            # ebcsim/local_map.py serves them); a dim past the kernel's 128 sectors stays on the host as well
+            self._device_map = (hasattr(self._backend, "local_map") and hasattr(self._backend, "configure_local_map")
+                                and self.angular_map_dim <= _abi.LOCAL_MAP_MAX_DIM)
+            if self._device_map:
+                self._backend.configure_local_map(self.angular_map_dim, self.angular_map_max_range,
+                                                  self.angular_map_min_angle, self.angular_map_max_angle)
         return self._backend
 
+    def _current_map(self):
+        """get_local_map_angular(robot.get_full_state()) of the backend's current state, appended like the host's."""
+        if not self._device_map:
+            return self.get_local_map_angular(self.robot.get_full_state())
+        m = self._backend.local_map()[0]
+        self.local_maps_angular.append(m)
+        return m
+
     def get_local_map_angular(self, ob, normalize=True, append=True):
-        """simulator/env.py:570-628, on the host (ebcsim/local_map.py): no policy on the path reads it."""
+        """simulator/env.py:570-628 for an arbitrary state `ob`, on the host (ebcsim/local_map.py).  reset / step
+        take the map of the env's own state from the device instead (ebc_local_map, ebc_step_with_map)."""
         from .local_map import angular_map
         m = angular_map(self.scene.obstacle_vertices, ob.px, ob.py, ob.radius, ob.theta,
                         self.angular_map_max_range, self.angular_map_dim, self.angular_map_min_angle,
@@ -196,7 +213,7 @@ class EntityBasedCollisionAvoidance(object):
         if hasattr(self.robot.policy, "get_attention_weights"):
             self.attention_weights = list()
         ob = [h.get_observable_state() for h in self._humans] + sc.static_obstacles_as_pedestrians
-        local_map = self.get_local_map_angular(self.robot.get_full_state()) if compute_local_map else None
+        local_map = self._current_map() if compute_local_map else None
         if self.robot.policy is not None and self.robot.policy.name == "ORCA":
             return ob, sc.obstacle_vertices, local_map
         return ob, local_map
@@ -270,7 +287,7 @@ class EntityBasedCollisionAvoidance(object):
             dg = float(np.linalg.norm(np.array((nx, ny)) - np.array(self.robot.get_goal_position())))
             info = self._info(out["info"][0, 0], dg, out["dmin"][0, 0])
             # env.py:460-465: the map of the CURRENT robot state, also in look-ahead
-            local_map = self.get_local_map_angular(self.robot.get_full_state()) if compute_local_map else None
+            local_map = self._current_map() if compute_local_map else None
             return ob, local_map, float(out["reward"][0, 0]), bool(out["done"][0, 0]), info
 
         # render history: full states before the update (env.py:344-351)
@@ -283,8 +300,10 @@ class EntityBasedCollisionAvoidance(object):
         if hasattr(self.robot.policy, "get_attention_weights"):
             self.attention_weights.append(self.robot.policy.get_attention_weights())
 
-        out = b.step(robot_action=act, human_policy=self._humans_for_lookahead(), border=self._border(border))
-        self.backend_calls += 1
+        device_map = compute_local_map and self._device_map
+        out = b.step(robot_action=act, human_policy=self._humans_for_lookahead(), border=self._border(border),
+                     **({"local_map": True} if device_map else {}))
+        self.backend_calls += 1  # one step, with or without its map
         self._humans_cached = False  # the state has moved on
         st = b.get_state()
         r = st["robot"][0]
@@ -302,7 +321,11 @@ class EntityBasedCollisionAvoidance(object):
             k += len(group)
         ob = self._rows_to_ob(out["ob"][0])
         info = self._info(out["info"][0], out["dist_to_goal"][0], out["dmin"][0])
-        local_map = self.get_local_map_angular(self.robot.get_full_state()) if compute_local_map else None
+        if device_map:  # the same ebc_step_with_map call's map of the post-step state
+            local_map = out["local_map"][0]
+            self.local_maps_angular.append(local_map)
+        else:
+            local_map = self.get_local_map_angular(self.robot.get_full_state()) if compute_local_map else None
         return ob, local_map, float(out["reward"][0]), bool(out["done"][0]), info
 
     def render(self, mode="adult", output_file=None):

@@ -1,8 +1,9 @@
 """Angular local map of the static obstacles around the robot (simulator/env.py:468-628).
 
 Host-side (numpy scalars): SURVEY 8(f)(3) — the reference spends 95 % of `step` here when a scene
-has obstacles, yet no policy on the path reads the result (agents/robot.py:20-24 ignores
-`local_map`).  The facade therefore computes it only on request; the kernels do not."""
+has obstacles.  This restatement is what the device map (csrc/ebc_local_map.h, ebc_local_map /
+ebc_step_with_map) is checked against, and what the facade uses for an arbitrary state or a backend
+without the device map."""
 import math
 
 import numpy as np

@@ -485,6 +485,8 @@ class SceneBatch:
     sradius: np.ndarray
     grid: Optional[np.ndarray]
     robot: np.ndarray
+    n_poly: Optional[np.ndarray] = None  # [n] int32: obstacle polygons per scene (Scene.obstacle_vertices)
+    poly: Optional[np.ndarray] = None    # [n][max(S, 1)][4][2] float64: their vertices (the angular local map's input)
 
     @classmethod
     def from_scenes(cls, scenes: List[Scene], max_humans=None, max_static=None):
@@ -515,4 +517,12 @@ class SceneBatch:
             if b.grid is not None:
                 b.grid[e] = pack_grid(s.grid)
             b.robot[e] = s.robot
+        b.n_poly = np.zeros(n, np.int32)
+        b.poly = np.zeros((n, max(S, 1), 4, 2))
+        for e, s in enumerate(scenes):
+            v = np.asarray(s.obstacle_vertices, dtype=np.float64).reshape(-1, 4, 2)
+            if len(v) > max(S, 1) or (len(v) and not S):
+                raise ValueError("scene %d has more obstacle polygons than max_static" % e)
+            b.n_poly[e] = len(v)
+            b.poly[e, :len(v)] = v
         return b

@@ -373,6 +373,49 @@ int ebc_row_counts(void *handle, int location, long long *n_rows);
 int ebc_il_targets(void *stream, const double *reward, const uint8_t *done, const uint8_t *info, int K, int E,
                    double gamma_bar, double *values, uint8_t *keep);
 
+/* ---- get_local_map_angular on the device (simulator/env.py:468-628) ------------------------------------------
+ * env.reset and env.step return (ob, local_map, ...) with compute_local_map=True by default (env.py:188-205,
+ * :460-465): `dim` sector minima of the distances between the four corners of the robot's box and the obstacle
+ * polygons, in the robot's heading frame, / max_range when normalize.  Same arithmetic as the reference, operation
+ * for operation (csrc/ebc_local_map.h states the one place it may differ: atan2 picks sectors).
+ *   ebc_local_map_config: dim ([map] angular_map_dim, <= 128, else EBC_ERR_UNSUPPORTED), max_range
+ *     (angular_map_max_range), angle_min / angle_max in radians (angle_min * pi, env.py:80-84).  Allocates the
+ *     polygon storage: [E + P][S][4] vertices plus a count per scene slot — the slots of the occupancy grids (an
+ *     env's own ebc_reset slot, the pool's scenes).  Until this call nothing is allocated and nothing launched.
+ *   ebc_set_obstacles: the polygons (scene.obstacle_vertices, scene_generator.py:109-328) of the listed envs'
+ *     ebc_reset scenes (env_ids NULL = 0..n-1); ebc_set_obstacle_pool: those of the installed pool (n = its P).
+ *     Every polygon is an axis-aligned 4-vertex rectangle (all the generator and saved scenes hold); anything
+ *     else, or more than S polygons, is EBC_ERR_INVALID.  ebc_generate_reset / ebc_generate_pool write the
+ *     polygons of the scenes they generate themselves.
+ *   ebc_reset marks its envs' slots unset, ebc_set_scene_pool the pool's (ebc_generate_pool sets them): a map is
+ *     EBC_ERR_STATE, naming the env or pool scene, while any slot an env can reach is unset.
+ *   ebc_local_map: out [E][dim] float64, the map of the CURRENT state — what env.reset returns and what the
+ *     look-ahead returns (env.py:460-465 with update=False).
+ *   ebc_step_with_map: ebc_step, plus local_map [E][dim] of each env's post-step state (with EBC_FLAG_AUTO_RESET
+ *     a terminal env's is that of its terminal state, like every other output of the step).  Same refusals as
+ *     ebc_step; the map is worked out from the pre-step state and the step's robot action. */
+typedef struct EbcLocalMapParams {
+  uint32_t struct_size;
+  int32_t dim;
+  double max_range;
+  double angle_min, angle_max;
+  int32_t normalize;
+  int32_t reserved;
+} EbcLocalMapParams;
+
+typedef struct EbcObstacles {
+  uint32_t struct_size;
+  int32_t n;
+  const int32_t *n_poly;  /* [n] polygons per scene, <= S */
+  const double *vertices; /* [n][S][4][2] host */
+} EbcObstacles;
+
+int ebc_local_map_config(void *handle, const EbcLocalMapParams *params);
+int ebc_set_obstacles(void *handle, const int32_t *env_ids, const EbcObstacles *obstacles);
+int ebc_set_obstacle_pool(void *handle, const EbcObstacles *obstacles);
+int ebc_local_map(void *handle, int location, double *out);
+int ebc_step_with_map(void *handle, const EbcStepArgs *args, double *local_map);
+
 /* Geometry of the handle (E, N, S, T, G). */
 int ebc_dims(void *handle, int32_t out[5]);
 
