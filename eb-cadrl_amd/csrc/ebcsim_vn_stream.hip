@@ -3,6 +3,7 @@
 // translation unit: seconds to compile beside the general blocks' minutes.
 #include <hip/hip_runtime.h>
 
+#include <cmath>
 #include <cstdlib>
 
 #include "ebc_vn_stream.h"
@@ -75,7 +76,10 @@ namespace ebc {
 
 // One workgroup per env.  Ranking by counting (A <= 1024 values in LDS: action i's rank = the number of actions with a
 // larger value, or the same value and a lower index): a full sort of every env's row, a dozen element-wise launches and a
-// sort in torch before.
+// sort in torch before.  A NaN compares false with everything, so the non-NaN values rank among themselves (0 .. n - 1)
+// and the NaNs take the ranks after them in index order: `order` is a permutation whatever the row holds.  The best
+// value and the near-best count are taken over the non-NaN values; a row the coarse values cannot rank (a NaN in it, or
+// no value above -inf) gets count -1: every action of it is a candidate.
 __global__ __launch_bounds__(128) void decision_rank_kernel(const float *v, const double *reward, double discount, double bound, int A,
                                                              double *values, int *order, int *count) {
   __shared__ double vals[1024];
@@ -86,28 +90,37 @@ __global__ __launch_bounds__(128) void decision_rank_kernel(const float *v, cons
     const double x = reward[(size_t)e * A + i] + discount * (double)v[(size_t)e * A + i];
     vals[i] = x;
     values[(size_t)e * A + i] = x;
-    order[(size_t)e * A + i] = i;  // (a NaN among the values leaves ranks unassigned: every entry stays a valid action)
   }
   __syncthreads();
-  int mine = 0;
   for (int i = threadIdx.x; i < A; i += blockDim.x) {
     const double x = vals[i];
     int rank = 0;
-    for (int j = 0; j < A; ++j) rank += (vals[j] > x || (vals[j] == x && j < i)) ? 1 : 0;
+    if (x == x) {
+      for (int j = 0; j < A; ++j) rank += (vals[j] > x || (vals[j] == x && j < i)) ? 1 : 0;
+    } else {  // every non-NaN value, and the NaNs of lower index
+      for (int j = 0; j < A; ++j) rank += (vals[j] == vals[j] || j < i) ? 1 : 0;
+    }
     order[(size_t)e * A + rank] = i;
   }
-  // the best value is the one of rank 0: found again by a max over the row (cheap), then the near-best count
-  double best = vals[0];
-  for (int j = 1; j < A; ++j) best = vals[j] > best ? vals[j] : best;
+  // the best non-NaN value: found again by a max over the row (cheap), then the near-best count
+  double best = -INFINITY;
+  bool nan = false;
+  for (int j = 0; j < A; ++j) {
+    best = vals[j] > best ? vals[j] : best;
+    nan = nan || vals[j] != vals[j];
+  }
   const double floor_ = best - bound;
+  int mine = 0;
   for (int i = threadIdx.x; i < A; i += blockDim.x) mine += vals[i] >= floor_ ? 1 : 0;
   atomicAdd(&near, mine);
   __syncthreads();
-  if (threadIdx.x == 0) count[e] = near;
+  if (threadIdx.x == 0) count[e] = (nan || !(best > -INFINITY)) ? -1 : near;
 }
 
 // values[env][act] = reward + discount * exact for the re-evaluated candidates; the largest |exact - coarse| among them
-// (non-negative floats order like their bit patterns: an atomic max on the bits; a NaN lands above every bound)
+// (non-negative floats order like their bit patterns: an atomic max on the bits).  A pair that is the same value (the
+// same infinity included) or NaN in both forms differs by 0; any other pair with a NaN in it differs by a NaN, which
+// lands above every bound.
 __global__ __launch_bounds__(256) void decision_apply_kernel(const float *exact, const float *v, const long long *env, const long long *act,
                                                               const double *reward, double discount, int A, int n, double *values,
                                                               unsigned *worst_bits) {
@@ -115,8 +128,8 @@ __global__ __launch_bounds__(256) void decision_apply_kernel(const float *exact,
   float d = 0.0f;
   if (i < n) {
     const size_t at = (size_t)env[i] * A + (size_t)act[i];
-    const float x = exact[i];
-    d = fabsf(x - v[at]);
+    const float x = exact[i], c = v[at];
+    d = (x == c || (x != x && c != c)) ? 0.0f : fabsf(x - c);
     values[at] = reward[at] + discount * (double)x;
   }
   unsigned bits = __float_as_uint(d);
@@ -143,8 +156,8 @@ extern "C" int ebc_decision_apply(void *stream, const float *exact, const float 
 
 extern "C" int ebc_decision_rank(void *stream, const float *v, const double *reward, double discount, double bound, int E, int A,
                                  double *values, int32_t *order, int32_t *count) {
-  if (!v || !reward || !values || !order || !count || E < 0 || A <= 0 || A > 1024)
-    return ebc_host::fail(EBC_ERR_INVALID, "decision_rank arguments (1 <= A <= 1024)");
+  if (!v || !reward || !values || !order || !count || E < 0 || A <= 0 || A > 1024 || !(bound >= 0.0))
+    return ebc_host::fail(EBC_ERR_INVALID, "decision_rank arguments (1 <= A <= 1024, bound >= 0)");
   if (E == 0) return EBC_OK;
   hipLaunchKernelGGL(ebc::decision_rank_kernel, dim3((unsigned)E), dim3(128), 0, (hipStream_t)stream, v, reward, discount, bound, A, values,
                      order, count);

@@ -14,6 +14,7 @@ import torch
 from .action import ActionRot, ActionXY
 from .actions import build_action_space
 from .policy import Policy
+from .sarl import reference_choice
 
 
 def _dims(config, key):
@@ -134,9 +135,7 @@ class SARL(Policy):
             reward = torch.from_numpy(np.ascontiguousarray(sweep["reward"], dtype=np.float64)).to(self.device)
             values = net.action_values(rows[None], reward[None], discount)[0].cpu().numpy()
             self.action_values = [float(x) for x in values]
-            if np.isnan(values).all():
-                raise ValueError("Value network is not well trained. ")
-            chosen = self.action_space[int(np.nanargmax(values))]  # first maximum, like `value > max_value`
+            chosen = self.action_space[int(reference_choice(values[None])[0])]
         if self.phase == "train":
             self.last_state = self.transform(state, env)
         return chosen

@@ -27,6 +27,30 @@ def uniform_v_pref(env):
     return float(v[0])
 
 
+def reference_choice(values, check=True):
+    """The reference's choice over the action values (multi_human_rl.py:36-80: max_value = -inf, then
+    `if value > max_value`): values [E, A] float64 (torch or numpy) -> the chosen action of every env [E].  The first
+    maximum wins and a NaN is never chosen; an env with no value above -inf raises the reference's ValueError (on a
+    device that test is a host round trip; check=False skips it for values known to pass it)."""
+    if isinstance(values, np.ndarray):
+        v = np.where(np.isnan(values), -np.inf, values)
+        if check and not bool((v > -np.inf).any(1).all()):
+            raise ValueError("Value network is not well trained. ")
+        return v.argmax(1)
+    v = values.masked_fill(torch.isnan(values), float("-inf"))
+    if check and not bool((v > float("-inf")).any(1).all()):
+        raise ValueError("Value network is not well trained. ")
+    return torch.argmax(v, dim=1)  # the first maximal index
+
+
+def _out(out, shape, dtype, device):
+    """A wrapper's output: `out` when the caller passes one (checked: shape, dtype, contiguous), else a new tensor."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous(), (tuple(out.shape), shape, out.dtype)
+    return out
+
+
 def _mlp(x, layers, last_relu):
     """Linear (+ ReLU) stack.  On the GPU the bias and the ReLU ride in the GEMM's epilogue
     (torch._addmm_activation -> hipBLASLt): same values, no separate pass over the activations."""
@@ -72,9 +96,9 @@ class _NativeMlp2(object):
         return torch.empty(((M + 31) // 32, (width + 31) // 32, 2, 2, 64, 4), dtype=torch.int32, device=device)
 
     def forward_ex(self, M, relu_out, x=None, frag_in=None, row_bias=None, group_rows=0, want_y=True, seg_rows=0,
-                   row_weight=None, want_partial=False, frag_out=None, general=False):
+                   row_weight=None, want_partial=False, frag_out=None, general=False, y_out=None, partial_out=None):
         """Every form of the forward in one call (ebc_mlp2_forward_ex): rows or fragments in; rows, per-group partial
-        sums and / or fragments out.  -> (y or None, partial or None)."""
+        sums and / or fragments out.  -> (y or None, partial or None); y_out / partial_out: the caller's buffers."""
         from . import _capi
         dev = (x if x is not None else frag_in).device
         a = _abi.EbcMlpArgs()
@@ -92,21 +116,21 @@ class _NativeMlp2(object):
             row_weight = row_weight.contiguous(); keep.append(row_weight); a.row_weight = row_weight.data_ptr()
         y = partial = None
         if want_y:
-            y = torch.empty((M,) if self.has_final else (M, self.O), dtype=torch.float32, device=dev)
+            y = _out(y_out, (M,) if self.has_final else (M, self.O), torch.float32, dev)
             a.y = y.data_ptr()
         if want_partial:
-            partial = torch.empty(((M + 31) // 32, 3, self.O), dtype=torch.float64, device=dev)
+            partial = _out(partial_out, ((M + 31) // 32, 3, self.O), torch.float64, dev)
             a.partial = partial.data_ptr()
         if frag_out is not None:
             a.frag_out = frag_out.data_ptr()
         _capi.check(self._L.ebc_mlp2_forward_ex(self._h, torch.cuda.current_stream(dev).cuda_stream, self._C.addressof(a)))
         return y, partial
 
-    def __call__(self, x, relu_out, row_bias=None, group_rows=0):
+    def __call__(self, x, relu_out, row_bias=None, group_rows=0, out=None):
         from . import _capi
         x = x.contiguous()
         shape = (x.shape[0],) if self.has_final else (x.shape[0], self.O)
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        y = _out(out, shape, torch.float32, x.device)
         if row_bias is not None:
             row_bias = row_bias.contiguous()
         _capi.check(self._L.ebc_mlp2_forward(self._h, torch.cuda.current_stream(x.device).cuda_stream,
@@ -128,13 +152,13 @@ class _NativeMlp2(object):
                                             t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
                                             None if f is None else f[0].data_ptr(), None if f is None else f[1].data_ptr()))
 
-    def f32(self, x, relu_out, row_bias=None, group_rows=0):
+    def f32(self, x, relu_out, row_bias=None, group_rows=0, out=None):
         """The same block in plain float32 on the vector ALUs (ebc_mlp2_forward_f32): float32-GEMM-grade values for the
         few rows that decide an argmax."""
         from . import _capi
         x = x.contiguous()
         shape = (x.shape[0],) if self.has_final else (x.shape[0], self.O)
-        y = torch.empty(shape, dtype=torch.float32, device=x.device)
+        y = _out(out, shape, torch.float32, x.device)
         if row_bias is not None:
             row_bias = row_bias.contiguous()
         _capi.check(self._L.ebc_mlp2_forward_f32(self._h, torch.cuda.current_stream(x.device).cuda_stream,
@@ -267,34 +291,34 @@ class SarlValueNet(object):
         return True
 
     @staticmethod
-    def _pair_mean(h1, nv64, B, R):
+    def _pair_mean(h1, nv64, B, R, out=None):
         """sarl.py:56-58 in one pass over h1 (libebcsim ebc_pair_mean)."""
         from . import _capi
         h1 = h1.contiguous()
-        g = torch.empty((B, h1.shape[1]), dtype=torch.float32, device=h1.device)
+        g = _out(out, (B, h1.shape[1]), torch.float32, h1.device)
         _capi.check(_capi.lib().ebc_pair_mean(torch.cuda.current_stream(h1.device).cuda_stream, h1.data_ptr(),
                                               None if nv64 is None else nv64.data_ptr(), B, R, int(h1.shape[1]),
                                               g.data_ptr()))
         return g
 
     @staticmethod
-    def _pair_attend(scores, feat, nv64, B, R):
+    def _pair_attend(scores, feat, nv64, B, R, out=None):
         """sarl.py:69-76 in one pass over the features (libebcsim ebc_pair_attend)."""
         from . import _capi
         scores, feat = scores.contiguous(), feat.contiguous()
-        out = torch.empty((B, feat.shape[2]), dtype=torch.float32, device=feat.device)
+        out = _out(out, (B, feat.shape[2]), torch.float32, feat.device)
         _capi.check(_capi.lib().ebc_pair_attend(torch.cuda.current_stream(feat.device).cuda_stream, scores.data_ptr(),
                                                 feat.data_ptr(), None if nv64 is None else nv64.data_ptr(), B, R,
                                                 int(feat.shape[2]), out.data_ptr()))
         return out
 
     @staticmethod
-    def _pair_combine(partial, nv64, B, R, mean):
+    def _pair_combine(partial, nv64, B, R, mean, out=None):
         """Per-pair sums of a block's tile partials (libebcsim ebc_pair_combine): the pair mean (sarl.py:56-58) or,
         with the attention weights as row weights, the weighted feature sum (sarl.py:73-76)."""
         from . import _capi
         O = int(partial.shape[2])
-        out = torch.empty((B, O), dtype=torch.float32, device=partial.device)
+        out = _out(out, (B, O), torch.float32, partial.device)
         _capi.check(_capi.lib().ebc_pair_combine(torch.cuda.current_stream(partial.device).cuda_stream, partial.data_ptr(),
                                                  None if nv64 is None else nv64.data_ptr(), B, R, O, int(bool(mean)),
                                                  out.data_ptr()))
@@ -375,11 +399,15 @@ class SarlValueNet(object):
         whose coarse value lies within 2 * discount * eps of the env's coarse best — any action whose float32 value could
         be the maximum — is re-evaluated with the float32 form of the same blocks (ebc_mlp2_forward_f32) before the
         caller takes the argmax (an env with a single such candidate is decided already and keeps its matrix-core
-        value); the bound is checked on those candidates (a violation widens it and repeats the
-        selection).  refine: None = this bound-driven set; an int k = the best k candidates of every env (0 = the
+        value); the bound is checked on those candidates (a violation widens it and repeats the selection from the
+        coarse values; after four violations every action of the batch is re-evaluated).  An env whose coarse values
+        hold a NaN, or none above -inf, is re-evaluated in full; one whose float32 values have none above -inf raises
+        the reference's ValueError (values_decidable: True when no env needed that; the first maximum is then the choice).
+        refine: None = this bound-driven set; an int k = the best k candidates of every env (0 = the
         matrix-core values as they are).  refine_stats counts decisions, re-evaluated candidates, envs with more than two
-        of them, the largest set, and bound violations."""
+        of them, the largest set, bound violations and fallbacks to the whole batch."""
         E, A, R, T = rows.shape
+        self.values_decidable = False  # set where the float32 selection leaves no NaN and a value above -inf in every env
         step = E if not chunk_pairs else max(1, int(chunk_pairs) // A)
         v = torch.empty((E, A), dtype=torch.float32, device=rows.device)
         n_chunks = -(-E // step)
@@ -434,40 +462,49 @@ class SarlValueNet(object):
         elif getattr(self, "coarse_eps", None) is None:
             self.calibrate_eps(rows.reshape(E * A, R, T), None if n_valid is None else n_valid.repeat_interleave(A))
         st = self.__dict__.setdefault("_refine_host", {"decisions": 0, "candidates": 0, "over2": 0, "capped": 0, "max_set": 0,
-                                                       "bound_violations": 0, "contested": 0})
+                                                       "bound_violations": 0, "contested": 0, "fallbacks": 0})
+        st.setdefault("fallbacks", 0)
         k = min(self.REFINE_CAP, A)
         ar = np.arange(E)
+        discount = float(discount)
+        # the candidates that could be the float32 best: a PREFIX of every env's sorted row, so the set is its length.
+        # The lengths go to the host in one 8 KB copy — the one host round trip of the selection — and the index lists
+        # and the counters are made there: torch.nonzero plus four .item() reads were five round trips with an idle GPU
+        # and a dozen launch-bound little kernels behind each.
+        count = count_dev.cpu().numpy().astype(np.int64)
+        # -1: the coarse values cannot rank the env (a NaN among them, or none above -inf).  All of its actions are
+        # re-evaluated, once, and its errors are not held against the bound (a coarse NaN has no error to measure); then
+        # the reference's rule decides it, and without a value above -inf it is the reference's ValueError.
+        full = count < 0
+        n_full = int(full.sum())
+        if n_full:
+            fe = np.nonzero(full)[0]
+            self._apply_exact(rows, n_valid, np.repeat(fe, A), np.tile(np.arange(A), n_full), reward, v, discount, values,
+                              torch.zeros(1, dtype=torch.float32, device=rows.device), E)
+            fe_dev = torch.from_numpy(fe).to(rows.device)
+            if not bool((values[fe_dev] > float("-inf")).any(1).all()):
+                raise ValueError("Value network is not well trained. ")
+        ranked = None
         for attempt in range(4):
-            bound = 2.0 * float(discount) * self.coarse_eps
-            # the candidates that could be the float32 best: a PREFIX of every env's sorted row, so the set is its length.
-            # The lengths go to the host in one 8 KB copy — the one host round trip of the selection — and the index
-            # lists and the counters are made there: torch.nonzero plus four .item() reads were five round trips with an
-            # idle GPU and a dozen launch-bound little kernels behind each.
-            if attempt == 0:
-                count = count_dev.cpu().numpy().astype(np.int64)
-            else:  # the bound was widened: the sizes again, from the ranked values
-                ranked = values.gather(1, order.to(torch.int64))
+            if attempt:  # the bound was widened: the sizes again, from the COARSE values by rank (a longer prefix)
+                bound = 2.0 * discount * self.coarse_eps
+                if ranked is None:
+                    ranked = (reward + discount * v.to(torch.float64)).gather(1, order.to(torch.int64))
                 count = (ranked >= (ranked[:, :1] - bound)).sum(1).cpu().numpy()
-            count = np.minimum(count, k)
+            count = np.where(full, A, np.minimum(count, k))
             # an env with ONE candidate is decided: every other action's float32 value lies below that one's
-            sizes = np.where(count > 1, count, 0)
+            sizes = np.where((count > 1) & ~full, count, 0)
             n_cand = int(sizes.sum())
             if n_cand == 0:
-                exact = None
                 break
             env_h = np.repeat(ar, sizes)
             slot_h = np.arange(n_cand) - np.repeat(np.cumsum(sizes) - sizes, sizes)
             idx = torch.from_numpy(np.stack([env_h, slot_h])).to(rows.device, non_blocking=True)
-            env_i, slot = idx[0], idx[1]
-            act_i = order[env_i, slot].to(torch.int64)
-            nv = None if n_valid is None else n_valid[env_i]
-            exact = self.forward(rows[env_i, act_i], nv, exact=True).to(torch.float32).contiguous()
+            act_i = order[idx[0], idx[1]].to(torch.int64)
             # the candidates' float32 values into `values`, and the bound checked where it matters: one launch, one read
-            # (a widened bound below selects a superset and applies again)
+            # (a widened bound below selects a longer prefix and applies again)
             worst_dev = torch.zeros(1, dtype=torch.float32, device=rows.device)
-            _capi.check(_capi.lib().ebc_decision_apply(torch.cuda.current_stream(rows.device).cuda_stream, exact.data_ptr(), v.data_ptr(),
-                                                       env_i.contiguous().data_ptr(), act_i.contiguous().data_ptr(), reward.data_ptr(),
-                                                       float(discount), A, n_cand, values.data_ptr(), worst_dev.data_ptr()))
+            self._apply_exact(rows, n_valid, idx[0], act_i, reward, v, discount, values, worst_dev, E)
             worst = float(worst_dev)
             if worst <= self.coarse_eps:
                 break
@@ -475,18 +512,53 @@ class SarlValueNet(object):
             if not worst <= self.COARSE_EPS_MAX:
                 raise RuntimeError("SarlValueNet: matrix-core values off by %.2e: not fit to rank this network's values" % worst)
             self.coarse_eps = self.EPS_MARGIN * worst
+        else:
+            # every widening pulled in a larger error: the bound has not settled, so every action of the batch is
+            # re-evaluated in float32 and the decision is the float32 network's; the errors seen widen the bound
+            live = np.nonzero(~full)[0]
+            worst_dev = torch.zeros(1, dtype=torch.float32, device=rows.device)
+            self._apply_exact(rows, n_valid, np.repeat(live, A), np.tile(np.arange(A), len(live)), reward, v, discount, values,
+                              worst_dev, step)
+            worst = float(worst_dev)
+            if not worst <= self.COARSE_EPS_MAX:
+                raise RuntimeError("SarlValueNet: matrix-core values off by %.2e: not fit to rank this network's values" % worst)
+            self.coarse_eps = max(self.coarse_eps, self.EPS_MARGIN * worst)
+            st["fallbacks"] += 1
+            count = np.full(E, A, dtype=np.int64)
+            n_cand = len(live) * A
         st["decisions"] += E
-        st["candidates"] += n_cand
+        st["candidates"] += n_cand + n_full * A
         st["contested"] += int((count > 1).sum())
         st["over2"] += int((count > 2).sum())
         st["capped"] += int((count >= k).sum()) if k < A else 0
-        st["max_set"] = max(st["max_set"], int(count.max()))
+        st["max_set"] = max(st["max_set"], int(count.max()) if E else 0)
+        # no NaN is left and every env has a value above -inf: a NaN in the coarse values flags its env, any other NaN
+        # error raised above; the flagged envs' float32 values may hold NaNs (reference_choice masks them)
+        self.values_decidable = n_full == 0
         return values
+
+    def _apply_exact(self, rows, n_valid, env_i, act_i, reward, v, discount, values, worst_dev, chunk_envs):
+        """The float32 form of the network on the pairs (env_i, act_i) (host arrays or device tensors), written into
+        `values` as reward + discount * value with the largest |float32 - coarse| among them into worst_dev
+        (ebc_decision_apply; worst_dev is not read here).  At most chunk_envs * A pairs per forward."""
+        from . import _capi
+        A = values.shape[1]
+        if not torch.is_tensor(env_i):
+            env_i, act_i = (torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64)).to(rows.device) for t in (env_i, act_i))
+        n, step = int(env_i.shape[0]), max(1, int(chunk_envs)) * A
+        for p0 in range(0, n, step):
+            e_i, a_i = (env_i, act_i) if step >= n else (env_i[p0:p0 + step].contiguous(), act_i[p0:p0 + step].contiguous())
+            nv = None if n_valid is None else n_valid[e_i]
+            exact = self.forward(rows[e_i, a_i], nv, exact=True).to(torch.float32).contiguous()
+            _capi.check(_capi.lib().ebc_decision_apply(torch.cuda.current_stream(rows.device).cuda_stream, exact.data_ptr(), v.data_ptr(),
+                                                       e_i.data_ptr(), a_i.data_ptr(), reward.data_ptr(), discount, A,
+                                                       int(e_i.shape[0]), values.data_ptr(), worst_dev.data_ptr()))
 
     @property
     def refine_stats(self):
         """Counters of the bound-driven re-evaluation since the network was made: decisions, re-evaluated candidates, envs
-        with more than one / more than two candidates, sets cut at REFINE_CAP, the largest set, bound violations."""
+        with more than one / more than two candidates, sets cut at REFINE_CAP, the largest set, bound violations, and
+        decisions whose bound did not settle in four attempts (every action re-evaluated)."""
         st = self.__dict__.get("_refine_host")
         return None if st is None else dict(st)
 
@@ -662,5 +734,12 @@ class DeviceSarlPolicy(object):
         env.lookahead_device(self._acts, self._bufs, human_policy=human_policy)
         values = self.values_from(self._bufs["rows_rotated"], self._bufs["reward"], self.n_valid,
                                   env.params.time_step, self._v_pref)
-        best = torch.argmax(values, dim=1)
-        return self._acts[best], values
+        return self._acts[self.choose(values)], values
+
+    def choose(self, values):
+        """The reference's choice over values [E, A] (reference_choice).  Values that action_values' float32 selection
+        left without a NaN and with a value above -inf in every env (values_decidable) need neither the NaN mask nor
+        the host round trip of the check: the first maximum is the reference's choice."""
+        if getattr(self.net, "values_decidable", False):
+            return torch.argmax(values, dim=1)
+        return reference_choice(values)

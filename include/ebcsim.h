@@ -515,16 +515,21 @@ int ebc_pair_weights(void *stream, const float *scores, const long long *n_valid
 
 /* The argmax side of MultiHumanRL.predict for a batch (rl/policy/multi_human_rl.py:72-80), one launch:
  *   values [E][A] (float64) = reward + discount * v      (v [E][A]: the value network's float32 outputs)
- *   order  [E][A] (int32)   = each env's actions by value, best first (equal values: the lower action index first)
- *   count  [E]    (int32)   = how many of them lie within `bound` of the env's best: the prefix of `order` that can
- *                             hold the float32 network's best action when the values carry an error of bound / 2
- * Device pointers; A <= 1024.  (What ebcsim.sarl.SarlValueNet.action_values selects its re-evaluated candidates from.) */
+ *   order  [E][A] (int32)   = each env's actions by value, best first (equal values: the lower action index first);
+ *                             NaN values last, in index order: always a permutation of 0 .. A - 1
+ *   count  [E]    (int32)   = how many of them lie within `bound` of the env's best non-NaN value: the prefix of `order`
+ *                             that can hold the float32 network's best action when the values carry an error of
+ *                             bound / 2; -1 when the values cannot rank the env (a NaN among them, or none above -inf):
+ *                             every action of it is a candidate
+ * Device pointers; 1 <= A <= 1024, bound >= 0.  (What ebcsim.sarl.SarlValueNet.action_values selects its re-evaluated
+ * candidates from.) */
 int ebc_decision_rank(void *stream, const float *v, const double *reward, double discount, double bound, int E, int A,
                       double *values, int32_t *order, int32_t *count);
 /* The re-evaluated candidates back into the values, one launch: for i < n, values[env[i]][act[i]] = reward[env[i]][act[i]] +
  * discount * exact[i] (exact: the float32 network's values of the n candidates; env / act: int64 indices), and
  * *worst (float, zeroed by the caller) = max_i |exact[i] - v[env[i]][act[i]]| — the error of the matrix-core values
- * where it matters, which the caller holds against its bound.  Device pointers. */
+ * where it matters, which the caller holds against its bound.  A pair that is NaN in both forms, or the same infinity,
+ * differs by 0; any other NaN difference makes *worst a NaN (above every bound).  Device pointers. */
 int ebc_decision_apply(void *stream, const float *exact, const float *v, const long long *env, const long long *act,
                        const double *reward, double discount, int A, int n, double *values, float *worst);
 int ebc_pair_mask(void *stream, const long long *n_valid, int B, int R, float *w);

@@ -323,3 +323,65 @@ def check_il_persistent(make_env, name, copies=1):
                 differs = differs or not np.allclose(a[0], z["action%d" % k][t], atol=1e-9, rtol=0)
                 env.step(robot_action=np.tile(z["action%d" % k][t], (copies, 1)), human_policy=_abi.HUMAN_ORCA)
         assert differs
+
+
+def reference_rule(row):
+    """The reference's choice of an action from its values, as it runs it (rl/policy/multi_human_rl.py:36-80): a scalar
+    loop from max_value = -inf that takes an action when `value > max_value` — so the first maximum wins, a NaN is never
+    taken, and a row with no value above -inf leaves max_action None, which raises."""
+    max_value = float("-inf")
+    max_action = None
+    for action, value in enumerate(row):
+        if value > max_value:
+            max_value = value
+            max_action = action
+    if max_action is None:
+        raise ValueError("Value network is not well trained. ")
+    return max_action
+
+
+class Guarded:
+    """A device buffer of any shape and dtype with a canary on each side, for the outputs a kernel writes.  Each canary is
+    at least 64 KiB and at least 8 row tiles of the buffer (8 * tile_rows rows: the span of one workgroup), so a write
+    past either end lands in a canary instead of the caching allocator's slack.  With poison (the default) the inside
+    starts as a byte pattern no kernel writes, and check() asserts that every element was overwritten — for buffers whose
+    contract says every element is written.  `t` is the view the kernel gets."""
+    CANARY, POISON = 0xB6, 0xA5
+
+    def __init__(self, shape, dtype, tile_rows=32, poison=True, device="cuda"):
+        import torch
+        self.shape = tuple(int(s) for s in shape)
+        self.isz = torch.empty((), dtype=dtype).element_size()
+        self.nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.isz
+        row = int(np.prod(self.shape[1:], dtype=np.int64)) * self.isz
+        self.pad = -(-max(64 << 10, 8 * tile_rows * row) // 256) * 256  # the inside keeps the allocation's alignment
+        self.raw = torch.full((2 * self.pad + self.nbytes,), self.CANARY, dtype=torch.uint8, device=device)
+        self.poison = bool(poison)
+        if poison:
+            self.raw[self.pad:self.pad + self.nbytes].fill_(self.POISON)
+        self.t = self.raw[self.pad:self.pad + self.nbytes].view(dtype).view(self.shape)
+        self.ptr = self.raw.data_ptr() + self.pad  # the inside's address, also when it is empty (t.data_ptr() is 0 then)
+        self.np_dtype = torch.empty((), dtype=dtype).numpy().dtype
+
+    def check(self, written=None):
+        """Asserts both canaries are intact; written (default: whether the buffer was poisoned) asserts that no element
+        still holds the poison, written=False that every one does (nothing written).  -> the inside on the host."""
+        b = self.raw.cpu().numpy()
+        lo, inside, hi = b[:self.pad], b[self.pad:self.pad + self.nbytes], b[self.pad + self.nbytes:]
+        bad = np.nonzero(lo != self.CANARY)[0]
+        assert not len(bad), "write before the buffer %s: %d canary bytes, the first %d bytes before it" % (
+            self.shape, len(bad), self.pad - bad[0])
+        bad = np.nonzero(hi != self.CANARY)[0]
+        assert not len(bad), "write past the end of the buffer %s: %d canary bytes, the last %d bytes after it" % (
+            self.shape, len(bad), bad[-1] + 1)
+        if written is None:
+            written = self.poison if self.poison else None
+        if written is not None:
+            assert self.poison, "check(written=...) needs a poisoned buffer"
+            untouched = (inside.reshape(-1, self.isz) == self.POISON).all(1)
+            if written:
+                assert not untouched.any(), "%d of %d elements of %s not written (the first: %d)" % (
+                    int(untouched.sum()), len(untouched), self.shape, int(np.argmax(untouched)))
+            else:
+                assert untouched.all(), "%d elements of %s written" % (int((~untouched).sum()), self.shape)
+        return inside.view(self.np_dtype).reshape(self.shape)

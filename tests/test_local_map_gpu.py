@@ -9,15 +9,15 @@ import os
 
 import numpy as np
 import pytest
+import torch
 
 from ebcsim import _abi, _capi, config as ebc_config, scene as ebc_scene
-from helpers import GOLDEN
+from helpers import GOLDEN, Guarded
 from test_local_map_cpu import (ROOT, _bench_scene_cfg, _bits_equal, _build, _check_pose, _fixture_cases,
                                 _static_known_answer)
 
 pytestmark = pytest.mark.gpu
 PI = np.pi
-CANARY = 64
 
 
 @pytest.fixture(scope="module")
@@ -67,20 +67,6 @@ def _assert_device_equals_host(lib, dev, host, polys, n_poly, robot, what):
     return len(bad)
 
 
-class Guarded:
-    """A torch float64 [E, dim] map buffer with CANARY words before and after it."""
-
-    def __init__(self, E, dim):
-        import torch
-        self.buf = torch.full((E * dim + 2 * CANARY,), -7.25, dtype=torch.float64, device="cuda")
-        self.t = self.buf[CANARY:CANARY + E * dim].view(E, dim)
-
-    def check(self):
-        b = self.buf.cpu().numpy()
-        assert (b[:CANARY] == -7.25).all() and (b[-CANARY:] == -7.25).all(), "map buffer overrun"
-        return b[CANARY:-CANARY].reshape(tuple(self.t.shape))
-
-
 def _env(params, E, N, S):
     from ebcsim.batched import BatchedEnv
     return BatchedEnv(params, E, N, S, device=0)
@@ -110,7 +96,7 @@ def test_goldens(fixture, host_lib):
         env = _env(_abi.default_params(), len(pose), 1, 20)
         env.configure_local_map(m["dim"], m["max_range"], m["angle_min"], m["angle_max"], m.get("normalize", True))
         env.reset(_pose_batch(m["vertices"], pose, 20))
-        g = Guarded(env.E, m["dim"])
+        g = Guarded((env.E, m["dim"]), torch.float64)
         env.local_map_device(g.t)
         env.synchronize()  # enqueued on the handle's stream
         got = g.check()
@@ -187,7 +173,7 @@ def _auto_reset_run(robot_policy, E=256, P=64, steps=200):
     A, B, Ctwin = envs
     rs = np.random.RandomState(3)
     first_done = np.full(E, -1)
-    g = Guarded(E, 48)
+    g = Guarded((E, 48), torch.float64)
     oa = A.alloc_step_outputs(KEYS)
     oa["local_map"] = g.t
     for t in range(steps):

@@ -1,10 +1,14 @@
 """Dense blocks of the SARL value network on the bf16 matrix cores with split operands
-(csrc/ebc_value_net.h) against torch float32."""
+(csrc/ebc_value_net.h) against torch float32.  Every buffer a kernel writes is a guarded one (tests/helpers.py: Guarded):
+a canary on each side catches a write past its ends, and where every element is to be written a poison fill catches
+one that was not."""
 import ctypes as C
 
 import numpy as np
 import pytest
 import torch
+
+from helpers import Guarded
 
 
 def _lib():
@@ -12,10 +16,28 @@ def _lib():
     return _capi.lib()
 
 
+def _y(blk, M):
+    """A guarded output of a block's forward: [M] with the one-output tail, else [M, O]."""
+    return Guarded((M,) if blk.has_final else (M, blk.O), torch.float32)
+
+
+def _part(M, O):
+    """A guarded partial-sums output [ceil(M / 32)][3][O] (one row tile per entry of the first dimension)."""
+    return Guarded(((M + 31) // 32, 3, O), torch.float64, tile_rows=1)
+
+
+def _frag(M, width):
+    """A guarded fragment buffer, _NativeMlp2.frag_buffer's [row tiles][column tiles][2][2][64] x 16 B (a row tile per
+    entry of the first dimension)."""
+    return Guarded(((M + 31) // 32, (width + 31) // 32, 2, 2, 64, 4), torch.int32, tile_rows=1)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("K0,H,O,M,relu_out", [(17, 300, 200, 1000, 1), (13, 150, 100, 333, 1),
                                                (200, 200, 100, 515, 0), (100, 100, 50, 64, 0),
-                                               (200, 200, 1, 2049, 0), (5, 7, 3, 31, 1)])
+                                               (200, 200, 1, 2049, 0), (5, 7, 3, 31, 1)]
+                         + [(17, 300, 200, M, 1) for M in (1, 17, 18, 31, 33)]
+                         + [(200, 200, 100, M, 0) for M in (1, 33)])
 def test_mlp2_split_bf16_matches_float32(K0, H, O, M, relu_out):
     import torch
     from ebcsim import _capi
@@ -30,14 +52,14 @@ def test_mlp2_split_bf16_matches_float32(K0, H, O, M, relu_out):
     _capi.check(L.ebc_mlp2_create(0, K0, H, O, w1.ctypes.data, b1.ctypes.data, w2.ctypes.data, b2.ctypes.data,
                                   None, None, C.byref(h)))
     xd = torch.from_numpy(x).cuda()
-    yd = torch.zeros((M, O), dtype=torch.float32, device="cuda")
+    yg = Guarded((M, O), torch.float32)
     torch.cuda.synchronize()
-    _capi.check(L.ebc_mlp2_forward(h, None, xd.data_ptr(), M, relu_out, None, 0, yd.data_ptr()))
+    _capi.check(L.ebc_mlp2_forward(h, None, xd.data_ptr(), M, relu_out, None, 0, yg.t.data_ptr()))
     torch.cuda.synchronize()
     ref = np.maximum(x.astype(np.float64) @ w1.T.astype(np.float64) + b1, 0) @ w2.T.astype(np.float64) + b2
     if relu_out:
         ref = np.maximum(ref, 0)
-    got = yd.cpu().numpy()
+    got = yg.check()
     f32 = torch.nn.functional.linear(torch.relu(torch.nn.functional.linear(torch.from_numpy(x), torch.from_numpy(w1), torch.from_numpy(b1))), torch.from_numpy(w2), torch.from_numpy(b2)).numpy()
     if relu_out:
         f32 = np.maximum(f32, 0)
@@ -68,15 +90,15 @@ def test_mlp2_attention_form(K0, H, O, R, B):
     _capi.check(L.ebc_mlp2_create(0, K0, H, O, w1.ctypes.data, b1.ctypes.data, w2.ctypes.data, b2.ctypes.data,
                                   w3.ctypes.data, b3.ctypes.data, C.byref(h)))
     xd, gd = torch.from_numpy(x).cuda(), torch.from_numpy(g).cuda()
-    yd = torch.zeros(M, dtype=torch.float32, device="cuda")
+    yg = Guarded((M,), torch.float32)
     torch.cuda.synchronize()
-    _capi.check(L.ebc_mlp2_forward(h, None, xd.data_ptr(), M, 0, gd.data_ptr(), R, yd.data_ptr()))
+    _capi.check(L.ebc_mlp2_forward(h, None, xd.data_ptr(), M, 0, gd.data_ptr(), R, yg.t.data_ptr()))
     torch.cuda.synchronize()
     x64, g64 = x.astype(np.float64), np.repeat(g.astype(np.float64), R, axis=0)
     a1 = np.maximum(x64 @ w1.T.astype(np.float64) + b1 + g64, 0)
     a2 = np.maximum(a1 @ w2.T.astype(np.float64) + b2, 0)
     ref = a2 @ w3.astype(np.float64) + b3[0]
-    err = np.abs(yd.cpu().numpy() - ref).max()
+    err = np.abs(yg.check() - ref).max()
     assert err <= 4e-5 * max(np.abs(ref).max(), 1.0), err
     _capi.check(L.ebc_mlp2_destroy(h))
 
@@ -103,9 +125,12 @@ def test_pair_glue_matches_torch(B, R, H, F, ragged):
     ref_g = (h.view(B, R, H) * valid[:, :, None]).sum(1) / denom
     e = torch.exp(scores) * (scores != 0).float() * valid
     ref_o = ((e / e.sum(1, keepdim=True)).unsqueeze(2) * feat).sum(1)
-    got_g = SarlValueNet._pair_mean(h, nv, B, R)
-    got_o = SarlValueNet._pair_attend(scores, feat, nv, B, R)
+    gg, go = Guarded((B, H), torch.float32), Guarded((B, F), torch.float32)
+    got_g = SarlValueNet._pair_mean(h, nv, B, R, out=gg.t)
+    got_o = SarlValueNet._pair_attend(scores, feat, nv, B, R, out=go.t)
     torch.cuda.synchronize()
+    gg.check()
+    go.check()
     torch.testing.assert_close(got_g, ref_g, atol=2e-6, rtol=1e-5)
     torch.testing.assert_close(got_o, ref_o, atol=2e-6, rtol=1e-5)
 
@@ -133,27 +158,32 @@ def test_mlp2_reduce_epilogue_gives_pair_sums(K0, H, O, R, B, ragged, store):
     h = C.c_void_p()
     _capi.check(L.ebc_mlp2_create(0, K0, H, O, w1.ctypes.data, b1.ctypes.data, w2.ctypes.data, b2.ctypes.data, None, None, C.byref(h)))
     xd = torch.from_numpy(x).cuda()
-    plain = torch.zeros((M, O), dtype=torch.float32, device="cuda")
+    plain_g = Guarded((M, O), torch.float32)
+    plain = plain_g.t
     _capi.check(L.ebc_mlp2_forward(h, None, xd.data_ptr(), M, 1, None, 0, plain.data_ptr()))
     nvd = None if nv is None else torch.from_numpy(nv).cuda()
     nvp = None if nvd is None else nvd.data_ptr()
     # (a) mean: weights = the mask (or none)
-    wd = None
+    wd = wg = None
     if nvd is not None:
-        wd = torch.zeros(M, dtype=torch.float32, device="cuda")
+        wg = Guarded((M,), torch.float32)
+        wd = wg.t
         _capi.check(L.ebc_pair_mask(None, nvp, B, R, wd.data_ptr()))
-    yd = torch.full((M, O), -7.0, dtype=torch.float32, device="cuda")
-    part = torch.full(((M + 31) // 32, 3, O), float("nan"), dtype=torch.float64, device="cuda")
-    _capi.check(L.ebc_mlp2_forward_reduce(h, None, xd.data_ptr(), M, 1, None, 0, yd.data_ptr() if store else None, R,
-                                          None if wd is None else wd.data_ptr(), part.data_ptr()))
-    mean = torch.zeros((B, O), dtype=torch.float32, device="cuda")
-    _capi.check(L.ebc_pair_combine(None, part.data_ptr(), nvp, B, R, O, 1, mean.data_ptr()))
+    yg = Guarded((M, O), torch.float32)
+    part = _part(M, O)
+    _capi.check(L.ebc_mlp2_forward_reduce(h, None, xd.data_ptr(), M, 1, None, 0, yg.t.data_ptr() if store else None, R,
+                                          None if wd is None else wd.data_ptr(), part.t.data_ptr()))
+    mean_g = Guarded((B, O), torch.float32)
+    mean = mean_g.t
+    _capi.check(L.ebc_pair_combine(None, part.t.data_ptr(), nvp, B, R, O, 1, mean.data_ptr()))
     torch.cuda.synchronize()
-    rows = plain.cpu().numpy().astype(np.float64).reshape(B, R, O)
+    rows = plain_g.check().astype(np.float64).reshape(B, R, O)
+    for buf in (part, mean_g) + (() if wg is None else (wg,)):
+        buf.check()
     if store:
-        np.testing.assert_array_equal(yd.cpu().numpy(), plain.cpu().numpy())
+        np.testing.assert_array_equal(yg.check(), plain.cpu().numpy())
     else:
-        assert (yd.cpu().numpy() == -7.0).all()
+        yg.check(written=False)  # the rows are not written at all
     valid = np.ones((B, R)) if nv is None else (np.arange(R)[None, :] < nv[:, None]).astype(np.float64)
     want = (rows * valid[:, :, None]).sum(1) / valid.sum(1)[:, None]
     np.testing.assert_allclose(mean.cpu().numpy(), want, rtol=2e-6, atol=2e-6 * np.abs(rows).max())
@@ -162,14 +192,18 @@ def test_mlp2_reduce_epilogue_gives_pair_sums(K0, H, O, R, B, ragged, store):
     sc[rs.rand(B, R) < 0.1] = 0.0
     sc[:, 0] = np.where(sc[:, 0] == 0, 0.5, sc[:, 0])  # at least one live row per pair
     scd = torch.from_numpy(sc).cuda()
-    w = torch.zeros(M, dtype=torch.float32, device="cuda")
+    w_g = Guarded((M,), torch.float32)
+    w = w_g.t
     _capi.check(L.ebc_pair_weights(None, scd.data_ptr(), nvp, B, R, w.data_ptr()))
-    _capi.check(L.ebc_mlp2_forward_reduce(h, None, xd.data_ptr(), M, 1, None, 0, None, R, w.data_ptr(), part.data_ptr()))
-    att = torch.zeros((B, O), dtype=torch.float32, device="cuda")
-    _capi.check(L.ebc_pair_combine(None, part.data_ptr(), None, B, R, O, 0, att.data_ptr()))
-    old = torch.zeros((B, O), dtype=torch.float32, device="cuda")
+    part = _part(M, O)
+    _capi.check(L.ebc_mlp2_forward_reduce(h, None, xd.data_ptr(), M, 1, None, 0, None, R, w.data_ptr(), part.t.data_ptr()))
+    att_g, old_g = Guarded((B, O), torch.float32), Guarded((B, O), torch.float32)
+    att, old = att_g.t, old_g.t
+    _capi.check(L.ebc_pair_combine(None, part.t.data_ptr(), None, B, R, O, 0, att.data_ptr()))
     _capi.check(L.ebc_pair_attend(None, scd.data_ptr(), plain.data_ptr(), nvp, B, R, O, old.data_ptr()))
     torch.cuda.synchronize()
+    for buf in (w_g, part, att_g, old_g):
+        buf.check()
     e = np.exp(sc.astype(np.float64)) * (sc != 0) * valid
     wt = e / e.sum(1, keepdims=True)
     np.testing.assert_allclose(w.cpu().numpy().reshape(B, R), wt, rtol=3e-6, atol=1e-7)
@@ -190,9 +224,11 @@ def test_mlp2_reduce_refuses_what_it_cannot_do():
     h = C.c_void_p()
     _capi.check(L.ebc_mlp2_create(0, 5, 8, 4, w1.ctypes.data, b1.ctypes.data, w2.ctypes.data, b2.ctypes.data, None, None, C.byref(h)))
     x = torch.zeros((64, 5), device="cuda")
-    part = torch.zeros((2, 3, 4), dtype=torch.float64, device="cuda")
-    assert L.ebc_mlp2_forward_reduce(h, None, x.data_ptr(), 64, 1, None, 0, None, 8, None, part.data_ptr()) == -2  # EBC_ERR_UNSUPPORTED: groups of 8 rows
-    assert L.ebc_mlp2_forward_reduce(h, None, x.data_ptr(), 64, 1, None, 0, None, 16, None, part.data_ptr()) == -2  # a block of 1 + 1 tiles has no tile epilogue
+    part = _part(64, 4)
+    assert L.ebc_mlp2_forward_reduce(h, None, x.data_ptr(), 64, 1, None, 0, None, 8, None, part.t.data_ptr()) == -2  # EBC_ERR_UNSUPPORTED: groups of 8 rows
+    assert L.ebc_mlp2_forward_reduce(h, None, x.data_ptr(), 64, 1, None, 0, None, 16, None, part.t.data_ptr()) == -2  # a block of 1 + 1 tiles has no tile epilogue
+    torch.cuda.synchronize()
+    part.check(written=False)
     _capi.check(L.ebc_mlp2_destroy(h))
 
 
@@ -216,8 +252,12 @@ def test_block_repacked_on_the_device_equals_the_host_pack():
         b.update([(w.to(dev), bb.to(dev)) for w, bb in want_l], None if want_f is None else tuple(t.to(dev) for t in want_f))
         torch.cuda.synchronize()
         for relu in (True, False):
-            assert torch.equal(a(x, relu), b(x, relu)), (K0, H, O, relu)
-            assert torch.equal(a.f32(x, relu), b.f32(x, relu)), (K0, H, O, relu)
+            for form in ("__call__", "f32"):
+                ya, yb = _y(a, 1000), _y(b, 1000)
+                getattr(a, form)(x, relu, out=ya.t)
+                getattr(b, form)(x, relu, out=yb.t)
+                torch.cuda.synchronize()
+                assert np.array_equal(ya.check(), yb.check()), (K0, H, O, relu, form)
 
 
 @pytest.mark.gpu
@@ -238,23 +278,29 @@ def test_float32_block_is_float32_gemm_grade():
 
 
 def _check_f32_block(blk, M, K0, H, O, w1, b1, w2, b2, fin, group, g, dev):
-    if True:
-        x = torch.randn(M, K0, generator=g)
-        rb = torch.randn((M + 17) // 18, H, generator=g) if group else None
+    """The block on M random rows against float64, no further from it than 3x torch's float32 GEMMs (or 2e-6); then the
+    tails — one row, a part-filled tile, one pair, a tile and one row — on the first rows of the same batch, held to the
+    same bound (the float32 error of the batch they belong to: a max over a handful of rows says little)."""
+    x = torch.randn(M, K0, generator=g)
+    rb = torch.randn((M + 17) // 18, H, generator=g) if group else None
 
-        def ref(dt):
-            h = torch.nn.functional.linear(x.to(dt), w1.to(dt), b1.to(dt))
-            if rb is not None:
-                h = h + rb.to(dt).repeat_interleave(18, 0)[:M]
-            y = torch.nn.functional.linear(torch.relu(h), w2.to(dt), b2.to(dt))
-            if fin is not None:  # the one-output tail acts on relu(out): the attention stack's third layer (sarl.py:25-27)
-                y = torch.nn.functional.linear(torch.relu(y), fin[0].to(dt), fin[1].to(dt)).squeeze(1)
-            return y
-        got = blk.f32(x.to(dev), False, row_bias=None if rb is None else rb.to(dev), group_rows=18 if group else 0).cpu()
-        exact = ref(torch.float64)
-        err_native = float((got.double() - exact).abs().max())
-        err_torch = float((ref(torch.float32).double() - exact).abs().max())
-        assert err_native <= max(3.0 * err_torch, 2e-6), (K0, H, O, err_native, err_torch)
+    def ref(dt):
+        h = torch.nn.functional.linear(x.to(dt), w1.to(dt), b1.to(dt))
+        if rb is not None:
+            h = h + rb.to(dt).repeat_interleave(18, 0)[:M]
+        y = torch.nn.functional.linear(torch.relu(h), w2.to(dt), b2.to(dt))
+        if fin is not None:  # the one-output tail acts on relu(out): the attention stack's third layer (sarl.py:25-27)
+            y = torch.nn.functional.linear(torch.relu(y), fin[0].to(dt), fin[1].to(dt)).squeeze(1)
+        return y
+    exact = ref(torch.float64)
+    err_torch = float((ref(torch.float32).double() - exact).abs().max())
+    for m in (M, 1, 17, 18, 31, 33):
+        yg = _y(blk, m)
+        blk.f32(x[:m].to(dev), False, row_bias=None if rb is None else rb[:(m + 17) // 18].to(dev), group_rows=18 if group else 0,
+                out=yg.t)
+        got = torch.from_numpy(yg.check())
+        err_native = float((got.double() - exact[:m]).abs().max())
+        assert err_native <= max(3.0 * err_torch, 2e-6), (K0, H, O, M, m, err_native, err_torch)
 
 
 @pytest.mark.gpu
@@ -302,14 +348,17 @@ def test_streamed_attention_block_equals_the_general_block_bit_for_bit():
         src = _NativeMlp2([(torch.randn(64, 17, generator=g), torch.randn(64, generator=g)),
                            (torch.randn(K0, 64, generator=g) / 8, torch.randn(K0, generator=g))], 0)
         blk = _NativeMlp2([(w1, b1), (w2, b2)], 0, final=fin, in_fragments=True)
-        for M in (18 * 600, 18 * 57 + 5, 31, 32 * 8 * 3 + 1):
+        for M in (18 * 600, 18 * 57 + 5, 31, 32 * 8 * 3 + 1, 18):
             x = torch.randn(M, 17, generator=g).to(dev)
-            frag = _NativeMlp2.frag_buffer(M, K0, dev)
-            src.forward_ex(M, True, x=x, want_y=False, seg_rows=18, want_partial=True, frag_out=frag)
+            frag, part = _frag(M, K0), _part(M, K0)
+            src.forward_ex(M, True, x=x, want_y=False, seg_rows=18, want_partial=True, frag_out=frag.t, partial_out=part.t)
             rb = torch.randn((M + 17) // 18, H, generator=g).to(dev)
-            a, _ = blk.forward_ex(M, False, frag_in=frag, row_bias=rb, group_rows=18)
-            b, _ = blk.forward_ex(M, False, frag_in=frag, row_bias=rb, group_rows=18, general=True)
+            ya, yb = _y(blk, M), _y(blk, M)
+            a, _ = blk.forward_ex(M, False, frag_in=frag.t, row_bias=rb, group_rows=18, y_out=ya.t)
+            b, _ = blk.forward_ex(M, False, frag_in=frag.t, row_bias=rb, group_rows=18, general=True, y_out=yb.t)
             torch.cuda.synchronize()
+            for buf in (frag, part, ya, yb):
+                buf.check()
             assert torch.equal(a, b), (K0, H, O, M, float((a - b).abs().max()))
             assert bool(torch.isfinite(a).all()) and float(a.abs().max()) > 0
 
@@ -339,16 +388,22 @@ def test_streamed_feature_block_equals_the_general_block_to_rounding():
                 x[7 * R:8 * R] = pair
                 x[33 * R:34 * R] = pair  # the same pair at another place of the batch (another tile alignment)
             x = x.to(dev)
-            frag = _NativeMlp2.frag_buffer(M, K0, dev)
-            rows, _ = src.forward_ex(M, True, x=x, want_y=True, seg_rows=R, want_partial=True, frag_out=frag)
+            frag, rows_g, part0 = _frag(M, K0), _y(src, M), _part(M, K0)
+            rows, _ = src.forward_ex(M, True, x=x, want_y=True, seg_rows=R, want_partial=True, frag_out=frag.t, y_out=rows_g.t,
+                                     partial_out=part0.t)
             w = torch.rand(M, generator=g).to(dev)
             if B > 40:
                 w[33 * R:34 * R] = w[7 * R:8 * R]
-            out = {}
+            out, guards = {}, [frag, rows_g, part0]
             for general in (False, True):
-                _, part = blk.forward_ex(M, False, frag_in=frag, want_y=False, seg_rows=R, row_weight=w, want_partial=True, general=general)
-                out[general] = SarlValueNet._pair_combine(part, None, B, R, False)
+                part, comb = _part(M, O), Guarded((B, O), torch.float32)
+                blk.forward_ex(M, False, frag_in=frag.t, want_y=False, seg_rows=R, row_weight=w, want_partial=True, general=general,
+                               partial_out=part.t)
+                out[general] = SarlValueNet._pair_combine(part.t, None, B, R, False, out=comb.t)
+                guards += [part, comb]
             torch.cuda.synchronize()
+            for buf in guards:
+                buf.check()
             h = torch.relu(torch.nn.functional.linear(rows.double().cpu(), w1[0].double(), w1[1].double()))
             yref = torch.nn.functional.linear(h, w2[0].double(), w2[1].double())
             ref = (yref * w.double().cpu()[:, None]).view(B, R, O).sum(1)
@@ -384,13 +439,17 @@ def test_streamed_first_block_equals_the_general_block_to_rounding():
             mask[35 * R:36 * R] = mask[9 * R:10 * R]
         xd, md = x.to(dev), mask.to(dev)
         out = {}
+        guards = []
         for general in (False, True):
-            frag = _NativeMlp2.frag_buffer(M, O, dev)
-            frag.zero_()
-            _, part = blk.forward_ex(M, True, x=xd, want_y=False, seg_rows=R, row_weight=md, want_partial=True, frag_out=frag, general=general)
-            f = frag.view(torch.bfloat16).float()                      # [tile][column tile][k-step][hi, lo][lane][8]
-            out[general] = (SarlValueNet._pair_combine(part, None, B, R, False), f[:, :, :, 0] + f[:, :, :, 1])
+            frag, part, comb = _frag(M, O), _part(M, O), Guarded((B, O), torch.float32)
+            blk.forward_ex(M, True, x=xd, want_y=False, seg_rows=R, row_weight=md, want_partial=True, frag_out=frag.t, general=general,
+                           partial_out=part.t)
+            f = frag.t.view(torch.bfloat16).float()                    # [tile][column tile][k-step][hi, lo][lane][8]
+            out[general] = (SarlValueNet._pair_combine(part.t, None, B, R, False, out=comb.t), f[:, :, :, 0] + f[:, :, :, 1])
+            guards += [frag, part, comb]
         torch.cuda.synchronize()
+        for buf in guards:
+            buf.check()
         h = torch.relu(torch.nn.functional.linear(x.double(), w1[0].double(), w1[1].double()))
         yref = torch.relu(torch.nn.functional.linear(h, w2[0].double(), w2[1].double()))
         ref = (yref * mask.double()[:, None]).view(B, R, O).sum(1)
