@@ -1,0 +1,574 @@
+// ebc_rollout.h — ebc_step_k with EBC_FLAG_ONE_LAUNCH: K env.step calls of every env in ONE kernel launch.
+//
+// Scenes are independent, so K fused steps need no grid barrier and no hand-off between workgroups: one workgroup
+// (EBC_RO_THREADS threads) owns `epg` consecutive envs for all K steps.  Their state is read once, lives in LDS for
+// the whole launch and is written back once; per step only the requested outputs, robot_action[k], the window of the
+// occupancy grid and — when an env ends under auto-reset — its restart scene cross the memory system.  The phases of
+// a step are separated by two workgroup barriers; there are no mailboxes and no polling, hence no give-up path.
+//
+//   P1   (pre-step state)
+//        all threads   state_rotated[k] rows -> LDS row buffer (they leave as 16-byte stores after the barrier)
+//        last wave     the robot side of the step, which needs nothing from the humans' ORCA: n_rows[k]; the robot's
+//                      action (EBC_ROBOT_LINEAR / _EXTERNAL: a lane per env; EBC_ROBOT_ORCA: a 32-lane ORCA group per
+//                      env over the N + S observation rows, with the persistent simulator when it is enabled); swept
+//                      robot-human distances, a lane per human; then a lane per env: ordered per-type reduce, grid
+//                      window, reward / done / info, the robot's next state and its frame
+//        every wave    the humans' ORCA velocities, GS lanes per human, from the LDS tile (the last wave takes a
+//                      share only when the robot is not on ORCA)
+//   P3a  a thread per human: move, first arrival, next tile record, its obs_rotated[k] row; static and padding rows
+//   P3b  (only in a workgroup where an env ended under auto-reset, behind a third barrier) the restart scene
+//
+// What is shared and what is restated.  The leaf arithmetic is called, not copied: orca_group, orca_pref_velocity /
+// orca_pref_from, closest_dist, grid_collision, reward_compute, linear_policy, robot_advance, rot_frame, rotate_row.
+// Restated here, because the per-step bodies read DevState arrays in global memory and their instruction sequence is
+// the measured headline (ebc_kernels.h is not touched by this form): the row set-up and persistent-simulator rule of
+// orca_robot_kernel, orca_tile_load + orca_wave_compute, the ordered per-type reduce of env_lane_role, and the
+// commit / restart of state_role with the pool-cursor walk.  Each block below names the function it restates; a
+// change to one of those has to be made here too, and the raw-byte tests fail on the GPU when it is not.
+//
+// The arithmetic is that of the per-step form, operation for operation (ebc_device.h, ebc_orca_group.h; the unit is
+// built with -ffp-contract=off): what the per-step kernels compute across several waves and launches is computed
+// here from the same inputs in the same order, so every output and the state left behind are bit-identical
+// (tests/test_step_k_one_launch_gpu.py holds that bar).  The width of the robot's ORCA group differs from the
+// per-step form's (32 lanes here, the smallest instantiated size >= N + S there): lanes past the valid rows rank
+// at +inf and are masked out of every ballot, so the width cannot change a result.
+#pragma once
+
+#include "ebc_kernels.h"
+
+namespace ebc {
+
+#define EBC_RO_THREADS 256
+#define EBC_RO_WAVES (EBC_RO_THREADS / EBC_WAVE)
+#define EBC_RO_RW 32       // lanes of the robot's ORCA group (check_robot_orca: N + S <= 32)
+#define EBC_RO_MAX_EPG 16  // envs per workgroup, at most
+#define EBC_RO_TMAX 17     // widest rotated row
+// Waves per SIMD the register budget is set for = workgroups per CU.  Measured at 4096 x 10 (DESIGN.md section 3,
+// item 15; GS = 9): without a budget the kernel takes 236 registers — the robot side (grid window, reward,
+// double-precision policy) is the part that wants them; at 4 (128) it spills 93 of them to scratch and every
+// workgroup of the launch is resident at once; at 5 and 6 (115 / 197 spilled) the step is slower again.
+#ifndef EBC_RO_OCC
+#define EBC_RO_OCC 4
+#endif
+
+struct RolloutIO {
+  int K, robot_policy, auto_reset, epg;
+  int T;  // floats per rotated row (13 or 17)
+  double safety_space;
+  RobotSim sim;
+  const double *robot_action;
+  float *state_rotated;
+  long long *n_rows;
+  double *robot_action_out, *reward;
+  uint8_t *done, *info;
+  double *dmin, *dist_to_goal;
+  float *obs_rotated;
+};
+
+// Byte offsets of the workgroup's LDS arrays (each 16-byte aligned).  Host and device use the same function.
+struct RolloutLds {
+  unsigned hum;    // 9 arrays [epg * N] of double: px py vx vy gx gy radius v_pref arrival
+  unsigned type;   // [epg * N] int
+  unsigned tile;   // [2 * epg * N] float4 (DevState::tile layout)
+  unsigned stat;   // 3 arrays [epg * S] of double: spx spy sradius
+  unsigned robot, rn;  // [epg][9] double: current / next robot state
+  unsigned act;        // [epg][2] double
+  unsigned gtime, tnew;  // [epg] double
+  unsigned dist;       // [epg * N] double: swept distances
+  unsigned vel;        // [epg * N] float2: the humans' ORCA velocities
+  unsigned ints;       // 7 arrays [epg] of int: n, ns, slot, cursor, done, sim_rows, restore
+  unsigned sim_self;   // [epg] float2
+  unsigned sim_radius;  // [epg * R] float
+  unsigned frame_cur, frame_next;  // [epg] RotFrame: the robot-centric frame of the current / the next robot state
+  unsigned rows_state, rows_obs;  // [epg * R * T] float each
+  unsigned scratch, scratch_stride;  // EBC_RO_WAVES ORCA scratch areas
+  unsigned bytes;
+};
+__host__ __device__ inline RolloutLds rollout_lds(int epg, int N, int S, int T, unsigned scratch_bytes) {
+  RolloutLds L;
+  unsigned o = 0;
+  auto take = [&](unsigned bytes) {
+    const unsigned at = o;
+    o += (bytes + 15u) & ~15u;
+    return at;
+  };
+  const unsigned HN = (unsigned)epg * N, R = (unsigned)(N + S);
+  L.hum = take(9 * HN * 8);
+  L.type = take(HN * 4);
+  L.tile = take(2 * HN * 16);
+  L.stat = take(3 * (unsigned)epg * (S ? S : 1) * 8);
+  L.robot = take((unsigned)epg * 72);
+  L.rn = take((unsigned)epg * 72);
+  L.act = take((unsigned)epg * 16);
+  L.gtime = take((unsigned)epg * 8);
+  L.tnew = take((unsigned)epg * 8);
+  L.dist = take(HN * 8);
+  L.vel = take(HN * 8);
+  L.ints = take(7 * (unsigned)epg * 4);
+  L.sim_self = take((unsigned)epg * 8);
+  L.sim_radius = take((unsigned)epg * R * 4);
+  L.frame_cur = take((unsigned)epg * sizeof(RotFrame));
+  L.frame_next = take((unsigned)epg * sizeof(RotFrame));
+  L.rows_state = take((unsigned)epg * R * T * 4);
+  L.rows_obs = take((unsigned)epg * R * T * 4);
+  L.scratch_stride = (scratch_bytes + 15u) & ~15u;
+  L.scratch = take(EBC_RO_WAVES * L.scratch_stride);
+  L.bytes = o;
+  return L;
+}
+
+template <int GS>
+struct RolloutScratch {
+  static constexpr unsigned A = (unsigned)OrcaLds<GS>::BYTES, B = (unsigned)OrcaLds<EBC_RO_RW>::BYTES;
+  static constexpr unsigned BYTES = A > B ? A : B;
+};
+
+// `cnt` floats of an LDS row buffer -> dst, in flat order: 16-byte stores between the first and the last 16-byte
+// boundary of the destination (a row's 4 T bytes are not a multiple of 16: see lookahead_kernel, phase C).
+__device__ __forceinline__ void rollout_flush_rows(const float *buf, float *dst, int cnt, int tid) {
+  int head = (int)(((16 - ((size_t)dst & 15)) & 15) >> 2);
+  head = head < cnt ? head : cnt;
+  if (tid < head) dst[tid] = buf[tid];
+  const int body4 = (cnt - head) / 4;
+  typedef float f32x4 __attribute__((ext_vector_type(4)));
+  for (int v = tid; v < body4; v += EBC_RO_THREADS) {
+    const int f = head + 4 * v;
+    const f32x4 w = {buf[f], buf[f + 1], buf[f + 2], buf[f + 3]};
+    __builtin_nontemporal_store(w, reinterpret_cast<f32x4 *>(dst + f));  // nothing on the device reads the rows again
+  }
+  const int tail0 = head + 4 * body4;
+  if (tid < cnt - tail0) dst[tail0 + tid] = buf[tail0 + tid];
+}
+
+// the first T floats of a rotated row into an LDS row buffer
+__device__ __forceinline__ void rollout_put_row(float *dst, const float (&out)[EBC_RO_TMAX], int T) {
+#pragma unroll
+  for (int c = 0; c < EBC_RO_TMAX; ++c)
+    if (c < T) dst[c] = out[c];
+}
+
+template <int GS>
+__global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutIO io) {
+  extern __shared__ __align__(16) unsigned char ro_lds[];
+  const int tid = threadIdx.x, lane = tid & (EBC_WAVE - 1), wave = tid / EBC_WAVE;
+  const int N = s.N, S = s.S, R = N + S, EPG = io.epg, T = io.T, E = s.E;
+  const int e0 = (int)blockIdx.x * EPG;
+  const int envs = min(EPG, E - e0);  // the last workgroup may own fewer
+  const int HN = envs * N, SN = envs * S, RN = envs * R;
+  const RolloutLds L = rollout_lds(EPG, N, S, T, RolloutScratch<GS>::BYTES);
+  double *const hum = reinterpret_cast<double *>(ro_lds + L.hum);
+  const int HS = EPG * N;  // stride between the human arrays
+  double *const h_px = hum, *const h_py = hum + HS, *const h_vx = hum + 2 * HS, *const h_vy = hum + 3 * HS;
+  double *const h_gx = hum + 4 * HS, *const h_gy = hum + 5 * HS, *const h_rad = hum + 6 * HS, *const h_vpref = hum + 7 * HS;
+  double *const h_arr = hum + 8 * HS;
+  int *const h_type = reinterpret_cast<int *>(ro_lds + L.type);
+  float4 *const tile = reinterpret_cast<float4 *>(ro_lds + L.tile);
+  const int SS = EPG * (S ? S : 1);
+  double *const st_x = reinterpret_cast<double *>(ro_lds + L.stat), *const st_y = st_x + SS, *const st_r = st_x + 2 * SS;
+  double *const robot = reinterpret_cast<double *>(ro_lds + L.robot);
+  double *const robot_next = reinterpret_cast<double *>(ro_lds + L.rn);
+  double *const act = reinterpret_cast<double *>(ro_lds + L.act);
+  double *const gtime = reinterpret_cast<double *>(ro_lds + L.gtime);
+  double *const tnew = reinterpret_cast<double *>(ro_lds + L.tnew);
+  double *const dist = reinterpret_cast<double *>(ro_lds + L.dist);
+  float2 *const vel = reinterpret_cast<float2 *>(ro_lds + L.vel);
+  int *const n_h = reinterpret_cast<int *>(ro_lds + L.ints), *const n_s = n_h + EPG, *const slot = n_h + 2 * EPG;
+  int *const cursor = n_h + 3 * EPG, *const done = n_h + 4 * EPG, *const sim_rows = n_h + 5 * EPG, *const restore = n_h + 6 * EPG;
+  float2 *const sim_self = reinterpret_cast<float2 *>(ro_lds + L.sim_self);
+  float *const sim_radius = reinterpret_cast<float *>(ro_lds + L.sim_radius);
+  RotFrame *const frame_cur = reinterpret_cast<RotFrame *>(ro_lds + L.frame_cur);
+  RotFrame *const frame_next = reinterpret_cast<RotFrame *>(ro_lds + L.frame_next);
+  float *const rows_state = reinterpret_cast<float *>(ro_lds + L.rows_state);
+  float *const rows_obs = reinterpret_cast<float *>(ro_lds + L.rows_obs);
+  unsigned char *const scratch = ro_lds + L.scratch + (unsigned)wave * L.scratch_stride;
+  const ScenePool &P = s.pool;
+  const double dt = p.time_step;
+  const bool robot_orca = io.robot_policy == EBC_ROBOT_ORCA;
+
+  // ---- the envs' state: global memory -> LDS, once
+  for (int q = tid; q < HN; q += EBC_RO_THREADS) {
+    const size_t k = (size_t)e0 * N + q;
+    h_px[q] = s.px[k]; h_py[q] = s.py[k]; h_vx[q] = s.vx[k]; h_vy[q] = s.vy[k];
+    h_gx[q] = s.gx[k]; h_gy[q] = s.gy[k]; h_rad[q] = s.radius[k]; h_vpref[q] = s.v_pref[k];
+    h_arr[q] = s.arrival[k];
+    h_type[q] = s.type[k];
+    tile[2 * q] = s.tile[2 * k];
+    tile[2 * q + 1] = s.tile[2 * k + 1];
+  }
+  for (int q = tid; q < SN; q += EBC_RO_THREADS) {
+    const size_t k = (size_t)e0 * S + q;
+    st_x[q] = s.spx[k]; st_y[q] = s.spy[k]; st_r[q] = s.sradius[k];
+  }
+  for (int q = tid; q < envs * 9; q += EBC_RO_THREADS) robot[q] = s.robot[(size_t)e0 * 9 + q];
+  if (tid < envs) {
+    const size_t e = (size_t)e0 + tid;
+    gtime[tid] = s.time[e];
+    n_h[tid] = s.n_humans[e];
+    n_s[tid] = S ? s.n_static[e] : 0;
+    slot[tid] = s.grid_scene[e];
+    cursor[tid] = P.P > 0 ? P.cursor[e] : (int)e;  // without a custom pool an env restarts from its own slot
+    done[tid] = s.done[e];
+    if (io.sim.rows) {
+      sim_rows[tid] = io.sim.rows[e];
+      sim_self[tid] = io.sim.self[e];
+    }
+  }
+  if (io.sim.rows)
+    for (int q = tid; q < RN; q += EBC_RO_THREADS) sim_radius[q] = io.sim.radius[(size_t)e0 * R + q];
+  __syncthreads();
+  if (io.state_rotated) {
+    if (tid < envs) frame_cur[tid] = rot_frame(robot + tid * 9, p.rotate_unicycle);
+    __syncthreads();
+  }
+
+  const int human_passes = (HN + (EBC_WAVE / GS) - 1) / (EBC_WAVE / GS);
+  const int robot_passes = robot_orca ? (envs + (EBC_WAVE / EBC_RO_RW) - 1) / (EBC_WAVE / EBC_RO_RW) : 0;
+
+  // The robot side of a step runs on the LAST wave (its ORCA groups or its policy, swept distances, reduce, grid window,
+  // reward): it needs nothing from the humans' ORCA, so it meets the other waves only at the barrier before the commit.
+  // The humans' ORCA passes are dealt out to all waves when the robot's action is cheap, to the others when it is ORCA.
+  const int orca_waves = robot_orca && EBC_RO_WAVES > 1 ? EBC_RO_WAVES - 1 : EBC_RO_WAVES;
+
+  for (int k = 0; k < io.K; ++k) {
+    const size_t ke = (size_t)k * E + e0;  // first env of this workgroup in a [K][E] output
+    // ================================================================ P1
+    if (k > 0 && io.obs_rotated) rollout_flush_rows(rows_obs, io.obs_rotated + (ke - E) * R * T, RN * T, tid);
+    if (io.state_rotated) {  // observe_kernel: rows of the current state in the robot's frame
+      for (int q = tid; q < RN; q += EBC_RO_THREADS) {
+        const int el = q / R, r = q - el * R;
+        const int n = n_h[el], ns = n_s[el];
+        float out[EBC_RO_TMAX] = {};  // a padding row is zeros
+        if (r < n) {
+          const int h = el * N + r;
+          rotate_row<EBC_RO_TMAX>(frame_cur[el], h_px[h], h_py[h], h_vx[h], h_vy[h], h_rad[h], h_type[h], out);
+        } else if (r - n < ns) {
+          const int g = el * S + (r - n);
+          rotate_row<EBC_RO_TMAX>(frame_cur[el], st_x[g], st_y[g], 0.0, 0.0, st_r[g], EBC_ADULT_STATIC, out);
+        }
+        rollout_put_row(rows_state + (size_t)q * T, out, T);
+      }
+    }
+    if (wave == EBC_RO_WAVES - 1) {
+      if (lane < envs && io.n_rows) io.n_rows[ke + lane] = (long long)n_h[lane] + n_s[lane];
+      if (robot_orca) {
+        for (int pass = 0; pass < robot_passes; ++pass) {  // orca_robot_kernel, rows from LDS
+          using OL = OrcaLds<EBC_RO_RW>;
+          constexpr int EPW = EBC_WAVE / EBC_RO_RW;
+          float *dist_lds = reinterpret_cast<float *>(scratch);
+          float4 *lines_lds = reinterpret_cast<float4 *>(scratch + OL::DIST);
+          float4 *segs_lds = lines_lds + OL::GROUPS * OL::Sh::LINES;
+          float4 *proj_lds = segs_lds + OL::GROUPS * OL::Sh::LINES;
+          const int group = lane / EBC_RO_RW, j = lane - group * EBC_RO_RW;
+          const int el_raw = pass * EPW + group;
+          const bool e_ok = el_raw < envs;
+          const int el = e_ok ? el_raw : 0;
+          const int n = e_ok ? n_h[el] : 0, ns = e_ok ? n_s[el] : 0;
+          const double *rb = robot + el * 9;
+          const float posx = (float)rb[0], posy = (float)rb[1], velx = (float)rb[2], vely = (float)rb[3];
+          float radius = (float)(rb[4] + 0.01 + io.safety_space), maxSpeed = (float)rb[7];
+          float prefx, prefy;
+          orca_pref_velocity(rb[0], rb[1], rb[5], rb[6], prefx, prefy);
+          const bool valid = e_ok && j < n + ns;
+          float opx = 0, opy = 0, ovx = 0, ovy = 0, orad = 0;
+          if (valid && j < n) {
+            const int h = el * N + j;
+            opx = (float)h_px[h];
+            opy = (float)h_py[h];
+            ovx = (float)h_vx[h];
+            ovy = (float)h_vy[h];
+            orad = (float)(h_rad[h] + 0.01 + io.safety_space);
+          } else if (valid) {
+            const int g = el * S + (j - n);
+            opx = (float)st_x[g];
+            opy = (float)st_y[g];
+            orad = (float)(st_r[g] + 0.01 + io.safety_space);
+          }
+          if (io.sim.rows && e_ok) {
+            // every lane of the group reads the simulator's row count before lane 0 of the group replaces it (one wave)
+            const bool rebuild = sim_rows[el] != n + ns;
+            const int g = el * R + j;
+            if (rebuild) {
+              if (valid) sim_radius[g] = orad;
+              if (j == 0) {
+                sim_self[el] = make_float2(radius, maxSpeed);
+                sim_rows[el] = n + ns;
+              }
+            } else {
+              if (valid) orad = sim_radius[g];
+              const float2 me = sim_self[el];
+              radius = me.x;
+              maxSpeed = me.y;
+            }
+          }
+          float ox, oy;
+          orca_group<EBC_RO_RW>(p, j, group, valid, posx, posy, velx, vely, radius, maxSpeed, prefx, prefy, opx, opy, ovx, ovy,
+                                orad, dist_lds + group * OL::Sh::DIST, lines_lds + group * OL::Sh::LINES,
+                                segs_lds + group * OL::Sh::LINES, proj_lds + group * OL::Sh::LINES, N + S, s.range_sq,
+                                s.inv_time_horizon, s.inv_time_step, ox, oy);
+          if (e_ok && j == 0) {
+            act[2 * el] = (double)ox;  // getAgentVelocity -> Python float
+            act[2 * el + 1] = (double)oy;
+          }
+        }
+      } else if (lane < envs) {  // robot_action(): env.py:388-392
+        const double *rb = robot + lane * 9;
+        double a0, a1;
+        if (io.robot_policy == EBC_ROBOT_LINEAR) {
+          linear_policy(rb[0], rb[1], rb[5], rb[6], rb[7], a0, a1);
+        } else {
+          a0 = io.robot_action[2 * (ke + lane)];
+          a1 = io.robot_action[2 * (ke + lane) + 1];
+        }
+        act[2 * lane] = a0;
+        act[2 * lane + 1] = a1;
+      }
+      wave_sync();  // act
+      for (int q = lane; q < HN; q += EBC_WAVE) {  // collisions.py:29-57 with the humans' CURRENT velocity
+        const int el = q / N, i = q - el * N;
+        const double *rb = robot + el * 9;
+        const double a0 = act[2 * el], a1 = act[2 * el + 1];
+        double rvx, rvy;
+        if (p.robot_kinematics == EBC_HOLONOMIC) {
+          rvx = a0;
+          rvy = a1;
+        } else {
+          rvx = a0 * cos(a1 + rb[8]);
+          rvy = a0 * sin(a1 + rb[8]);
+        }
+        dist[q] = i < n_h[el] ? closest_dist(h_px[q], h_py[q], h_vx[q], h_vy[q], h_rad[q], rb[0], rb[1], rb[4], rvx, rvy, dt) : 0.0;
+      }
+      wave_sync();  // dist
+      if (lane < envs) {
+        const int el = lane;
+        double rb[9], rn[9];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) rn[c] = rb[c] = robot[el * 9 + c];
+        const double a0 = act[2 * el], a1 = act[2 * el + 1];
+        robot_advance(p, rn, a0, a1);
+        // compute_collisions (env.py:303-338): per type in index order, break at the first hit (env_lane_role's
+        // walk and ordered combination of its quarters, as one walk)
+        double fm[3] = {INFINITY, INFINITY, INFINITY};
+        int fc[3] = {0, 0, 0};
+        const int n = n_h[el];
+        for (int i = 0; i < n; ++i) {
+          const double d = dist[el * N + i];
+          const int t = h_type[el * N + i];
+#pragma unroll
+          for (int q = 0; q < 3; ++q) {
+            if (t == q && !fc[q]) {
+              if (d < 0) fc[q] = 1;
+              else if (d < fm[q]) fm[q] = d;
+            }
+          }
+        }
+        int c4[4] = {fc[0], fc[1], fc[2], 0};
+        c4[3] = grid_collision(P.grid ? P.grid + (size_t)slot[el] * s.G * 2 : nullptr, s.G, p.map_size_m, p.map_resolution,
+                               rn[0], rn[1], rb[4], nullptr);
+        const double g_now = gtime[el];
+        const RewardOut ro = reward_compute(p, rn[0], rn[1], rb[5], rb[6], rb[4], a1, g_now, fm, c4);
+        const size_t o = ke + el;
+        if (io.reward) io.reward[o] = ro.reward;
+        if (io.done) io.done[o] = (uint8_t)ro.done;
+        if (io.info) io.info[o] = (uint8_t)ro.info;
+        if (io.dmin) {
+          io.dmin[3 * o] = fm[0];
+          io.dmin[3 * o + 1] = fm[1];
+          io.dmin[3 * o + 2] = fm[2];
+        }
+        if (io.dist_to_goal) io.dist_to_goal[o] = ro.dist_to_goal;
+        if (io.robot_action_out) {
+          io.robot_action_out[2 * o] = a0;
+          io.robot_action_out[2 * o + 1] = a1;
+        }
+#pragma unroll
+        for (int c = 0; c < 9; ++c) robot_next[el * 9 + c] = rn[c];
+        if (io.obs_rotated || io.state_rotated) frame_next[el] = rot_frame(rn, p.rotate_unicycle);
+        done[el] = ro.done;
+        restore[el] = (io.auto_reset && ro.done) ? 1 : 0;
+        tnew[el] = g_now + dt;
+      }
+    }
+    for (int hp = 0; hp < human_passes; ++hp) {  // orca_tile_load + orca_wave_compute, tile and robot from LDS
+      if (hp % orca_waves != wave) continue;
+      using OL = OrcaLds<GS>;
+      constexpr int HPW = EBC_WAVE / GS;
+      float *dist_lds = reinterpret_cast<float *>(scratch);
+      float4 *lines_lds = reinterpret_cast<float4 *>(scratch + OL::DIST);
+      float4 *segs_lds = lines_lds + OL::GROUPS * OL::Sh::LINES;
+      float4 *proj_lds = segs_lds + OL::GROUPS * OL::Sh::LINES;
+      const int group = lane / GS, j = lane - group * GS;
+      const int u = hp * HPW + group;           // human of this workgroup: el * N + i
+      const bool h_ok = group < HPW && u < HN;  // lanes past HPW * GS idle
+      const int el = h_ok ? u / N : 0;
+      const int i = h_ok ? u - el * N : 0;
+      const int n = h_ok ? n_h[el] : 0;
+      const int base = el * N;
+      const int ks = base + i;
+      const int oj = j < i ? j : j + 1;  // humans before / after this one
+      const int ko = base + (oj < N ? oj : N - 1);
+      float4 ta = make_float4(0, 0, 0, 0), tb = ta, tc = ta;
+      float orad = 0;
+      if (h_ok) {
+        ta = tile[2 * ks];
+        tb = tile[2 * ks + 1];
+        tc = tile[2 * ko];
+        orad = tile[2 * ko + 1].x;
+      }
+      const bool human_ok = h_ok && i < n;
+      const float posx = ta.x, posy = ta.y, velx = ta.z, vely = ta.w;
+      const float radius = tb.x, maxSpeed = tb.y, prefx = tb.z, prefy = tb.w;
+      float opx = tc.x, opy = tc.y, ovx = tc.z, ovy = tc.w;
+      const int n_others = human_ok ? (n - 1 + (p.robot_visible ? 1 : 0)) : 0;
+      const bool valid = j < n_others;
+      if (p.robot_visible && valid && j == n - 1) {  // the robot, last in ob (env.py:401-402)
+        const double *rb = robot + el * 9;
+        opx = (float)rb[0];
+        opy = (float)rb[1];
+        ovx = (float)rb[2];
+        ovy = (float)rb[3];
+        orad = (float)(rb[4] + 0.01 + p.orca_safety_space);
+      }
+      float ox, oy;
+      orca_group<GS>(p, j, group, valid, posx, posy, velx, vely, radius, maxSpeed, prefx, prefy, opx, opy, ovx, ovy, orad,
+                     dist_lds + group * OL::Sh::DIST, lines_lds + group * OL::Sh::LINES, segs_lds + group * OL::Sh::LINES,
+                     proj_lds + group * OL::Sh::LINES, N - 1 + (p.robot_visible ? 1 : 0), s.range_sq, s.inv_time_horizon,
+                     s.inv_time_step, ox, oy);
+      if (h_ok && j == 0) vel[u] = make_float2(human_ok ? ox : 0.0f, human_ok ? oy : 0.0f);
+    }
+    __syncthreads();
+    // ================================================================ P3a
+    if (io.state_rotated) rollout_flush_rows(rows_state, io.state_rotated + ke * R * T, RN * T, tid);
+    bool any_restore = false;
+    for (int el = 0; el < envs; ++el) any_restore = any_restore || restore[el];  // the same answer in every thread
+    for (int q = tid; q < HN; q += EBC_RO_THREADS) {
+      const int el = q / N, i = q - el * N;
+      if (i >= n_h[el]) continue;
+      // Agent.step (agent.py:202-211), first arrival (env.py:365-378), the float tile record (orca.py:110-140):
+      // state_role's commit; the row is rows_role's
+      const double ax = (double)vel[q].x, ay = (double)vel[q].y;  // getAgentVelocity -> Python float
+      const double px = h_px[q] + ax * dt, py = h_py[q] + ay * dt;
+      const double rad = h_rad[q];
+      if (io.obs_rotated) {
+        float out[EBC_RO_TMAX];
+        rotate_row<EBC_RO_TMAX>(frame_next[el], px, py, ax, ay, rad, h_type[q], out);
+        rollout_put_row(rows_obs + (size_t)(el * R + i) * T, out, T);
+      }
+      if (!restore[el]) {
+        const double dx = h_gx[q] - px, dy = h_gy[q] - py;
+        const double dg = norm2(dx, dy);
+        if (h_arr[q] == 0 && dg < rad) h_arr[q] = tnew[el];
+        float prefx, prefy;
+        orca_pref_from(dx, dy, dg, prefx, prefy);
+        h_px[q] = px; h_py[q] = py; h_vx[q] = ax; h_vy[q] = ay;
+        tile[2 * q] = make_float4((float)px, (float)py, (float)ax, (float)ay);
+        tile[2 * q + 1] = make_float4((float)(rad + 0.01 + p.orca_safety_space), (float)h_vpref[q], prefx, prefy);
+      }
+    }
+    if (io.obs_rotated) {  // static obstacles as pedestrians (env.py:457-458) and the padding rows
+      for (int q = tid; q < RN; q += EBC_RO_THREADS) {
+        const int el = q / R, r = q - el * R;
+        const int n = n_h[el], ns = n_s[el];
+        if (r < n) continue;
+        float out[EBC_RO_TMAX] = {};
+        if (r - n < ns) {
+          const int g = el * S + (r - n);
+          rotate_row<EBC_RO_TMAX>(frame_next[el], st_x[g], st_y[g], 0.0, 0.0, st_r[g], EBC_ADULT_STATIC, out);
+        }
+        rollout_put_row(rows_obs + (size_t)q * T, out, T);
+      }
+    }
+    if (tid < envs) {
+      if (!restore[tid]) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) robot[tid * 9 + c] = robot_next[tid * 9 + c];
+        gtime[tid] = tnew[tid];
+        if (io.state_rotated) frame_cur[tid] = frame_next[tid];  // rot_frame of the same nine doubles
+      } else {
+        slot[tid] = cursor[tid];  // the scene the env restarts from, and its occupancy grid from now on
+      }
+    }
+    // ================================================================ P3b: restart scenes (rare)
+    // state_role's restore branch: every per-scene field from the pool slot, time 0, the cursor walks on
+    if (any_restore) {
+      __syncthreads();  // the rows above read the pre-step rows and row counts
+      for (int q = tid; q < HN; q += EBC_RO_THREADS) {
+        const int el = q / N, i = q - el * N;
+        if (!restore[el]) continue;
+        const int cur = slot[el];
+        const size_t src = (size_t)cur * N + i;
+        const bool live = i < P.n_humans[cur];
+        const double npx = live ? P.px[src] : 0.0, npy = live ? P.py[src] : 0.0;
+        const double nvx = live ? P.vx[src] : 0.0, nvy = live ? P.vy[src] : 0.0;
+        const double nrad = live ? P.radius[src] : 0.0, nvp = live ? P.v_pref[src] : 0.0;
+        h_px[q] = npx; h_py[q] = npy; h_vx[q] = nvx; h_vy[q] = nvy;
+        h_gx[q] = live ? P.gx[src] : 0.0;
+        h_gy[q] = live ? P.gy[src] : 0.0;
+        h_rad[q] = nrad; h_vpref[q] = nvp;
+        h_arr[q] = 0.0;
+        h_type[q] = live ? (int)P.type[src] : 0;
+        if (live) {
+          const float2 rp = P.pref[src];
+          tile[2 * q] = make_float4((float)npx, (float)npy, (float)nvx, (float)nvy);
+          tile[2 * q + 1] = make_float4((float)(nrad + 0.01 + p.orca_safety_space), (float)nvp, rp.x, rp.y);
+        } else {
+          tile[2 * q] = make_float4(0, 0, 0, 0);
+          tile[2 * q + 1] = make_float4(0, 0, 0, 0);
+        }
+      }
+      for (int q = tid; q < SN; q += EBC_RO_THREADS) {
+        const int el = q / S, r = q - el * S;
+        if (!restore[el]) continue;
+        const size_t src = (size_t)slot[el] * S + r;
+        st_x[q] = P.spx[src]; st_y[q] = P.spy[src]; st_r[q] = P.sradius[src];
+      }
+      if (tid < envs && restore[tid]) {
+        const int cur = slot[tid];
+        n_h[tid] = P.n_humans[cur];
+        if (S) n_s[tid] = P.n_static[cur];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) robot[tid * 9 + c] = P.robot[(size_t)cur * 9 + c];
+        gtime[tid] = 0.0;
+        if (io.state_rotated) frame_cur[tid] = rot_frame(robot + tid * 9, p.rotate_unicycle);
+        if (P.P > 0) {  // walk the custom pool; without one the env keeps restarting from its own slot
+          const int nxt = cur - E + P.stride;
+          cursor[tid] = E + (nxt >= P.P ? nxt % P.P : nxt);
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (io.obs_rotated) rollout_flush_rows(rows_obs, io.obs_rotated + ((size_t)(io.K - 1) * E + e0) * R * T, RN * T, tid);
+
+  // ---- LDS -> global memory, once: what K per-step steps would have left
+  for (int q = tid; q < HN; q += EBC_RO_THREADS) {
+    const size_t k = (size_t)e0 * N + q;
+    s.px[k] = h_px[q]; s.py[k] = h_py[q]; s.vx[k] = h_vx[q]; s.vy[k] = h_vy[q];
+    s.gx[k] = h_gx[q]; s.gy[k] = h_gy[q]; s.radius[k] = h_rad[q]; s.v_pref[k] = h_vpref[q];
+    s.arrival[k] = h_arr[q];
+    s.type[k] = (uint8_t)h_type[q];
+    s.tile[2 * k] = tile[2 * q];
+    s.tile[2 * k + 1] = tile[2 * q + 1];
+  }
+  for (int q = tid; q < SN; q += EBC_RO_THREADS) {
+    const size_t k = (size_t)e0 * S + q;
+    s.spx[k] = st_x[q]; s.spy[k] = st_y[q]; s.sradius[k] = st_r[q];
+  }
+  for (int q = tid; q < envs * 9; q += EBC_RO_THREADS) s.robot[(size_t)e0 * 9 + q] = robot[q];
+  if (tid < envs) {
+    const size_t e = (size_t)e0 + tid;
+    s.time[e] = gtime[tid];
+    s.n_humans[e] = n_h[tid];
+    if (S) s.n_static[e] = n_s[tid];
+    s.grid_scene[e] = slot[tid];
+    if (P.P > 0) P.cursor[e] = cursor[tid];
+    s.done[e] = (uint8_t)done[tid];
+    if (io.sim.rows) {
+      io.sim.rows[e] = sim_rows[tid];
+      io.sim.self[e] = sim_self[tid];
+    }
+  }
+  if (io.sim.rows)
+    for (int q = tid; q < RN; q += EBC_RO_THREADS) io.sim.radius[(size_t)e0 * R + q] = sim_radius[q];
+}
+
+}  // namespace ebc

@@ -14,6 +14,7 @@
 #include "ebc_host.h"
 #include "ebc_kernels.h"
 #include "ebc_local_map_kernel.h"
+#include "ebc_rollout.h"
 
 namespace {
 
@@ -34,6 +35,7 @@ struct Handle {
   hipStream_t stream = nullptr;
   bool has_reset = false;
   double *act_scratch = nullptr;  // ebc_step_k: the ORCA robot's action when the caller keeps none
+  int cus = 0;  // compute units of the device (EBC_FLAG_ONE_LAUNCH sizes its workgroups by them), read on first use
   int *robot_sim_rows = nullptr;
   ebc::RobotSim robot_sim = {nullptr, nullptr, nullptr};  // ebc_robot_orca_sim: the demonstrator's persistent rvo2 simulators
   bool faulted = false;  // a mailbox wait timed out and was reported: only ebc_reset re-arms the handle
@@ -1019,6 +1021,63 @@ int launch_observe(Handle *h, double *d_ob, float *d_obs) {
   return EBC_OK;
 }
 
+// EBC_FLAG_ONE_LAUNCH: rollout_kernel (ebc_rollout.h), a workgroup per group of envs for all K steps.
+template <int GS>
+int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
+  const int N = h->s.N, S = h->s.S, E = h->s.E;
+  constexpr unsigned scratch = ebc::RolloutScratch<GS>::BYTES;
+  // envs per workgroup.  Two lower bounds, the larger decides: (1) what gives every wave one pass of ORCA groups per
+  // step (the robot's groups take a wave of their own): 2 at 10 humans in 9-lane groups; (2) enough that all workgroups
+  // of the launch are resident at once, EBC_RO_OCC per CU — a workgroup stays for K steps, so a second round of
+  // workgroups doubles the call: 4 at 4096 envs on 256 CUs, and this is the bound that decides from 2049 envs on.
+  // Then the upper bounds: EBC_RO_MAX_EPG, E, and 48 KB of LDS per workgroup.
+  int epg = ((robot_orca ? EBC_RO_WAVES - 1 : EBC_RO_WAVES) * (EBC_WAVE / GS)) / N;
+  if (!h->cus) {
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device));
+    h->cus = cus > 0 ? cus : 1;
+  }
+  const int resident = h->cus * EBC_RO_OCC;
+  if (epg < (E + resident - 1) / resident) epg = (E + resident - 1) / resident;
+  const char *force = getenv("EBCSIM_ONE_LAUNCH_EPG");  // measurements only (environment switches)
+  if (force && atoi(force) > 0) epg = atoi(force);
+  epg = epg < 1 ? 1 : (epg > EBC_RO_MAX_EPG ? EBC_RO_MAX_EPG : epg);
+  epg = epg > E ? E : epg;
+  while (epg > 1 && ebc::rollout_lds(epg, N, S, h->T, scratch).bytes > 48u * 1024u) --epg;
+  const unsigned lds = ebc::rollout_lds(epg, N, S, h->T, scratch).bytes;
+  // one env always fits: ebc_create takes at most 33 humans and 128 rows, which is under 30 KB here (the two row
+  // buffers are 17 KB of it); the check guards the launch against a later change of those limits
+  if (lds > 48u * 1024u) return fail(EBC_ERR_UNSUPPORTED, "EBC_FLAG_ONE_LAUNCH: one env needs more than 48 KB of LDS");
+  io.epg = epg;
+  const unsigned blocks = (unsigned)((E + epg - 1) / epg);
+  hipLaunchKernelGGL((ebc::rollout_kernel<GS>), dim3(blocks), dim3(EBC_RO_THREADS), lds, h->stream, h->p, h->s, io);
+  HIP_TRY(hipGetLastError());
+  return EBC_OK;
+}
+
+int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca) {
+#ifdef EBC_DEV_GS
+  if (h->orca_gs != EBC_DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: one ORCA group size only");
+  return launch_rollout_gs<EBC_DEV_GS>(h, io, robot_orca);
+#else
+  switch (h->orca_gs) {
+    case 2: return launch_rollout_gs<2>(h, io, robot_orca);
+    case 3: return launch_rollout_gs<3>(h, io, robot_orca);
+    case 4: return launch_rollout_gs<4>(h, io, robot_orca);
+    case 5: return launch_rollout_gs<5>(h, io, robot_orca);
+    case 6: return launch_rollout_gs<6>(h, io, robot_orca);
+    case 7: return launch_rollout_gs<7>(h, io, robot_orca);
+    case 8: return launch_rollout_gs<8>(h, io, robot_orca);
+    case 9: return launch_rollout_gs<9>(h, io, robot_orca);
+    case 10: return launch_rollout_gs<10>(h, io, robot_orca);
+    case 12: return launch_rollout_gs<12>(h, io, robot_orca);
+    case 16: return launch_rollout_gs<16>(h, io, robot_orca);
+    case 21: return launch_rollout_gs<21>(h, io, robot_orca);
+    default: return launch_rollout_gs<32>(h, io, robot_orca);
+  }
+#endif
+}
+
 }  // namespace
 
 extern "C" {
@@ -1112,6 +1171,12 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     return fail(EBC_ERR_UNSUPPORTED, "the linear robot policy is holonomic (simulator/policy/linear.py:11)");
   if (a->robot_policy == EBC_ROBOT_ORCA && (rc = check_robot_orca(h, a->robot_safety_space)) != EBC_OK) return rc;
   if (a->flags & EBC_FLAG_BORDER) return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: no border");
+  const bool one_launch = (a->flags & EBC_FLAG_ONE_LAUNCH) != 0;
+  // strict: a caller who sets the flag knows which form ran
+  if (one_launch && a->human_policy == EBC_HUMAN_LINEAR)
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_LINEAR (the one-launch form moves ORCA humans only)");
+  if (one_launch && a->human_policy == EBC_HUMAN_EXTERNAL)
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_EXTERNAL (the one-launch form moves ORCA humans only)");
   const DevState &s = h->s;
   const size_t E = s.E, R = s.N + s.S, T = h->T, K = (size_t)a->K;
   const double *d_act_in = a->robot_action;
@@ -1129,6 +1194,22 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     d_act_out = st.out(a->robot_action_out, K * E * 2); d_reward = st.out(a->reward, K * E);
     d_done = st.out(a->done, K * E); d_info = st.out(a->info, K * E); d_dmin = st.out(a->dmin, K * E * 3);
     d_goal = st.out(a->dist_to_goal, K * E); d_obs = st.out(a->obs_rotated, K * E * R * T);
+  }
+  if (one_launch) {
+    ebc::RolloutIO io;
+    memset(&io, 0, sizeof(io));
+    io.K = a->K;
+    io.robot_policy = a->robot_policy;
+    io.auto_reset = (a->flags & EBC_FLAG_AUTO_RESET) ? 1 : 0;
+    io.T = h->T;
+    io.safety_space = a->robot_safety_space;
+    if (a->robot_policy == EBC_ROBOT_ORCA) io.sim = h->robot_sim;
+    io.robot_action = a->robot_policy == EBC_ROBOT_EXTERNAL ? d_act_in : nullptr;
+    io.state_rotated = d_state; io.n_rows = d_rows; io.robot_action_out = d_act_out; io.reward = d_reward;
+    io.done = d_done; io.info = d_info; io.dmin = d_dmin; io.dist_to_goal = d_goal; io.obs_rotated = d_obs;
+    if ((rc = launch_rollout(h, io, a->robot_policy == EBC_ROBOT_ORCA)) != EBC_OK) return rc;
+    if (a->location != EBC_DEVICE) return st.finish();
+    return EBC_OK;
   }
   // the ORCA robot's action of step k needs a home when the caller does not ask for the actions
   double *orca_act = nullptr;

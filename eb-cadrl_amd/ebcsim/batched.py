@@ -414,7 +414,8 @@ class BatchedEnv:
 
     def step_k(self, K, keys=("reward", "done", "info", "state_rotated"), robot_action=None,
                human_policy=_abi.HUMAN_ORCA, robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0):
-        """K steps in one call (ebc_step_k), host buffers: returns {key: array [K, ...]}."""
+        """K steps in one call (ebc_step_k), host buffers: returns {key: array [K, ...]}.  flags may carry
+        _abi.FLAG_ONE_LAUNCH: the K steps as one kernel launch, same results bit for bit (ORCA humans only)."""
         shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
         out = {k: np.zeros((K,) + shapes[k][0], dtype=shapes[k][1]) for k in keys}
         ra = None
@@ -434,7 +435,7 @@ class BatchedEnv:
 
     def step_k_device(self, outputs, K, robot_action=None, human_policy=_abi.HUMAN_ORCA,
                       robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0):
-        """Enqueue K steps (ebc_step_k) writing into torch CUDA tensors [K, ...] (not copied)."""
+        """Enqueue K steps (ebc_step_k) writing into torch CUDA tensors [K, ...] (not copied); flags as step_k."""
         for k, t in outputs.items():
             if t.shape[0] != K or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous [K, ...] tensor" % k)

@@ -376,7 +376,8 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
     return total / steps
 
 
-def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HUMAN_ORCA, persistent_sim=True):
+def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HUMAN_ORCA, persistent_sim=True,
+               one_launch=False):
     """The imitation-learning stage's rollouts (rl/train.py:124-133, explorer.py:33-92 with
     imitation_learning=True): the robot of every env of the rank's slice on ORCA (ebc_robot_orca ->
     ebc_step, auto-reset) for `steps` steps; the states of every episode that ended inside the window in
@@ -387,7 +388,9 @@ def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HU
     built at the env's first step of this call and again whenever the row count of its scene changes, and in between
     keeps the radii / maxSpeed it was built with (simulator/policy/orca.py:96-133), across restarts too: an env's
     episode sequence equals the reference's serial sequence on the same scenes (tests: il_persistent_* goldens).
-    persistent_sim=False: the demonstrator sees every state's own radii (a fresh policy object per step)."""
+    persistent_sim=False: the demonstrator sees every state's own radii (a fresh policy object per step).
+    one_launch=True: the window runs as ONE kernel launch (EBC_FLAG_ONE_LAUNCH, ORCA humans only): the same memory,
+    bit for bit."""
     E, R, T = env.E, env.R, env.T
     env.robot_orca_sim(bool(persistent_sim))
     v_pref = uniform_v_pref(env)
@@ -399,7 +402,8 @@ def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HU
     keys = ("state_rotated", "reward", "done", "info") + (("n_rows",) if ragged else ())
     outs = env.alloc_step_k_outputs(steps, keys)
     env.step_k_device(outs, steps, human_policy=human_policy, robot_policy=_abi.ROBOT_ORCA,
-                      flags=_abi.FLAG_AUTO_RESET, robot_safety_space=safety_space)
+                      flags=_abi.FLAG_AUTO_RESET | (_abi.FLAG_ONE_LAUNCH if one_launch else 0),
+                      robot_safety_space=safety_space)
     states, rewards, dones, infos = outs["state_rotated"], outs["reward"], outs["done"], outs["info"]
     rows = outs["n_rows"] if ragged else None
     values, keep = il_value_targets(rewards, dones, gamma_bar, infos)

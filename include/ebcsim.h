@@ -89,7 +89,8 @@ enum {
 enum {
   EBC_FLAG_AUTO_RESET = 1, /* a terminal step's outputs describe the terminal transition; the env's
                               state is then put back to its reset() scene (time 0) for the next step */
-  EBC_FLAG_BORDER = 2      /* border[4] valid: simulator/env.py:264-271 */
+  EBC_FLAG_BORDER = 2,     /* border[4] valid: simulator/env.py:264-271 */
+  EBC_FLAG_ONE_LAUNCH = 4  /* ebc_step_k: all K steps in ONE kernel launch, state kept on chip between steps */
 };
 
 /* Everything env.configure() / Reward.__init__ / ORCA.__init__ read from the INI
@@ -334,7 +335,24 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *args);
  * (EBC_ROBOT_ORCA: ebc_robot_orca with robot_safety_space; EBC_ROBOT_LINEAR; EBC_ROBOT_EXTERNAL:
  * robot_action[k]), and ebc_step with every output written at index k.  Same arithmetic, launch for launch,
  * as K calls of ebc_observe / ebc_robot_orca / ebc_step (tests hold it equal to K oracle steps); what it
- * removes is the per-step host work.  EBC_FLAG_AUTO_RESET keeps every env in an episode. */
+ * removes is the per-step host work.  EBC_FLAG_AUTO_RESET keeps every env in an episode.
+ *
+ * EBC_FLAG_ONE_LAUNCH: the same K steps as ONE kernel launch.  A workgroup owns a few envs for the whole call, keeps
+ * their state in LDS between steps and separates the phases of a step with workgroup barriers; state is read once
+ * and written once, and per step only the requested outputs, robot_action[k], the grid window and an ending env's
+ * restart scene touch memory.
+ *   - Same arguments, the same outputs at the same [k] indices, the same state left behind, BIT FOR BIT, as the
+ *     per-step form: humans, robot, time, arrival, done, float tile, grid slot, pool cursor and the persistent
+ *     simulators of ebc_robot_orca_sim hold what K per-step steps would have left, so ebc_step, ebc_lookahead,
+ *     ebc_observe, ebc_get_state, ebc_local_map and a further ebc_step_k of either form continue from it.
+ *   - Covers EBC_HUMAN_ORCA with each robot policy (EBC_ROBOT_EXTERNAL reading robot_action[k], EBC_ROBOT_LINEAR,
+ *     EBC_ROBOT_ORCA with or without the persistent simulator), with and without EBC_FLAG_AUTO_RESET, own-scene
+ *     and installed pools, both row widths, holonomic and unicycle robots where the per-step form takes them,
+ *     every output optional, host and device location.
+ *   - Strict: EBC_HUMAN_LINEAR and EBC_HUMAN_EXTERNAL return EBC_ERR_UNSUPPORTED; nothing else is left out (every
+ *     handle ebc_create accepts fits).  The call never falls back to the per-step form.  Every refusal of ebc_step_k (capturing
+ *     stream, EBC_FLAG_BORDER, K < 1, before reset, faulted handle) holds for it too.
+ *   - No mailboxes, no polling, no give-up path: this launch cannot raise the handle's fault word. */
 typedef struct EbcStepKArgs {
   uint32_t struct_size;
   int32_t location;      /* of every pointer below */

@@ -29,6 +29,8 @@ def main():
     ap.add_argument("--batch-size", type=int, default=100)
     ap.add_argument("--device-scenes", action="store_true",
                     help="every episode on a scene generated on the device from the train seeds (run_training scene_gen)")
+    ap.add_argument("--one-launch", action="store_true",
+                    help="the timed imitation-learning rollout as one kernel launch (EBC_FLAG_ONE_LAUNCH)")
     args = ap.parse_args()
     import torch
     import torch.distributed as dist
@@ -63,15 +65,16 @@ def main():
     # always on the HOST-generated batch, whatever --device-scenes says: the il_* fields are labelled so), then
     # the whole schedule
     mem = DeviceReplay(args.il_steps * args.envs, env.R, env.T, dev)
-    collect_il(env, mem, min(args.il_steps, 20), 0.9, 0.15)
+    collect_il(env, mem, min(args.il_steps, 20), 0.9, 0.15, one_launch=args.one_launch)
     del mem
     env.reset(batch)
     t0 = sync()
     mem = DeviceReplay(args.il_steps * args.envs, env.R, env.T, dev)
-    stored, episodes = collect_il(env, mem, args.il_steps, 0.9, 0.15)
+    stored, episodes = collect_il(env, mem, args.il_steps, 0.9, 0.15, one_launch=args.one_launch)
     t1 = sync()
     times["il_rollout_s"] = t1 - t0
     times["il_env_steps_per_s"] = args.il_steps * args.envs * world / (t1 - t0)
+    times["il_one_launch"] = bool(args.one_launch)
     times["il_fields"] = "il_* measured on the host-generated batch after a 20-step warm-up call (not on device-generated scenes)"
     del mem
     env.reset(batch)
