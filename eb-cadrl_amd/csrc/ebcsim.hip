@@ -40,7 +40,6 @@ struct Handle {
   ebc::RobotSim robot_sim = {nullptr, nullptr, nullptr};  // ebc_robot_orca_sim: the demonstrator's persistent rvo2 simulators
   bool faulted = false;  // a mailbox wait timed out and was reported: only ebc_reset re-arms the handle
   int orca_gs = 16;  // lanes per human of the ORCA waves
-  int step_form = 3;  // the fused ORCA step: 3 = four roles, ENV with four lanes per env (default); 1 = ENV with a lane per human slot (rounds 1-2); 2 = orca_step2_kernel (experiment: ORCA groups commit their own human)
   unsigned epoch = 0;  // fused ORCA steps launched so far (StepGrid::epoch)
   std::vector<void *> pool_allocs;   // pool arrays (re-allocated by ebc_set_scene_pool)
   uint64_t *pool_grid_alloc = nullptr;
@@ -94,9 +93,6 @@ int arm_mailboxes(Handle *h) {
   HIP_TRY(hipMemsetAsync(h->s.rows_loaded, 0, E * 4, h->stream));
   HIP_TRY(hipMemsetAsync(h->s.robot_ready, 0, E * 4, h->stream));
   HIP_TRY(hipMemsetAsync(h->s.fault, 0, 4, h->stream));
-  HIP_TRY(hipMemsetAsync(h->s.frame, 0, E * 64, h->stream));
-  HIP_TRY(hipMemsetAsync(h->s.ract, 0, E * 64, h->stream));
-  HIP_TRY(hipMemsetAsync(h->s.committed, 0, EN * 4, h->stream));
   return EBC_OK;
 }
 
@@ -159,32 +155,48 @@ int orca_blocks(const Handle *h) {
   return (int)((humans + hpw - 1) / hpw);
 }
 
+// The ORCA group sizes (lanes per human, or per robot) the kernels are instantiated for.
+const int kGroupSizes[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32};
+
+// the smallest instantiated group size with at least n lanes (n <= 32)
+int group_size_for(int n) {
+  for (int g : kGroupSizes)
+    if (g >= n) return g;
+  return 32;
+}
+
+// Development builds (make dev) instantiate ONE group size per kind of kernel: EBC_DEV_GS for the kernels
+// of the humans' ORCA, 21 for the robot's.  0 = every size of kGroupSizes.
+#ifdef EBC_DEV_GS
+constexpr int kDevHumanGs = EBC_DEV_GS, kDevRobotGs = 21;
+#else
+constexpr int kDevHumanGs = 0, kDevRobotGs = 0;
+#endif
+
+// Run-time group size -> compile-time one: calls f(std::integral_constant<int, GS>()) for GS == gs, a member of
+// kGroupSizes.  The only place that lists the instantiated sizes besides the table.
+template <int DEV_GS, typename F>
+int with_group_size(int gs, F f) {
+  if constexpr (DEV_GS != 0) {
+    if (gs != DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: " + std::to_string(DEV_GS) + "-lane ORCA groups only");
+    return f(std::integral_constant<int, DEV_GS>());
+  } else {
+    switch (gs) {
+#define GS_(N) case N: return f(std::integral_constant<int, N>())
+      GS_(2); GS_(3); GS_(4); GS_(5); GS_(6); GS_(7); GS_(8); GS_(9); GS_(10); GS_(12); GS_(16); GS_(21);
+#undef GS_
+      default: return f(std::integral_constant<int, 32>());
+    }
+  }
+}
+
 int launch_orca(Handle *h) {
   const int blocks = orca_blocks(h);
-#define OK_(GS) hipLaunchKernelGGL((ebc::orca_kernel<GS>), dim3(blocks), dim3(EBC_WAVE), 0, h->stream, h->p, h->s)
-#ifdef EBC_DEV_GS  // quick development builds: one group size, one row width (make dev)
-  if (h->orca_gs != EBC_DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: one ORCA group size only");
-  OK_(EBC_DEV_GS);
-#else
-  switch (h->orca_gs) {
-    case 2: OK_(2); break;
-    case 3: OK_(3); break;
-    case 4: OK_(4); break;
-    case 5: OK_(5); break;
-    case 6: OK_(6); break;
-    case 7: OK_(7); break;
-    case 8: OK_(8); break;
-    case 9: OK_(9); break;
-    case 10: OK_(10); break;
-    case 12: OK_(12); break;
-    case 16: OK_(16); break;
-    case 21: OK_(21); break;
-    default: OK_(32); break;
-  }
-#endif
-#undef OK_
-  HIP_TRY(hipGetLastError());
-  return EBC_OK;
+  return with_group_size<kDevHumanGs>(h->orca_gs, [&](auto gs) -> int {
+    hipLaunchKernelGGL((ebc::orca_kernel<decltype(gs)::value>), dim3(blocks), dim3(EBC_WAVE), 0, h->stream, h->p, h->s);
+    HIP_TRY(hipGetLastError());
+    return EBC_OK;
+  });
 }
 
 template <int POLICY>
@@ -204,86 +216,22 @@ int launch_orca_step_gs(Handle *h, const StepIO &io, unsigned blocks, const ebc:
   if (h->T == 17)
     hipLaunchKernelGGL((ebc::orca_step_kernel<GS, 17>), dim3((blocks + EBC_STEP_WPB - 1) / EBC_STEP_WPB), dim3(EBC_WAVE * EBC_STEP_WPB), 0, h->stream,
                        g.env_blocks, g.orca_blocks, h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile,
-                       (const int *)h->s.n_humans, h->s.vel, g.epoch, h->step_form == 3 ? 1u : 0u, h->p, h->s, io, g);
+                       (const int *)h->s.n_humans, h->s.vel, g.epoch, 0u, h->p, h->s, io, g);
   else
     hipLaunchKernelGGL((ebc::orca_step_kernel<GS, 13>), dim3((blocks + EBC_STEP_WPB - 1) / EBC_STEP_WPB), dim3(EBC_WAVE * EBC_STEP_WPB), 0, h->stream,
                        g.env_blocks, g.orca_blocks, h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile,
-                       (const int *)h->s.n_humans, h->s.vel, g.epoch, h->step_form == 3 ? 1u : 0u, h->p, h->s, io, g);
+                       (const int *)h->s.n_humans, h->s.vel, g.epoch, 0u, h->p, h->s, io, g);
   HIP_TRY(hipGetLastError());
   return EBC_OK;
-}
-
-int launch_orca_step_sized(Handle *h, const StepIO &io, unsigned blocks, const ebc::StepGrid &g);
-
-template <int GS>
-int launch_orca_step2_gs(Handle *h, const StepIO &io, const ebc::Step2Grid &g) {
-  if (h->T == 17)
-    hipLaunchKernelGGL((ebc::orca_step2_kernel<GS, 17>), dim3(g.total), dim3(EBC_WAVE), 0, h->stream, g.env1_blocks, g.orca_blocks,
-                       h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile, (const int *)h->s.n_humans, g.epoch,
-                       0u, 0u, 0u, h->p, h->s, io, g);
-  else
-    hipLaunchKernelGGL((ebc::orca_step2_kernel<GS, 13>), dim3(g.total), dim3(EBC_WAVE), 0, h->stream, g.env1_blocks, g.orca_blocks,
-                       h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile, (const int *)h->s.n_humans, g.epoch,
-                       0u, 0u, 0u, h->p, h->s, io, g);
-  HIP_TRY(hipGetLastError());
-  return EBC_OK;
-}
-
-// The second form of the fused step (ebc_kernels.h: orca_step2_kernel): ENV1 (lane = env), ORCA (commits its human),
-// ENV2 (lane = human slot).  The launch leaves the humans' next positions / velocities / float tile and the robots'
-// next state in the second buffers: they are the current ones from here on.
-int launch_orca_step2(Handle *h, const StepIO &io) {
-  const int epb = EBC_WAVE / h->s.N;
-  ebc::Step2Grid g;
-  g.env1_blocks = (unsigned)((h->s.E + EBC_WAVE - 1) / EBC_WAVE);
-  g.orca_blocks = (unsigned)orca_blocks(h);
-  g.env2_blocks = (unsigned)((h->s.E + epb - 1) / epb);
-  const unsigned long long blocks = (unsigned long long)g.env1_blocks + g.orca_blocks + g.env2_blocks;
-  if (blocks >= 2147483648ull) return fail(EBC_ERR_UNSUPPORTED, "ORCA step grid >= 2^31 workgroups");
-  if (++h->epoch == 0) h->epoch = 1;
-  g.epoch = h->epoch;
-  g.total = (unsigned)blocks;
-  int rc;
-#ifdef EBC_DEV_GS
-  if (h->orca_gs != EBC_DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: one ORCA group size only");
-  rc = launch_orca_step2_gs<EBC_DEV_GS>(h, io, g);
-#else
-  switch (h->orca_gs) {
-    case 2: rc = launch_orca_step2_gs<2>(h, io, g); break;
-    case 3: rc = launch_orca_step2_gs<3>(h, io, g); break;
-    case 4: rc = launch_orca_step2_gs<4>(h, io, g); break;
-    case 5: rc = launch_orca_step2_gs<5>(h, io, g); break;
-    case 6: rc = launch_orca_step2_gs<6>(h, io, g); break;
-    case 7: rc = launch_orca_step2_gs<7>(h, io, g); break;
-    case 8: rc = launch_orca_step2_gs<8>(h, io, g); break;
-    case 9: rc = launch_orca_step2_gs<9>(h, io, g); break;
-    case 10: rc = launch_orca_step2_gs<10>(h, io, g); break;
-    case 12: rc = launch_orca_step2_gs<12>(h, io, g); break;
-    case 16: rc = launch_orca_step2_gs<16>(h, io, g); break;
-    case 21: rc = launch_orca_step2_gs<21>(h, io, g); break;
-    default: rc = launch_orca_step2_gs<32>(h, io, g); break;
-  }
-#endif
-  if (rc == EBC_OK) {
-    std::swap(h->s.robot, h->s.robot_n);
-    std::swap(h->s.px, h->s.px_n);
-    std::swap(h->s.py, h->s.py_n);
-    std::swap(h->s.vx, h->s.vx_n);
-    std::swap(h->s.vy, h->s.vy_n);
-    std::swap(h->s.tile, h->s.tile_n);
-  }
-  return rc;
 }
 
 int launch_orca_step(Handle *h, const StepIO &io) {
-  if (h->step_form == 2) return launch_orca_step2(h, io);
   const int epb = EBC_WAVE / h->s.N;
   const int R = h->s.N + h->s.S;
   ebc::StepGrid g;
   const unsigned state_blocks = (unsigned)((h->s.E + epb - 1) / epb);
-  // form 3: the ENV role with four lanes per ENV (16 envs per wave) instead of a lane per human slot
-  constexpr int envs_per_wave3 = EBC_WAVE / EBC_ENV_LANES;
-  g.env_blocks = h->step_form == 3 ? (unsigned)((h->s.E + envs_per_wave3 - 1) / envs_per_wave3) : state_blocks;
+  constexpr int envs_per_env_wave = EBC_WAVE / EBC_ENV_LANES;
+  g.env_blocks = (unsigned)((h->s.E + envs_per_env_wave - 1) / envs_per_env_wave);
   g.orca_blocks = (unsigned)orca_blocks(h);
   g.rows_epw = R <= EBC_WAVE ? (unsigned)(EBC_WAVE / R) : 1u;
   g.rows_blocks = (io.ob || io.obs_rotated) ? (unsigned)((h->s.E + g.rows_epw - 1) / g.rows_epw) : 0u;
@@ -292,33 +240,11 @@ int launch_orca_step(Handle *h, const StepIO &io) {
   if (++h->epoch == 0) h->epoch = 1;  // every mailbox word is tagged with the epoch of the launch that wrote it; 0 = never
   g.epoch = h->epoch;
   g.total = (unsigned)blocks;
-  const int rc = launch_orca_step_sized(h, io, blocks, g);
+  const int rc = with_group_size<kDevHumanGs>(
+      h->orca_gs, [&](auto gs) { return launch_orca_step_gs<decltype(gs)::value>(h, io, (unsigned)blocks, g); });
   // the launch leaves the robots' next state in robot_n: that is the current state from here on
   if (rc == EBC_OK) std::swap(h->s.robot, h->s.robot_n);
   return rc;
-}
-
-int launch_orca_step_sized(Handle *h, const StepIO &io, unsigned blocks, const ebc::StepGrid &g) {
-#ifdef EBC_DEV_GS
-  if (h->orca_gs != EBC_DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: one ORCA group size only");
-  return launch_orca_step_gs<EBC_DEV_GS>(h, io, blocks, g);
-#else
-  switch (h->orca_gs) {
-    case 2: return launch_orca_step_gs<2>(h, io, blocks, g);
-    case 3: return launch_orca_step_gs<3>(h, io, blocks, g);
-    case 4: return launch_orca_step_gs<4>(h, io, blocks, g);
-    case 5: return launch_orca_step_gs<5>(h, io, blocks, g);
-    case 6: return launch_orca_step_gs<6>(h, io, blocks, g);
-    case 7: return launch_orca_step_gs<7>(h, io, blocks, g);
-    case 8: return launch_orca_step_gs<8>(h, io, blocks, g);
-    case 9: return launch_orca_step_gs<9>(h, io, blocks, g);
-    case 10: return launch_orca_step_gs<10>(h, io, blocks, g);
-    case 12: return launch_orca_step_gs<12>(h, io, blocks, g);
-    case 16: return launch_orca_step_gs<16>(h, io, blocks, g);
-    case 21: return launch_orca_step_gs<21>(h, io, blocks, g);
-    default: return launch_orca_step_gs<32>(h, io, blocks, g);
-  }
-#endif
 }
 
 int launch_step(Handle *h, const StepIO &io, int policy) {
@@ -610,8 +536,6 @@ int ebc_create(int device_id, int n_envs, int max_humans, int max_static, const 
   A_(tile, EN * 2);
   A_(done, n_envs); A_(hact, EN * 2);
   A_(vel, EN); A_(env_done, n_envs); A_(rows_loaded, n_envs); A_(robot_ready, n_envs); A_(fault, 1);  // zeroed: tag 0 = no launch
-  A_(px_n, EN); A_(py_n, EN); A_(vx_n, EN); A_(vy_n, EN); A_(tile_n, EN * 2);
-  A_(frame, (size_t)n_envs * 4); A_(ract, (size_t)n_envs * 4); A_(committed, EN);
 #undef A_
   if (rc == EBC_OK) rc = dev_alloc(h, &s.pool.cursor, n_envs);
   if (rc == EBC_OK) rc = dev_alloc(h, &s.grid_scene, n_envs);
@@ -631,15 +555,9 @@ int ebc_create(int device_id, int n_envs, int max_humans, int max_static, const 
     const int others = max_humans - 1 + (params->robot_visible ? 1 : 0);
     // lanes per human = its number of others, rounded up to a size that is instantiated and never
     // to one that fits fewer humans in a wave (64 / GS): 9 others -> 9 lanes, 7 humans per wave
-    static const int sizes[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32};
-    for (int g : sizes)
-      if (g >= others) { h->orca_gs = g; break; }
-    const char *form = getenv("EBCSIM_STEP_FORM");  // measurements only: 1 = the four-role launch of rounds 1-2
-    if (form && atoi(form) >= 1 && atoi(form) <= 3) h->step_form = atoi(form);
+    h->orca_gs = group_size_for(others);
     const char *force = getenv("EBCSIM_ORCA_GROUP");  // measurements only: a larger group size
-    if (force && atoi(force) >= h->orca_gs)
-      for (int g : sizes)
-        if (g >= atoi(force)) { h->orca_gs = g; break; }
+    if (force && atoi(force) >= h->orca_gs && atoi(force) <= 32) h->orca_gs = group_size_for(atoi(force));
   }
   *handle_out = h;
   return EBC_OK;
@@ -971,36 +889,15 @@ namespace {
 // orca_robot_kernel for every env -> d_act [E][2] (device pointer), on the handle's stream
 int launch_robot_orca(Handle *h, double safety_space, double *d_act) {
   const int others = h->s.N + h->s.S;  // rows of the observation
-  static const int sizes[] = {2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32};
-  int gs = 32;
-  for (int g : sizes)
-    if (g >= others) { gs = g; break; }
+  const int gs = group_size_for(others);
   const int epw = EBC_WAVE / gs;
   const unsigned blocks = (unsigned)((h->s.E + epw - 1) / epw);
-#define RK_(GS) hipLaunchKernelGGL((ebc::orca_robot_kernel<GS>), dim3(blocks), dim3(EBC_WAVE), 0, h->stream, h->p, h->s, safety_space, d_act, h->robot_sim)
-#ifdef EBC_DEV_GS
-  if (gs != 21) return fail(EBC_ERR_UNSUPPORTED, "development build: robot ORCA for 21-lane groups only");
-  RK_(21);
-#else
-  switch (gs) {
-    case 2: RK_(2); break;
-    case 3: RK_(3); break;
-    case 4: RK_(4); break;
-    case 5: RK_(5); break;
-    case 6: RK_(6); break;
-    case 7: RK_(7); break;
-    case 8: RK_(8); break;
-    case 9: RK_(9); break;
-    case 10: RK_(10); break;
-    case 12: RK_(12); break;
-    case 16: RK_(16); break;
-    case 21: RK_(21); break;
-    default: RK_(32); break;
-  }
-#endif
-#undef RK_
-  HIP_TRY(hipGetLastError());
-  return EBC_OK;
+  return with_group_size<kDevRobotGs>(gs, [&](auto g) -> int {
+    hipLaunchKernelGGL((ebc::orca_robot_kernel<decltype(g)::value>), dim3(blocks), dim3(EBC_WAVE), 0, h->stream, h->p, h->s, safety_space,
+                       d_act, h->robot_sim);
+    HIP_TRY(hipGetLastError());
+    return EBC_OK;
+  });
 }
 
 int check_robot_orca(const Handle *h, double safety_space) {
@@ -1056,26 +953,8 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
 }
 
 int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca) {
-#ifdef EBC_DEV_GS
-  if (h->orca_gs != EBC_DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: one ORCA group size only");
-  return launch_rollout_gs<EBC_DEV_GS>(h, io, robot_orca);
-#else
-  switch (h->orca_gs) {
-    case 2: return launch_rollout_gs<2>(h, io, robot_orca);
-    case 3: return launch_rollout_gs<3>(h, io, robot_orca);
-    case 4: return launch_rollout_gs<4>(h, io, robot_orca);
-    case 5: return launch_rollout_gs<5>(h, io, robot_orca);
-    case 6: return launch_rollout_gs<6>(h, io, robot_orca);
-    case 7: return launch_rollout_gs<7>(h, io, robot_orca);
-    case 8: return launch_rollout_gs<8>(h, io, robot_orca);
-    case 9: return launch_rollout_gs<9>(h, io, robot_orca);
-    case 10: return launch_rollout_gs<10>(h, io, robot_orca);
-    case 12: return launch_rollout_gs<12>(h, io, robot_orca);
-    case 16: return launch_rollout_gs<16>(h, io, robot_orca);
-    case 21: return launch_rollout_gs<21>(h, io, robot_orca);
-    default: return launch_rollout_gs<32>(h, io, robot_orca);
-  }
-#endif
+  return with_group_size<kDevHumanGs>(h->orca_gs,
+                                      [&](auto gs) { return launch_rollout_gs<decltype(gs)::value>(h, io, robot_orca); });
 }
 
 }  // namespace
@@ -1586,13 +1465,6 @@ extern "C" int ebc_debug_wave_trace(void *device_buffer, unsigned blocks) {
 }
 // tests only: from the next fused ORCA step on, the ORCA group of flat human index `human` (e * N + i) does
 // not publish its velocity, so its consumers run into EBC_SPIN_LIMIT (lowered in this build); -1 = off
-// tests / debugging only: the hand-off records of the second step form, copied to the host
-extern "C" int ebc_debug_read(void *handle, int which, void *dst, size_t bytes) {
-  Handle *h = (Handle *)handle;
-  const void *src = which == 0 ? (const void *)h->s.frame : which == 1 ? (const void *)h->s.ract : (const void *)h->s.committed;
-  (void)hipDeviceSynchronize();
-  return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? EBC_OK : EBC_ERR_DEVICE;
-}
 extern "C" int ebc_debug_withhold(int human) {
   if (hipMemcpyToSymbol(HIP_SYMBOL(ebc::g_withhold_human), &human, sizeof(human)) != hipSuccess) return EBC_ERR_DEVICE;
   return EBC_OK;

@@ -61,10 +61,8 @@ def main():
         if not len(rows):
             continue
         if tag == 2:  # orca_step_kernel: blocks in role order ENV, ORCA, ROWS, STATE
-            env_blocks = -(-E // (64 // batch.N))
-            state_blocks = env_blocks
-            if os.environ.get("EBCSIM_STEP_FORM", "3") == "3":  # the default form: the ENV role with four lanes per env
-                env_blocks = -(-E // 16)
+            env_blocks = -(-E // 16)  # the ENV role has four lanes per env
+            state_blocks = -(-E // (64 // batch.N))
             others = batch.N - 1 + (1 if params.robot_visible else 0)
             gs = next(g for g in (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32) if g >= others)
             orca_blocks = -(-E * batch.N // (64 // gs))
@@ -82,21 +80,23 @@ def main():
         for name, sel in parts:
             if sel.any():
                 report(np, name, rows[sel], launch0 if tag == 3 and launch0 is not None else base_all)
-        if tag == 2 and len(idx) == b3 + state_blocks and state_blocks == env_blocks:
-            # what each STATE wave waited for: the ORCA waves of its envs and its ENV wave
+        if tag == 2 and len(idx) == b3 + state_blocks:
+            # what each STATE wave waited for: the ORCA waves and the ENV waves of its envs
             end = (rows[:, 1].astype(np.int64) - base_all) / 100.0
             start = (rows[:, 0].astype(np.int64) - base_all) / 100.0
             hpw, epb = 64 // gs, 64 // batch.N
             lag, info = [], []
-            for sb in range(env_blocks):
-                h0, h1 = sb * epb * batch.N, min((sb + 1) * epb, E) * batch.N - 1
+            for sb in range(state_blocks):
+                e0, e1 = sb * epb, min((sb + 1) * epb, E) - 1
+                h0, h1 = e0 * batch.N, (e1 + 1) * batch.N - 1
                 o0, o1 = b1 + h0 // hpw, b1 + h1 // hpw
                 ready_orca = end[o0:o1 + 1].max()
-                ready = max(ready_orca, end[sb])
+                ready_env = end[e0 // 16:e1 // 16 + 1].max()
+                ready = max(ready_orca, ready_env)
                 lag.append(end[b3 + sb] - ready)
-                info.append((end[b3 + sb], ready_orca, end[sb], start[b3 + sb]))
+                info.append((end[b3 + sb], ready_orca, ready_env, start[b3 + sb]))
             lag = np.array(lag)
-            print("STATE end minus (its last ORCA wave's end, its ENV wave's end): p10/p50/p90/max %.2f %.2f %.2f %.2f us" % (
+            print("STATE end minus (its last ORCA wave's end, its last ENV wave's end): p10/p50/p90/max %.2f %.2f %.2f %.2f us" % (
                 np.percentile(lag, 10), np.percentile(lag, 50), np.percentile(lag, 90), lag.max()))
             last = np.argsort([q[0] for q in info])[-6:]
             print("   the 6 STATE waves that ended last (end, last ORCA end, ENV end, own start): " +
@@ -116,13 +116,7 @@ def report(np, name, rows, base):
     edges = np.arange(0, us(r1.max()) + 1.0, 1.0)
     print("   resident waves at t = 0, 1, 2 ... us: " + " ".join(str(int(((us(r0) <= x) & (us(r1) > x)).sum())) for x in edges))
     print("   started by t:                        " + " ".join(str(int((us(r0) <= x).sum())) for x in edges))
-    if name == "ENV" and rows[:, 5].any():
-        c0 = rows[:, 2].astype(np.int64)
-        mk = rows[:, 5:10].astype(np.int64)
-        names = ["start->loads ready", "robot action", "distances", "ordered reduce", "grid window", "reward + outputs"]
-        segs = [mk[:, 0] - c0] + [mk[:, q + 1] - mk[:, q] for q in range(4)] + [cyc - (mk[:, 4] - c0)]
-        print("   cycles mean: " + ", ".join("%s %.0f" % (n, v.mean()) for n, v in zip(names, segs)))
-    elif name == "ENV" and rows[:, 6].any():  # four lanes per env: marks 1 (action), 2 (quarters combined), 3 (grid), 4 (end)
+    if name == "ENV" and rows[:, 6].any():  # marks 1 (action), 2 (quarters combined), 3 (grid), 4 (end)
         c0 = rows[:, 2].astype(np.int64)
         mk = rows[:, 6:10].astype(np.int64) - c0[:, None]
         names = ["start->robot action done", "publish + humans + distances + combine", "grid window", "reward + outputs"]
