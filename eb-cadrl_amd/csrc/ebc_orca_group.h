@@ -22,7 +22,8 @@
 // operation.  What is re-associated is only min / max over candidate interval ends (exact, order
 // free) and the position of early exits (a failing prefix of linearProgram1 fails at the end as
 // well: tLeft only grows, tRight only shrinks).  Results are bit-identical to the scalar form;
-// tests/test_gpu_parity.py holds that bar.
+// tests/test_orca_branches_gpu.py holds that bar, at every instantiated group size and in every branch of RVO2
+// (tests/test_orca_branches_cpu.py asserts from the traced oracle that its batches reach them).
 #pragma once
 
 #include "ebc_device.h"

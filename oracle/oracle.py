@@ -31,44 +31,48 @@ def lib():
         path = os.path.join(_HERE, "libebc_oracle.so")
         if not os.path.exists(path):
             build()
-        L = C.CDLL(path)
-        d, i = C.c_double, C.c_int
-        pd = C.POINTER(C.c_double)
-        L.orc_point_to_segment_dist.restype = d
-        L.orc_point_to_segment_dist.argtypes = [d] * 6
-        L.orc_collision_agent_robot.restype = i
-        L.orc_collision_agent_robot.argtypes = [d] * 9 + [i] + [d] * 3 + [pd]
-        L.orc_grid_collision.restype = i
-        L.orc_grid_collision.argtypes = [C.c_void_p, i, d, d, d, d, d, C.c_void_p]
-        L.orc_reward.restype = None
-        L.orc_reward.argtypes = [C.c_void_p, C.c_void_p, d, d, d, C.c_void_p, C.c_void_p,
-                                 pd, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), pd]
-        L.orc_linear.restype = None
-        L.orc_linear.argtypes = [d] * 5 + [pd, pd]
-        L.orc_orca.restype = None
-        L.orc_orca.argtypes = [C.c_void_p] + [d] * 8 + [i] + [C.c_void_p] * 5 + [pd, pd]
-        L.orc_rvo2_agent0.restype = None
-        L.orc_rvo2_agent0.argtypes = [C.c_float, C.c_float, i, C.c_float, C.c_void_p, C.c_void_p,
-                                      C.c_float, C.c_float, C.c_void_p, i, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p]
-        L.orc_rotate_row.restype = None
-        L.orc_rotate_row.argtypes = [C.c_void_p, i, i, C.c_void_p]
-        L.orc_propagate_robot.restype = None
-        L.orc_propagate_robot.argtypes = [C.c_void_p, i, d, d, d, C.c_void_p]
-        L.orc_observe.restype = i
-        L.orc_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.orc_step.restype = i
-        L.orc_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.orc_lookahead.restype = i
-        L.orc_lookahead.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.orc_robot_orca.restype = i
-        L.orc_robot_orca.argtypes = [C.c_void_p, C.c_void_p, d, C.c_void_p]
-        L.orc_robot_orca_sim.restype = i
-        L.orc_robot_orca_sim.argtypes = [C.c_void_p, C.c_void_p, d, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.orc_set_threads.restype = i
-        L.orc_set_threads.argtypes = [i]
-        _LIB = L
+        _LIB = _declare(C.CDLL(path))
     return _LIB
+
+
+def _declare(L):
+    """argument / result types of the checker's entry points on a loaded library"""
+    d, i = C.c_double, C.c_int
+    pd = C.POINTER(C.c_double)
+    L.orc_point_to_segment_dist.restype = d
+    L.orc_point_to_segment_dist.argtypes = [d] * 6
+    L.orc_collision_agent_robot.restype = i
+    L.orc_collision_agent_robot.argtypes = [d] * 9 + [i] + [d] * 3 + [pd]
+    L.orc_grid_collision.restype = i
+    L.orc_grid_collision.argtypes = [C.c_void_p, i, d, d, d, d, d, C.c_void_p]
+    L.orc_reward.restype = None
+    L.orc_reward.argtypes = [C.c_void_p, C.c_void_p, d, d, d, C.c_void_p, C.c_void_p,
+                             pd, C.POINTER(C.c_uint8), C.POINTER(C.c_uint8), pd]
+    L.orc_linear.restype = None
+    L.orc_linear.argtypes = [d] * 5 + [pd, pd]
+    L.orc_orca.restype = None
+    L.orc_orca.argtypes = [C.c_void_p] + [d] * 8 + [i] + [C.c_void_p] * 5 + [pd, pd]
+    L.orc_rvo2_agent0.restype = None
+    L.orc_rvo2_agent0.argtypes = [C.c_float, C.c_float, i, C.c_float, C.c_void_p, C.c_void_p,
+                                  C.c_float, C.c_float, C.c_void_p, i, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]
+    L.orc_rotate_row.restype = None
+    L.orc_rotate_row.argtypes = [C.c_void_p, i, i, C.c_void_p]
+    L.orc_propagate_robot.restype = None
+    L.orc_propagate_robot.argtypes = [C.c_void_p, i, d, d, d, C.c_void_p]
+    L.orc_observe.restype = i
+    L.orc_observe.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_step.restype = i
+    L.orc_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_lookahead.restype = i
+    L.orc_lookahead.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_robot_orca.restype = i
+    L.orc_robot_orca.argtypes = [C.c_void_p, C.c_void_p, d, C.c_void_p]
+    L.orc_robot_orca_sim.restype = i
+    L.orc_robot_orca_sim.argtypes = [C.c_void_p, C.c_void_p, d, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.orc_set_threads.restype = i
+    L.orc_set_threads.argtypes = [i]
+    return L
 
 
 def set_threads(n):
@@ -143,18 +147,50 @@ def orca(params, self_state, others):
 
 
 def rvo2_agent0(time_step, neighbor_dist, max_neighbors, time_horizon, pos, vel, radius,
-                max_speed0, pref0):
-    """pos/vel [n][2], radius [n] float32 state of an rvo2 simulator; returns agent 0's new velocity."""
+                max_speed0, pref0, library=None):
+    """pos/vel [n][2], radius [n] float32 state of an rvo2 simulator; returns agent 0's new velocity.
+    library: a Traced().lib to count the branches taken (default: the plain checker)."""
     pos = np.ascontiguousarray(pos, dtype=np.float32)
     vel = np.ascontiguousarray(vel, dtype=np.float32)
     radius = np.ascontiguousarray(radius, dtype=np.float32)
     pref0 = np.ascontiguousarray(pref0, dtype=np.float32)
     out = np.zeros(2, np.float32)
-    lib().orc_rvo2_agent0(time_step, neighbor_dist, max_neighbors, time_horizon, pos[0].ctypes.data,
-                          vel[0].ctypes.data, float(radius[0]), max_speed0, pref0.ctypes.data,
-                          len(pos) - 1, pos[1:].ctypes.data, vel[1:].ctypes.data,
-                          radius[1:].ctypes.data, out.ctypes.data)
+    (library or lib()).orc_rvo2_agent0(time_step, neighbor_dist, max_neighbors, time_horizon, pos[0].ctypes.data,
+                                       vel[0].ctypes.data, float(radius[0]), max_speed0, pref0.ctypes.data,
+                                       len(pos) - 1, pos[1:].ctypes.data, vel[1:].ctypes.data,
+                                       radius[1:].ctypes.data, out.ctypes.data)
     return float(out[0]), float(out[1])
+
+
+TRACE_NAMES = ("line_colliding", "line_circle", "line_left_leg", "line_right_leg", "line_nan",
+               "nb_truncated", "nb_out_of_range", "nb_none",
+               "lp1_dir0", "lp1_dir1", "lp1_fail_discriminant", "lp1_fail_parallel", "lp1_fail_interval",
+               "lp1_parallel_skip",
+               "lp2_fail_at_0", "lp2_fail_at_1", "lp2_fail_at_2", "lp2_fail_at_3_or_more",
+               "lp3_entered", "lp3_bodies", "lp3_most_bodies", "lp3_parallel_same", "lp3_parallel_opposite",
+               "lp3_inner_fail", "agents")  # the ORC_TR_* enum of ebc_oracle.c, in its order
+
+
+class Traced:
+    """The checker compiled with -DORC_TRACE (make -C oracle trace) into `directory` and loaded beside the plain one:
+    OracleEnv(..., library=t.lib) and rvo2_agent0(..., library=t.lib) count the RVO2 branches they take into
+    t.counts() (lp3_most_bodies is a maximum, the others are sums) until t.reset().  Test infrastructure only."""
+
+    def __init__(self, directory):
+        so = os.path.join(os.path.abspath(directory), "libebc_oracle_trace.so")
+        subprocess.check_call(["make", "-s", "-C", _HERE, "trace", "TRACE_SO=" + so])
+        self.lib = _declare(C.CDLL(so))
+        self.lib.orc_trace_count.restype = C.c_int
+        assert self.lib.orc_trace_count() == len(TRACE_NAMES)
+        self._counts = (C.c_longlong * len(TRACE_NAMES)).in_dll(self.lib, "orc_trace_counts")
+        self.lib.orc_set_threads(1)
+
+    def reset(self):
+        for k in range(len(TRACE_NAMES)):
+            self._counts[k] = 0
+
+    def counts(self):
+        return {name: int(self._counts[k]) for k, name in enumerate(TRACE_NAMES)}
 
 
 def rotate_rows(rows15, with_agent_type, rotate_unicycle):
@@ -180,8 +216,9 @@ def propagate_robot(robot, kinematics, action, dt):
 class OracleEnv:
     """Same call surface as ebcsim.BatchedEnv, computed by the scalar C restatement."""
 
-    def __init__(self, params, n_envs, max_humans, max_static):
+    def __init__(self, params, n_envs, max_humans, max_static, library=None):
         self.params = params
+        self._lib = library  # None: the plain checker; Traced().lib: the one with branch counters
         self.E, self.N, self.S = n_envs, max_humans, max_static
         self.G = int(round(params.map_size_m / params.map_resolution))
         self.T = _abi.rot_width(params)
@@ -246,6 +283,9 @@ class OracleEnv:
         self.stride = (E if stride is None else stride) % P
         self.cursor = (E + np.arange(E) % P).astype(np.int32)
 
+    def _L(self):
+        return self._lib or lib()
+
     def _state(self):
         st = self._st
         st.E, st.N, st.S, st.G = self.E, self.N, self.S, self.G
@@ -297,7 +337,7 @@ class OracleEnv:
         args.flags = flags
         for k, v in out.items():
             setattr(args, k, v.ctypes.data)
-        rc = lib().orc_step(C.addressof(self.params), C.addressof(self._state()), C.addressof(args))
+        rc = self._L().orc_step(C.addressof(self.params), C.addressof(self._state()), C.addressof(args))
         if rc != 0:
             raise RuntimeError("orc_step failed: %d" % rc)
         return out
@@ -323,7 +363,7 @@ class OracleEnv:
         args.flags = flags
         for k, v in out.items():
             setattr(args, k, v.ctypes.data)
-        rc = lib().orc_lookahead(C.addressof(self.params), C.addressof(self._state()),
+        rc = self._L().orc_lookahead(C.addressof(self.params), C.addressof(self._state()),
                                  C.addressof(args))
         if rc != 0:
             raise RuntimeError("orc_lookahead failed: %d" % rc)
@@ -332,7 +372,7 @@ class OracleEnv:
     def observe(self):
         ob = np.zeros((self.E, self.R, 5))
         obs = np.zeros((self.E, self.R, self.T), np.float32)
-        lib().orc_observe(C.addressof(self.params), C.addressof(self._state()), ob.ctypes.data,
+        self._L().orc_observe(C.addressof(self.params), C.addressof(self._state()), ob.ctypes.data,
                           obs.ctypes.data)
         return ob, obs
 
@@ -357,11 +397,11 @@ class OracleEnv:
         act = np.zeros((self.E, 2))
         sim = getattr(self, "_sim", None)
         if sim is not None:
-            rc = lib().orc_robot_orca_sim(C.addressof(self.params), C.addressof(self._state()), float(safety_space),
+            rc = self._L().orc_robot_orca_sim(C.addressof(self.params), C.addressof(self._state()), float(safety_space),
                                           sim["rows"].ctypes.data, sim["radius"].ctypes.data, sim["self"].ctypes.data,
                                           act.ctypes.data)
         else:
-            rc = lib().orc_robot_orca(C.addressof(self.params), C.addressof(self._state()),
+            rc = self._L().orc_robot_orca(C.addressof(self.params), C.addressof(self._state()),
                                       float(safety_space), act.ctypes.data)
         if rc:
             raise RuntimeError("orc_robot_orca failed: %d" % rc)

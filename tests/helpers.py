@@ -385,3 +385,223 @@ class Guarded:
             else:
                 assert untouched.all(), "%d elements of %s written" % (int((~untouched).sum()), self.shape)
         return inside.view(self.np_dtype).reshape(self.shape)
+
+
+# ---- batches that drive the ORCA solver into every branch (tests/test_orca_branches_cpu.py asserts from the traced
+# oracle that they do; tests/test_orca_branches_gpu.py holds the kernels to the oracle on the same batches) ----------
+
+ORCA_GROUP_SIZES = (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32)  # kGroupSizes of csrc/ebcsim.hip
+
+
+def orca_group_size(others):
+    return next((g for g in ORCA_GROUP_SIZES if g >= others), 32)
+
+
+def _blank_batch(E, N, S):
+    f = lambda *s: np.zeros(s)  # noqa: E731
+    b = SceneBatch(E, N, S, np.full(E, N, np.int32), f(E, N), f(E, N), f(E, N), f(E, N), f(E, N), f(E, N), f(E, N),
+                   f(E, N), np.zeros((E, N), np.uint8), np.full(E, S, np.int32), f(E, max(S, 1)), f(E, max(S, 1)),
+                   f(E, max(S, 1)), None, f(E, 9))
+    b.robot[:] = [0.0, -30.0, 0.0, 0.0, 0.3, 0.0, 30.0, 0.7, np.pi / 2]  # out of everyone's range
+    return b
+
+
+def _ragged(rs, b):
+    """A third of the envs hold 0..N humans (0..S static rows): empty lanes inside groups, empty envs."""
+    for e in range(2, b.n, 3):
+        b.n_humans[e] = rs.randint(0, b.N + 1)
+        if b.S:
+            b.n_static[e] = rs.randint(0, b.S + 1)
+
+
+def _clear_unused(b):
+    for e in range(b.n):
+        for k in ("px", "py", "vx", "vy", "gx", "gy", "radius", "v_pref"):
+            getattr(b, k)[e, b.n_humans[e]:] = 0
+        for k in ("spx", "spy", "sradius"):
+            getattr(b, k)[e, b.n_static[e]:] = 0
+
+
+def orca_crowd(rs, E, N, box, S=0, robot_inside=False):
+    """Positions and goals uniform in [-box, box]^2, velocities in +-0.5, radius U(0.1, 0.5), v_pref U(0.3, 1.2); static
+    rows drawn like the positions, three in ten on top of a human; the robot, when it takes part, drawn like a human."""
+    b = _blank_batch(E, N, S)
+    _ragged(rs, b)
+    for k in ("px", "py", "gx", "gy"):
+        getattr(b, k)[:] = rs.uniform(-box, box, (E, N))
+    b.vx[:], b.vy[:] = rs.uniform(-0.5, 0.5, (E, N)), rs.uniform(-0.5, 0.5, (E, N))
+    b.radius[:], b.v_pref[:] = rs.uniform(0.1, 0.5, (E, N)), rs.uniform(0.3, 1.2, (E, N))
+    if S:
+        b.spx[:], b.spy[:] = rs.uniform(-box, box, (E, S)), rs.uniform(-box, box, (E, S))
+        b.sradius[:] = rs.uniform(0.1, 0.5, (E, S))
+        for e in range(E):
+            for j in range(S):
+                if b.n_humans[e] and rs.uniform() < 0.3:
+                    i = rs.randint(b.n_humans[e])
+                    b.spx[e, j], b.spy[e, j] = b.px[e, i], b.py[e, i]
+    if robot_inside:
+        b.robot[:, 0:2] = rs.uniform(-box, box, (E, 2))
+        b.robot[:, 2:4] = rs.uniform(-0.5, 0.5, (E, 2))
+        b.robot[:, 5:7] = rs.uniform(-box, box, (E, 2))
+    _clear_unused(b)
+    return b
+
+
+def orca_lattice(rs, E, N, spacing, S=0, robot_inside=False):
+    """Humans (then the robot, then the static rows while free cells last) on distinct cells of the smallest square
+    lattice that holds them, centred on the origin; spacing 0.5 or 0.75 is exact in float32, so squared distances tie
+    exactly and ORCA lines come out parallel.  Radius 0.3, v_pref 1, goal = -position, velocity = the unit vector to the
+    goal.  Both sides under test rank equal distances in insertion order; RVO2's kd-tree order for >= 11 agents is not
+    modelled."""
+    b = _blank_batch(E, N, S)
+    _ragged(rs, b)
+    side = int(np.ceil(np.sqrt(N + int(robot_inside))))
+    cells = (np.stack(np.meshgrid(np.arange(side), np.arange(side)), -1).reshape(-1, 2) - (side - 1) / 2.0) * spacing
+
+    def heading(p):
+        n = np.hypot(p[..., 0], p[..., 1])[..., None]
+        return np.where(n > 0, -p / np.where(n > 0, n, 1), 0.0)
+    for e in range(E):
+        order = rs.permutation(len(cells))
+        pos = cells[order[:N]]
+        b.px[e], b.py[e] = pos.T
+        b.gx[e], b.gy[e] = -pos.T
+        b.vx[e], b.vy[e] = heading(pos).T
+        rest = list(order[N:])
+        if robot_inside:
+            c = cells[rest.pop(0)]
+            b.robot[e, 0:2], b.robot[e, 5:7], b.robot[e, 2:4] = c, -c, heading(c) * 0.7
+        for j in range(S):  # on a free cell, else on top of a human
+            c = cells[rest.pop(0)] if rest else pos[rs.randint(N)]
+            b.spx[e, j], b.spy[e, j] = c
+    b.radius[:], b.v_pref[:] = 0.3, 1.0
+    b.sradius[:] = 0.3 if S else 0.0
+    _clear_unused(b)
+    return b
+
+
+def orca_twins(rs, E, N, box, prob=0.3, S=0, robot_inside=False):
+    """orca_crowd in which each human i >= 1 (and the robot, when it takes part) copies, with probability prob, the
+    position and radius of a random earlier human; half of those copy its velocity too: relative position AND velocity
+    zero, w = 0, a NaN ORCA line.  The others keep their own: a finite line from a zero relative position."""
+    b = orca_crowd(rs, E, N, box, S, robot_inside)
+    for e in range(E):
+        n = int(b.n_humans[e])
+        for i in list(range(1, n)) + ([N] if robot_inside and n else []):
+            if rs.uniform() < prob:
+                k = rs.randint(min(i, n))
+                same_velocity = rs.uniform() < 0.5
+                if i < N:
+                    b.px[e, i], b.py[e, i], b.radius[e, i] = b.px[e, k], b.py[e, k], b.radius[e, k]
+                    if same_velocity:
+                        b.vx[e, i], b.vy[e, i] = b.vx[e, k], b.vy[e, k]
+                else:
+                    b.robot[e, 0:2] = b.px[e, k], b.py[e, k]
+                    if same_velocity:
+                        b.robot[e, 2:4] = b.vx[e, k], b.vy[e, k]
+    return b
+
+
+def concat_batches(parts):
+    b = _blank_batch(sum(p.n for p in parts), parts[0].N, parts[0].S)
+    for k in ("n_humans", "px", "py", "vx", "vy", "gx", "gy", "radius", "v_pref", "type", "n_static", "spx", "spy",
+              "sradius", "robot"):
+        setattr(b, k, np.concatenate([getattr(p, k) for p in parts]))
+    return b
+
+
+def orca_branch_batch(seed, N, lanes, S=0, robot_inside=False):
+    """One batch for one (N, S): crowd(4), crowd(1), lattice(0.5), lattice(0.75) and twins(1.5) one after the other, 24 to
+    32 envs each.  `lanes` is the ORCA group size the batch is meant for: the number of envs is odd and, where such a
+    number exists, neither it nor the number of humans is a multiple of the groups per wave (64 // lanes), so the
+    last wave of a launch is partly filled."""
+    rs = np.random.RandomState(seed)
+    per_wave = 64 // lanes
+    sizes = [(c, c2) for c in range(27, 33) for c2 in range(24, 33) if (4 * c + c2) % 2 == 1]
+    c, c2 = max(sizes, key=lambda s: int((4 * s[0] + s[1]) * N % per_wave != 0) + int((4 * s[0] + s[1]) % per_wave != 0))
+    kw = dict(S=S, robot_inside=robot_inside)
+    return concat_batches([orca_crowd(rs, c, N, 4.0, **kw), orca_crowd(rs, c, N, 1.0, **kw),
+                           orca_lattice(rs, c, N, 0.5, **kw), orca_lattice(rs, c, N, 0.75, **kw),
+                           orca_twins(rs, c2, N, 1.5, **kw)])
+
+
+# (humans, robot_visible): every group size, each both full and with spare lanes
+ORCA_HUMAN_COUNTS = [(n, 0) for n in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 17, 18, 22, 23, 33)] + [(10, 1), (32, 1)]
+# name -> (maxNeighbors, neighborDist)
+ORCA_PARAM_SETS = {"default": (10, 10.0), "mn3-nd2": (3, 2.0), "mn1": (1, 10.0), "mn0": (0, 10.0)}
+ORCA_HUMAN_CASES = ([(n, rv, ps) for n, rv in ORCA_HUMAN_COUNTS for ps in ("default", "mn3-nd2")]
+                    + [(n, 0, ps) for n in (6, 13) for ps in ("mn1", "mn0")])
+# (humans, static rows) of the robot's own ORCA: rows 1..13, 16, 17, 21, 22, 32
+ORCA_ROBOT_CASES = [(r, 0) for r in (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 16, 17, 22)] + [(6, 4), (10, 11), (20, 12)]
+ORCA_STEPS = 3
+
+
+def orca_case_id(case):
+    return "N%d%s-%s" % (case[0], "+robot" if case[1] else "", case[2]) if len(case) == 3 else "N%d-S%d" % case
+
+
+def orca_case_params(rv=0, param_set="default"):
+    params = params_of(load("traj_n10_walls_t17_orcasub"))  # time_step 0.25, horizon 5
+    params.robot_visible = rv
+    params.orca_max_neighbors, params.orca_neighbor_dist = ORCA_PARAM_SETS[param_set]
+    return params
+
+
+_orca_batches = {}
+
+
+def orca_human_batch(N, rv):
+    """The batch of a human count: the same under every parameter set, for the CPU and the GPU tests alike."""
+    if (N, rv) not in _orca_batches:
+        _orca_batches[N, rv] = orca_branch_batch(52000 + 10 * N + rv, N, orca_group_size(max(N - 1 + rv, 1)),
+                                                 robot_inside=bool(rv))
+    return _orca_batches[N, rv]
+
+
+def orca_robot_batch(N, S):
+    if (N, S, "robot") not in _orca_batches:
+        _orca_batches[N, S, "robot"] = orca_branch_batch(67000 + 100 * N + S, N, orca_group_size(N + S), S=S,
+                                                         robot_inside=True)
+    return _orca_batches[N, S, "robot"]
+
+
+def orca_robot_actions(E):
+    """The robot's supplied action of every step: [ORCA_STEPS, E, 2] from the holonomic action space."""
+    from ebcsim import actions as ebc_actions
+    space = ebc_actions.build_action_space(0.7)
+    return space[np.random.RandomState(4242).randint(len(space), size=(ORCA_STEPS, E))]
+
+
+_orca_refs = {}
+
+
+def orca_reference(case, library=None):
+    """What the oracle computes for a case of ORCA_HUMAN_CASES, once per session for the plain library: the outputs of
+    ORCA_STEPS steps from reset under HUMAN_ORCA with the supplied robot actions, and the state after each."""
+    from oracle import oracle
+    if library is None and case in _orca_refs:
+        return _orca_refs[case]
+    N, rv, ps = case
+    b = orca_human_batch(N, rv)
+    o = oracle.OracleEnv(orca_case_params(rv, ps), b.n, N, 0, library=library)
+    o.reset(b)
+    act = orca_robot_actions(b.n)
+    ref = dict(out=[], state=[])
+    for t in range(ORCA_STEPS):
+        ref["out"].append(o.step(robot_action=act[t], human_policy=_abi.HUMAN_ORCA))
+        ref["state"].append(o.get_state())
+    if library is None:
+        for v in ref["out"] + ref["state"]:
+            for a in v.values():
+                a.flags.writeable = False
+        _orca_refs[case] = ref
+    return ref
+
+
+def orca_robot_reference(case, safety, library=None):
+    from oracle import oracle
+    N, S = case
+    b = orca_robot_batch(N, S)
+    o = oracle.OracleEnv(orca_case_params(), b.n, N, S, library=library)
+    o.reset(b)
+    return o.robot_orca(safety)
