@@ -63,6 +63,15 @@ __device__ __forceinline__ void robot_next_position(const double *rb, int kin, d
   }
 }
 
+// bits [s, e) of a 64-bit word, both ends clamped to [0, 64]
+__device__ __forceinline__ uint64_t half_mask(long s, long e) {
+  s = s < 0 ? 0 : s;
+  e = e > 64 ? 64 : e;
+  if (e <= s) return 0;
+  const uint64_t upto_e = e == 64 ? ~(uint64_t)0 : ((uint64_t)1 << e) - 1;
+  return upto_e & ~(((uint64_t)1 << s) - 1);  // s < e <= 64 here
+}
+
 // simulator/env.py:227-271: window of the 128-bit-row occupancy grid around the
 // robot's NEXT position; round() is half-to-even = rint.
 __device__ __forceinline__ int grid_collision(const uint64_t *grid, int G, double map_size_m,
@@ -84,10 +93,9 @@ __device__ __forceinline__ int grid_collision(const uint64_t *grid, int G, doubl
       ex = ex > G ? G : ex;
       ey = ey > G ? G : ey;
       if (ey > sy) {
-        // mask of columns [sy, ey) in the two 64-bit halves of a row
-        const int w = (int)(ey - sy);
-        const unsigned __int128 mask = (((unsigned __int128)1 << w) - 1) << sy;
-        const uint64_t lo = (uint64_t)mask, hi = (uint64_t)(mask >> 64);
+        // mask of columns [sy, ey) in the two 64-bit halves of a row; each half is built from its own clamped ends,
+        // so a window over all 128 columns needs no shift by the width of the type
+        const uint64_t lo = half_mask(sy, ey), hi = half_mask(sy - 64, ey - 64);
         // rows [sx, ex): the first eight are loaded together (robot radius <= 0.56 m at 0.1 m
         // cells never needs more), the rest in a plain loop
         uint64_t acc = 0;

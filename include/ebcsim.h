@@ -134,7 +134,9 @@ typedef struct EbcScene {
   int32_t n;
   const int32_t *n_humans;   /* [n] */
   const double *px, *py, *vx, *vy, *gx, *gy, *radius, *v_pref; /* [n][N] */
-  const uint8_t *type;       /* [n][N] AgentType */
+  const uint8_t *type;       /* [n][N] AgentType 0..2.  The reference lays humans out type-major, but nothing here needs
+                              * it: collisions and dmin walk each type's humans in index order whatever the layout,
+                              * so interleaved types are accepted and give what the reference's per-type lists would */
   const int32_t *n_static;   /* [n] (may be NULL when S == 0) */
   const double *spx, *spy, *sradius; /* [n][S] static_obstacles_as_pedestrians */
   const uint64_t *grid;      /* [n][G][2] or NULL */

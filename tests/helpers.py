@@ -605,3 +605,619 @@ def orca_robot_reference(case, safety, library=None):
     o = oracle.OracleEnv(orca_case_params(), b.n, N, S, library=library)
     o.reset(b)
     return o.robot_orca(safety)
+
+
+# ---- the robot side of a step: collision per type, dmin, reward, done, info (tests/test_robot_outcome_cpu.py asserts
+# the recipes and the coverage on the oracle; tests/test_robot_outcome_gpu.py holds the four kernels that restate the
+# reduction to the same answers) -----------------------------------------------------------------------------------
+
+OUTCOME_FORMS = ("step", "orca", "lookahead", "one_launch")  # step_kernel, orca_step_kernel, lookahead_kernel, rollout_kernel
+OUTCOME_KEYS = ("reward", "done", "info", "dmin", "dist_to_goal")
+COLLISION_CODE = (_abi.INFO_COLLISION_ADULT, _abi.INFO_COLLISION_BICYCLE, _abi.INFO_COLLISION_CHILD)
+LA_CHUNK = 127  # envs = actions of one look-ahead call: under the 128 the call takes, and no multiple of a wave
+FAR_GOAL = 50.0
+
+
+def outcome_params(kinematics=_abi.HOLONOMIC, dt=0.25, **kw):
+    """Holonomic / unicycle parameters on the 9.0 m / 0.1 m map with an invisible robot; kw sets fields (tuples: arrays)."""
+    import ctypes
+    p = params_of(load("traj_n10_walls_t17_orcasub"))
+    p.robot_kinematics, p.time_step, p.robot_visible, p.time_limit = kinematics, dt, 0, 25.0
+    p.map_size_m, p.map_resolution = 9.0, 0.1
+    for k, v in kw.items():
+        setattr(p, k, (ctypes.c_double * len(v))(*v) if isinstance(v, (tuple, list)) else v)
+    return p
+
+
+def batch_rows(b, ids):
+    """The envs `ids` of a batch as a batch of their own."""
+    ids = np.asarray(ids)
+    f = lambda a: np.ascontiguousarray(a[ids])  # noqa: E731
+    return SceneBatch(len(ids), b.N, b.S, f(b.n_humans), f(b.px), f(b.py), f(b.vx), f(b.vy), f(b.gx), f(b.gy),
+                      f(b.radius), f(b.v_pref), f(b.type), f(b.n_static), f(b.spx), f(b.spy), f(b.sradius),
+                      None if b.grid is None else f(b.grid), f(b.robot))
+
+
+def split_off_wave_multiples(ids):
+    """`ids` as it is, or in two odd-sized parts when its length is a multiple of 4 (of the four-lanes-per-env packing,
+    hence of every envs-per-wave count and of 64): every launch then ends in a part-filled wave."""
+    ids = np.asarray(ids)
+    if len(ids) % 4 or len(ids) < 4:
+        return [ids]
+    cut = len(ids) // 2 + (1 if (len(ids) // 2) % 2 == 0 else 0)
+    return [ids[:cut], ids[cut:]]
+
+
+def _close(env):
+    if hasattr(env, "close"):
+        env.close()
+
+
+def robot_outcome_forms(make_env, params, b, act, border=None, forms=OUTCOME_FORMS):
+    """One step of batch `b` under the supplied robot actions `act` [E, 2], from reset, once per form ->
+    {form: {reward, done, info, dmin, dist_to_goal}} (the look-ahead has no dist_to_goal; the one-launch form takes no
+    border and is left out when there is one).  The look-ahead runs LA_CHUNK envs at a time with the chunk's own
+    actions as the action set, and the diagonal (env i, action i) is what it reports for env i."""
+    E = b.n
+    act = np.ascontiguousarray(act, dtype=np.float64).reshape(E, 2)
+    res = {}
+    env = make_env(params, E, b.N, b.S)
+    for form in forms:
+        if form == "lookahead" or (form == "one_launch" and border is not None):
+            continue
+        env.reset(b)
+        if form == "step":
+            o = env.step(robot_action=act, human_policy=_abi.HUMAN_LINEAR, border=border)
+        elif form == "orca":
+            o = env.step(robot_action=act, human_policy=_abi.HUMAN_ORCA, border=border)
+        else:
+            o = env.step_k(1, OUTCOME_KEYS, robot_action=act[None], human_policy=_abi.HUMAN_ORCA,
+                           robot_policy=_abi.ROBOT_EXTERNAL, flags=_abi.FLAG_ONE_LAUNCH)
+            o = {k: v[0] for k, v in o.items()}
+        res[form] = {k: np.array(o[k]) for k in OUTCOME_KEYS}
+    _close(env)
+    if "lookahead" in forms:
+        c = min(LA_CHUNK, E)
+        env = make_env(params, c, b.N, b.S)
+        parts = {k: [] for k in ("reward", "done", "info", "dmin")}
+        for lo in range(0, E, c):
+            ids = np.arange(lo, min(lo + c, E))
+            m = len(ids)
+            env.reset(batch_rows(b, ids))  # a short last chunk leaves the other envs on the chunk before
+            a = np.concatenate([act[ids], np.repeat(act[ids][-1:], c - m, 0)])
+            la = env.lookahead(a, human_policy=_abi.HUMAN_LINEAR, border=border, want_rows=False)
+            d = np.arange(m)
+            for k in parts:
+                parts[k].append(la[k][d, d])
+        _close(env)
+        res["lookahead"] = {k: np.concatenate(v) for k, v in parts.items()}
+    return res
+
+
+def assert_forms_agree(res, tag):
+    """reward, done, info, dmin (dist_to_goal where both have it): byte for byte between every two forms."""
+    names = list(res)
+    for name in names[1:]:
+        for k in OUTCOME_KEYS:
+            if k in res[names[0]] and k in res[name]:
+                x, y = res[names[0]][k], res[name][k]
+                assert x.shape == y.shape and x.astype(y.dtype).tobytes() == y.tobytes(), \
+                    "%s: %s of %s and %s differ (first env %s)" % (tag, k, names[0], name, np.argwhere(
+                        ~((x == y) | ((x != x) & (y != y))))[:1].tolist())
+
+
+def assert_outcome(got, ref, tag, atol=1e-9):
+    """done and info exact; reward, dmin and dist_to_goal at the project's 1e-9 (inf equal to inf)."""
+    np.testing.assert_array_equal(got["done"].astype(bool), ref["done"].astype(bool), err_msg=tag + " done")
+    np.testing.assert_array_equal(got["info"], ref["info"], err_msg=tag + " info")
+    for k in ("reward", "dmin", "dist_to_goal"):
+        if k in got:
+            np.testing.assert_allclose(got[k], ref[k], atol=atol, rtol=0, err_msg=tag + " " + k)
+
+
+def oracle_env(params, E, N, S):
+    from oracle import oracle
+    return oracle.OracleEnv(params, E, N, S)
+
+
+def oracle_outcome(params, b, act, border=None):
+    return robot_outcome_forms(oracle_env, params, b, act, border, forms=("step",))["step"]
+
+
+def _robot_rows(b, px, py, radius, theta=0.0, goal=None):
+    b.robot[:] = 0
+    b.robot[:, 0], b.robot[:, 1], b.robot[:, 4], b.robot[:, 7], b.robot[:, 8] = px, py, radius, 1.0, theta
+    b.robot[:, 5], b.robot[:, 6] = (FAR_GOAL, FAR_GOAL) if goal is None else goal
+
+
+# -- 1. tests/golden/collisions.npz: one env per row
+
+def golden_collision_groups():
+    """(fixture, {(kinematics, dt): row indices}): dt = 0.25 holds all but the reference's own six unit rows."""
+    z = load("collisions")
+    groups = {}
+    for k in range(len(z["h"])):
+        groups.setdefault((int(z["kin"][k]), float(z["dt"][k])), []).append(k)
+    return z, {key: np.array(v) for key, v in groups.items()}
+
+
+def golden_collision_batch(z, rows):
+    """n = 1: the human at h with h's velocity and its goal where it stands, type = row index % 3; the robot at r with
+    its heading in slot 8 and a far goal -> (batch, the rows' actions)."""
+    b = _blank_batch(len(rows), 1, 0)
+    h, r = z["h"][rows], z["r"][rows]
+    b.px[:, 0], b.py[:, 0], b.vx[:, 0], b.vy[:, 0], b.radius[:, 0] = h.T
+    b.gx[:, 0], b.gy[:, 0], b.v_pref[:, 0] = h[:, 0], h[:, 1], 1.0
+    b.type[:, 0] = rows % 3
+    _robot_rows(b, r[:, 0], r[:, 1], r[:, 3], theta=r[:, 2])
+    return b, z["act"][rows]
+
+
+def check_golden_collisions(make_env, forms=OUTCOME_FORMS):
+    """Every row of collisions.npz through every form -> {form: (holonomic rows not bit-identical to the reference,
+    holonomic rows, largest |difference| on the unicycle rows)} after the assertions of the issue."""
+    z, groups = golden_collision_groups()
+    n = len(z["h"])
+    typ = np.arange(n) % 3
+    got = {}  # form -> (flag [n], min(dmin_in, dmin[type]) [n])
+    for (kin, dt), all_rows in sorted(groups.items()):
+        params = outcome_params(kin, dt)
+        for rows in split_off_wave_multiples(all_rows):
+            b, act = golden_collision_batch(z, rows)
+            res = robot_outcome_forms(make_env, params, b, act, forms=forms)
+            assert_forms_agree(res, "kin %d dt %g" % (kin, dt))
+            for form, o in res.items():
+                flag, dm = got.setdefault(form, (np.zeros(n, bool), np.zeros(n)))
+                t = typ[rows]
+                code = np.array(COLLISION_CODE)[t]
+                is_code = np.isin(o["info"], COLLISION_CODE)
+                assert (is_code <= (o["info"] == code)).all(), "%s: another type's collision code" % form
+                flag[rows] = o["info"] == code
+                others = np.ones((len(rows), 3), bool)
+                others[np.arange(len(rows)), t] = False
+                assert np.isinf(o["dmin"][others]).all(), "%s: dmin of a type with no member" % form
+                own = o["dmin"][np.arange(len(rows)), t]
+                assert np.isinf(own[flag[rows]]).all(), "%s: a colliding row reports a finite dmin" % form
+                dm[rows] = np.minimum(z["dmin_in"][rows], own)
+    stats = {}
+    hol = z["kin"] == _abi.HOLONOMIC
+    ref = z["dmin_out"]
+    for form, (flag, dm) in got.items():
+        np.testing.assert_array_equal(flag, z["coll"], err_msg=form + " collision flag")
+        for k in range(int(z["n_unit"])):
+            assert bool(flag[k]) == bool(z["unit_expected"][k]), (form, "unit row", k)
+        both_inf = np.isinf(dm) & np.isinf(ref) & (dm == ref)
+        with np.errstate(invalid="ignore"):
+            diff = np.where(both_inf, 0.0, np.abs(dm - ref))
+        assert not np.isnan(diff).any() and np.isfinite(diff).all(), form
+        not_identical = int((dm[hol] != ref[hol]).sum())
+        worst_uni = float(diff[~hol].max())
+        print("golden collisions, %-10s %d envs: %d of %d holonomic rows not bit-identical (cap %d), largest holonomic "
+              "|diff| %.3g, largest unicycle |diff| %.3g" % (form, n, not_identical, int(hol.sum()),
+                                                            int(0.02 * hol.sum()), float(diff[hol].max()), worst_uni))
+        assert diff[hol].max() <= 1e-12, (form, "holonomic", float(diff[hol].max()))
+        assert not_identical <= 0.02 * hol.sum(), (form, not_identical)
+        assert worst_uni <= 1e-9, (form, "unicycle", worst_uni)
+        stats[form] = (not_identical, int(hol.sum()), worst_uni)
+    return stats
+
+
+# -- 2. tests/golden/grid.npz: one env per point
+
+def _grid_point_batch(packed, pts):
+    """n = 0 (the one human slot unused), the robot at the point with the point's radius, that map as the env's grid."""
+    b = _blank_batch(len(pts), 1, 0)
+    b.n_humans[:] = 0
+    b.grid = np.ascontiguousarray(packed, dtype=np.uint64)
+    _robot_rows(b, pts[:, 0], pts[:, 1], pts[:, 2])
+    return b
+
+
+def golden_grid_batches():
+    """[(batch, border or None, expected collision)] over all 18 x 400 points of grid.npz: the rows that used the
+    fixture's border as calls of their own."""
+    z = load("grid")
+    packed, pts, exp = [], [], []
+    for k in range(int(z["n"])):
+        g = pack_grid(1.0 - z["grid_%d" % k])
+        packed += [g] * len(z["pts_%d" % k])
+        pts.append(z["pts_%d" % k])
+        exp.append(z["coll_%d" % k])
+    packed, pts, exp = np.stack(packed), np.concatenate(pts), np.concatenate(exp).astype(bool)
+    out = []
+    for use_border in (False, True):
+        for ids in split_off_wave_multiples(np.nonzero(pts[:, 3].astype(bool) == use_border)[0]):
+            out.append((_grid_point_batch(packed[ids], pts[ids]), z["border"] if use_border else None, exp[ids]))
+    assert sum(b.n for b, _, _ in out) == len(pts) and float(z["map_size_m"]) == 9.0 and float(z["map_resolution"]) == 0.1
+    return out
+
+
+def check_obstacle_outcome(make_env, params, b, border, expected, tag, forms=OUTCOME_FORMS):
+    """Standing robots with no human: info is INFO_COLLISION_OBSTACLE (terminal) exactly where expected, else a
+    non-terminal INFO_NOTHING, in every form, and the forms agree byte for byte."""
+    res = robot_outcome_forms(make_env, params, b, np.zeros((b.n, 2)), border, forms)
+    assert_forms_agree(res, tag)
+    want = np.where(expected, _abi.INFO_COLLISION_OBSTACLE, _abi.INFO_NOTHING)
+    for form, o in res.items():
+        bad = np.nonzero(o["info"] != want)[0]
+        assert not len(bad), "%s %s: %d of %d envs, the first %d: info %d, expected %d" % (
+            tag, form, len(bad), b.n, bad[0], o["info"][bad[0]], want[bad[0]])
+        np.testing.assert_array_equal(o["done"].astype(bool), expected, err_msg=tag + " " + form)
+    return res
+
+
+# -- 3. grid windows the goldens do not reach
+
+def grid_window_restated(occ, map_size_m, map_resolution, px, py, radius, border=None):
+    """simulator/env.py:227-271 in plain Python / numpy: indices rounded half to even, the clipped slice, .any()."""
+    lim = int(round(map_size_m / map_resolution))
+    ix = int(round((px + map_size_m / 2.0) / map_resolution))
+    iy = int(round((py + map_size_m / 2.0) / map_resolution))
+    h = int(np.ceil(radius / np.sqrt(2.0) / map_resolution))
+    sx, ex = max(ix - h, 0), min(ix - h + 2 * h, lim)
+    sy, ey = max(iy - h, 0), min(iy - h + 2 * h, lim)
+    hit = False
+    if ex > sx and ey > sy:
+        hit = bool(occ[sx:ex, sy:ey].any())
+    if border is not None:
+        hit = hit or bool(px <= border[0] + radius or px >= border[1] - radius or py <= border[2] + radius
+                          or py >= border[3] - radius)
+    return hit
+
+
+GRID_MAPS = ((9.0, 0.1), (9.0, 0.075), (12.8, 0.1))  # G = 90, 120, 128
+GRID_RADII = (0.6, 0.9, 1.5)  # windows of 10, 14 and 22 rows at 0.1 m: the row loop after the eight unrolled rows runs
+GRID_BORDER = (-3.0, 3.0, -2.5, 3.5)
+WIDE_RADIUS = 9.0  # ceil(9 / sqrt(2) / 0.1) = 64: from index 64 the window spans all 128 columns of a G = 128 map
+
+
+def grid_window_cases(map_size_m, res):
+    """[(occupied [G, G] bool, px, py, radius, border or None, note)] for one map geometry."""
+    G = int(round(map_size_m / res))
+    half = map_size_m / 2.0
+    cases = []
+
+    def cell_map(cells):
+        occ = np.zeros((G, G), bool)
+        for x, y in cells:
+            if 0 <= x < G and 0 <= y < G:
+                occ[x, y] = True
+        return occ
+
+    def at(i, frac=0.0):  # the coordinate of index i (+ frac cells: 0.5 is the half-cell boundary)
+        return (i + frac) * res - half
+    for radius in GRID_RADII:
+        h = int(np.ceil(radius / np.sqrt(2.0) / res))
+        mid = G // 2
+        # a single occupied cell at the first / last column (row) of the window and one outside it on each side
+        targets = [(mid, c) for c in (0, 63, 64, G - 1)] + [(r, mid) for r in (0, G - 1)]
+        for (r, c) in targets:
+            occ = cell_map([(r, c)])
+            for off in (-h, -h + 1, h, h + 1):
+                for frac in (0.0, 0.5, -0.5):
+                    cases.append((occ, at(r), at(c + off, frac), radius, None, "cell (%d, %d) column offset %d" % (r, c, off)))
+                    cases.append((occ, at(r + off, frac), at(c), radius, None, "cell (%d, %d) row offset %d" % (r, c, off)))
+        # the only occupied cells lie one column / row outside the window on each side; and just inside it
+        for ci in (mid, h, G - h):
+            lo, hi = ci - h, ci + h  # the window is [lo, hi)
+            ring = [(ci, lo - 1), (ci, hi), (lo - 1, ci), (hi, ci), (lo - 1, lo - 1), (hi, hi)]
+            cases.append((cell_map(ring), at(ci), at(ci), radius, None, "cells one outside the window"))
+            for cell in ((ci, lo), (ci, hi - 1), (lo, ci), (hi - 1, ci)):
+                cases.append((cell_map([cell]), at(ci), at(ci), radius, None, "cell on the window's edge"))
+        # the four corners and points up to a radius outside the map, on a map with every cell occupied and on one with
+        # the four corner cells: the window clips to a sliver, then to nothing
+        corners = cell_map([(0, 0), (0, G - 1), (G - 1, 0), (G - 1, G - 1)])
+        full = np.ones((G, G), bool)
+        for sx in (-1, 1):
+            for sy in (-1, 1):
+                for out in (0.0, 0.25, 0.5, 0.75, 1.0, 1.25):
+                    for occ in (corners, full):
+                        cases.append((occ, sx * (half + out * radius), sy * half, radius, None, "outside in x"))
+                        cases.append((occ, sx * half, sy * (half + out * radius), radius, None, "outside in y"))
+                        cases.append((occ, sx * (half + out * radius), sy * (half + out * radius), radius, None, "outside in both"))
+    # the border's four equalities (<= / >=: a collision) and one ulp inside each (none), on an empty map
+    empty = np.zeros((G, G), bool)
+    r, bd = 1.5, GRID_BORDER
+    for px, py, inward in ((bd[0] + r, 0.5, (1, 0)), (bd[1] - r, 0.5, (-1, 0)), (0.0, bd[2] + r, (0, 1)), (0.0, bd[3] - r, (0, -1))):
+        cases.append((empty, px, py, r, bd, "border equality"))
+        cases.append((empty, float(np.nextafter(px, px + inward[0])) if inward[0] else px,
+                      float(np.nextafter(py, py + inward[1])) if inward[1] else py, r, bd, "one ulp inside the border"))
+    cases.append((empty, 0.0, 0.5, r, bd, "well inside the border"))
+    if G == 128:  # the window over all 128 columns, and over 127 and 126 of them
+        for iy in (64, 65, 63, 62):
+            for cell in ((5, 127), (5, 0), (5, 64), (5, 63), (127, 126), None):
+                occ = cell_map([cell] if cell else [])
+                cases.append((occ, at(64), at(iy), WIDE_RADIUS, None, "wide window at column index %d" % iy))
+    return cases
+
+
+def grid_window_batches(map_size_m, res):
+    """[(batch, border, expected from the restatement, notes)] of a geometry: the border cases as a call of their own."""
+    cases = grid_window_cases(map_size_m, res)
+    out = []
+    for with_border in (False, True):
+        sel = [c for c in cases if (c[4] is not None) == with_border]
+        while len(sel) % 4 == 0:
+            sel.append(sel[len(sel) // 3])
+        pts = np.array([[c[1], c[2], c[3]] for c in sel])
+        b = _grid_point_batch(np.stack([pack_grid(1.0 - c[0].astype(np.float64)) for c in sel]), pts)
+        border = GRID_BORDER if with_border else None
+        exp = np.array([grid_window_restated(c[0], map_size_m, res, c[1], c[2], c[3], border) for c in sel])
+        out.append((b, border, exp, [c[5] for c in sel], [c[0] for c in sel]))
+    return out
+
+
+# -- 4. the ordered per-type reduction: standing humans at exact gaps around a standing robot
+
+ORDERED_COUNTS = (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 17, 24, 25, 32, 33)
+ORDERED_ENVS = 203  # 7 * 29: no multiple of 4 lanes per env, 16 envs per wave or 64
+ROBOT_RADIUS = 0.25
+COLLIDER = -1.0 / 16
+
+
+def place_standing(b, e, i, gap, origin=(0.0, 0.0)):
+    """Human i of env e stands still on axis i % 4, radius 0.25 + (i // 4) / 8, its boundary `gap` from the robot's
+    (radius 0.25 at `origin`): all binary fractions, so the reference distance is exactly `gap`."""
+    rad = 0.25 + (i // 4) * 0.125
+    d = ROBOT_RADIUS + rad + gap
+    ax, ay = ((1, 0), (0, 1), (-1, 0), (0, -1))[i % 4]
+    b.px[e, i], b.py[e, i] = origin[0] + ax * d, origin[1] + ay * d
+    b.gx[e, i], b.gy[e, i] = b.px[e, i], b.py[e, i]
+    b.vx[e, i] = b.vy[e, i] = 0.0
+    b.radius[e, i], b.v_pref[e, i] = rad, 1.0
+
+
+def _distinct_gaps(gap, n):
+    """Two humans on one axis must not stand on one spot (ORCA's coincident twins are not this test's business): a
+    non-collider that would is moved out by 1/64 until it does not."""
+    for i in range(n):
+        def spot(j):
+            return 0.25 + (j // 4) * 0.125 + gap[j]
+        while gap[i] >= 0 and any(spot(j) == spot(i) for j in range(i % 4, n, 4) if j != i):
+            gap[i] = gap[i] + 1.0 / 64 if gap[i] < 63.0 / 64 else 1.0 / 64
+    return gap
+
+
+def ordered_batch(N, interleaved):
+    """ORDERED_ENVS envs of up to N standing humans (b.gap [E, N] holds the exact distances): hand-built envs for the
+    order-dependent cases first, a seeded random fill after them.  Types are grouped as SceneBatch.from_scenes lays
+    them out, or, with `interleaved`, mixed by index."""
+    rs = np.random.RandomState(9100 + 2 * N + int(interleaved))
+    E = ORDERED_ENVS
+    b = _blank_batch(E, N, 0)
+    _robot_rows(b, 0.0, 0.0, ROBOT_RADIUS)
+    gap = np.full((E, N), 0.5)
+    typ = np.zeros((E, N), np.uint8)
+    n_h = np.full(E, N, np.int32)
+    c = -(-N // 4)  # the humans of one quarter
+    e = 0
+    n_h[e] = 0  # an empty env
+    e += 1
+    if N >= 5:
+        for t in range(3):
+            for q in range(4):
+                fi = q * c  # the first collider of type t opens quarter q
+                if fi >= N:
+                    continue
+                typ[e] = [(t + 1 + i % 2) % 3 for i in range(N)] if interleaved else t
+                keys = [0, fi] + [i for i in (fi + 1, fi + 2) if i < N]
+                typ[e, keys] = t
+                gap[e, fi] = COLLIDER
+                if q > 0:
+                    gap[e, 0] = 8.0 / 64  # the closest of its type, a quarter earlier: counts
+                if fi + 1 < N:
+                    gap[e, fi + 1] = 1.0 / 64  # closer still, behind the collider: ignored
+                if fi + 2 < N:
+                    gap[e, fi + 2] = COLLIDER  # a second collider behind the first
+                e += 1
+        for hit in ((0, 1), (0, 2), (1, 2), (0, 1, 2)):  # two and three types collide in one env
+            typ[e] = np.arange(N) % 3 if interleaved else np.sort(np.arange(N) % 3)
+            for t in hit:
+                gap[e, int(np.argmax(typ[e] == t))] = COLLIDER
+            e += 1
+    while e < E:
+        n_h[e] = N - rs.randint(0, min(N, 3) + 1)  # ragged: n in [N - 3, N]
+        kinds = rs.choice(3, size=rs.randint(1, 4), replace=False)  # one to three types present
+        typ[e] = rs.choice(kinds, size=N)
+        if not interleaved:
+            typ[e] = np.sort(typ[e])
+        p_hit = rs.choice([0.0, 0.1, 0.3])
+        gap[e] = np.where(rs.uniform(size=N) < p_hit, COLLIDER, rs.randint(1, 64, size=N) / 64.0)
+        e += 1
+    for e in range(E):
+        _distinct_gaps(gap[e], int(n_h[e]))
+        for i in range(N):
+            place_standing(b, e, i, gap[e, i])
+    b.n_humans[:], b.type[:] = n_h, typ
+    _clear_unused(b)
+    b.gap = gap
+    return b
+
+
+def ordered_walk_restated(b):
+    """simulator/env.py:303-313 per type over the exact gaps -> (dmin [E, 3], collision [E, 3]) and, for the coverage,
+    what[e][t] = dict(first collider's index, quarter, closer_behind, closer_before_earlier_quarter, second_collider)."""
+    E, N = b.n, b.N
+    c = -(-N // 4)
+    dmin = np.full((E, 3), np.inf)
+    coll = np.zeros((E, 3), bool)
+    what = [[None] * 3 for _ in range(E)]
+    for e in range(E):
+        n = int(b.n_humans[e])
+        for t in range(3):
+            members = [i for i in range(n) if b.type[e, i] == t]
+            best = None
+            for i in members:
+                if b.gap[e, i] < 0:
+                    coll[e, t] = True
+                    behind = [j for j in members if j > i]
+                    what[e][t] = dict(first=i, quarter=i // c,
+                                      closer_behind=any(0 <= b.gap[e, j] < dmin[e, t] for j in behind),
+                                      closer_before_earlier_quarter=best is not None and best // c < i // c,
+                                      second_collider=any(b.gap[e, j] < 0 for j in behind))
+                    break
+                if b.gap[e, i] < dmin[e, t]:
+                    dmin[e, t] = b.gap[e, i]
+                    best = i
+    return dmin, coll, what
+
+
+def ordered_coverage(b):
+    """The order-dependent cases a batch holds, counted from the restatement alone."""
+    dmin, coll, what = ordered_walk_restated(b)
+    cov = {}
+    for t in range(3):
+        for q in range(4):
+            cov["type %d first collider in quarter %d" % (t, q)] = sum(1 for w in what if w[t] and w[t]["quarter"] == q)
+        for k in ("closer_behind", "closer_before_earlier_quarter", "second_collider"):
+            cov["type %d %s" % (t, k)] = sum(1 for w in what if w[t] and w[t][k])
+        cov["type %d without a member" % t] = int(((b.type != t) | (np.arange(b.N)[None] >= b.n_humans[:, None])).all(1).sum())
+    cov["two types collide"] = int((coll.sum(1) == 2).sum())
+    cov["three types collide"] = int((coll.sum(1) == 3).sum())
+    cov["humans but no collider"] = int(((coll.sum(1) == 0) & (b.n_humans > 0)).sum())
+    cov["empty env"] = int((b.n_humans == 0).sum())
+    return cov
+
+
+def check_ordered(make_env, N, interleaved, forms=OUTCOME_FORMS):
+    """dmin of every form bitwise the restatement's and the oracle's; info / done the oracle's; the forms byte-identical."""
+    b = ordered_batch(N, interleaved)
+    params = outcome_params()
+    act = np.zeros((b.n, 2))
+    dmin, coll, _ = ordered_walk_restated(b)
+    ref = oracle_outcome(params, b, act)
+    tag = "N %d %s" % (N, "interleaved" if interleaved else "grouped")
+    np.testing.assert_array_equal(ref["dmin"], dmin, err_msg=tag + ": the oracle against the restatement")
+    res = robot_outcome_forms(make_env, params, b, act, forms=forms)
+    for form, o in res.items():
+        bad = np.argwhere(o["dmin"] != dmin)
+        assert not len(bad), "%s %s: dmin of %d (env, type), the first %s: %r, expected %r (n = %d, types %s, gaps %s)" % (
+            tag, form, len(bad), bad[0].tolist(), o["dmin"][tuple(bad[0])], dmin[tuple(bad[0])], b.n_humans[bad[0][0]],
+            b.type[bad[0][0]].tolist(), b.gap[bad[0][0]].tolist())
+        assert_outcome(o, ref, tag + " " + form)
+    assert_forms_agree(res, tag)
+    return b, res
+
+
+# -- 5. the reward ladder
+
+LADDER = dict(collision_penalty=(-0.25, -0.5, -0.75, -0.125), discomfort_dist=(0.125, 0.25, 0.375),
+              discomfort_factor=(0.5, 1.0, 2.0), success_reward=1.0, max_goal_distance=16.0, time_good=10.0,
+              time_max=20.0)
+LADDER_BORDER = (-4.0, 4.0, -4.0, 4.0)
+
+
+def ladder_params(new_reward, time_limit=25.0, **kw):
+    args = dict(LADDER, new_reward=new_reward, time_limit=time_limit)
+    args.update(kw)
+    return outcome_params(**args)
+
+
+def ladder_batch(wall):
+    """One standing human per type around a standing robot: colliding subset of {adult, bicycle, child, wall} (16) x
+    goal reached or not (2) x which humans stand inside their type's discomfort distance (8), then the exact
+    thresholds.  wall = "grid": the wall is an occupied cell under the robot; "border": the robot stands where
+    px == border[0] + radius under LADDER_BORDER (pass it to the call).  b.meta[e] = (colliding subset, reached, inside)."""
+    dd = LADDER["discomfort_dist"]
+    rows = [(sub, reached, inside) for sub in range(16) for reached in (0, 1) for inside in range(8)]
+    extra = [("goal at the radius", None), ("goal one ulp inside", None)]
+    extra += [("gap == discomfort_dist", t) for t in range(3)] + [("gap 1/64 under discomfort_dist", t) for t in range(3)]
+    extra += [("gap 0", t) for t in range(3)]
+    E = len(rows) + len(extra)
+    assert E % 4
+    G = 90
+    b = _blank_batch(E, 3, 0)
+    b.grid = np.zeros((E, G, 2), np.uint64)
+    b.type[:] = (0, 1, 2)
+    meta = []
+    under_robot = pack_grid(1.0 - (np.arange(G)[:, None] == 45) * (np.arange(G)[None] == 45) * 1.0)
+    for e in range(E):
+        origin, goal_dx, gaps = (0.0, 0.0), 3.0, [0.5, 0.5, 0.5]
+        if e < len(rows):
+            sub, reached, inside = rows[e]
+            for t in range(3):
+                gaps[t] = COLLIDER if sub >> t & 1 else (dd[t] / 2 if inside >> t & 1 else 0.5)
+            if sub >> 3 & 1:
+                if wall == "grid":
+                    b.grid[e] = under_robot
+                else:
+                    origin = (LADDER_BORDER[0] + ROBOT_RADIUS, 0.0)
+            goal_dx = 0.125 if reached else 3.0
+            meta.append((sub, reached, inside))
+        else:
+            name, t = extra[e - len(rows)]
+            if name == "goal at the radius":
+                goal_dx = ROBOT_RADIUS
+            elif name == "goal one ulp inside":
+                goal_dx = float(np.nextafter(ROBOT_RADIUS, 0.0))
+            elif name == "gap == discomfort_dist":
+                gaps[t] = dd[t]
+            elif name == "gap 1/64 under discomfort_dist":
+                gaps[t] = dd[t] - 1.0 / 64
+            else:
+                gaps[t] = 0.0
+            meta.append(name)
+        b.robot[e] = [origin[0], origin[1], 0.0, 0.0, ROBOT_RADIUS, origin[0] + goal_dx, origin[1], 1.0, 0.0]
+        for t in range(3):
+            place_standing(b, e, t, gaps[t], origin)
+    b.meta = meta
+    return b
+
+
+def unicycle_batch():
+    """A standing unicycle robot (v = 0) that turns by a1 = 0, 0.5 or -0.5, with no human or one of each type inside its
+    discomfort distance: 9 envs; run under rotation_penalty_factor 0 and 0.5."""
+    cases = [(a1, t) for a1 in (0.0, 0.5) for t in (None, 0, 1, 2)] + [(-0.5, None)]
+    b = _blank_batch(len(cases), 3, 0)
+    b.type[:] = (0, 1, 2)
+    _robot_rows(b, 0.0, 0.0, ROBOT_RADIUS, theta=np.pi / 2)
+    for e, (a1, t) in enumerate(cases):
+        for k in range(3):
+            place_standing(b, e, k, LADDER["discomfort_dist"][k] / 2 if k == t else 0.5)
+    return b, np.array([[0.0, a1] for a1, _ in cases])
+
+
+TIME_REWARD = dict(time_good=0.5, time_max=1.0)
+TIME_STEPS = 9
+ARRIVALS = (0.0, 0.25, 0.5, 0.75, 1.0, 1.25, None)
+
+
+def time_reward_batch():
+    """ROBOT_LINEAR robots (v_pref 1, radius 0.25, dt 0.25) whose goals lie 0.375 + t ahead: they arrive in the step that
+    starts at t = 0, 0.25, ... 1.25; the last one never does and times out at t == time_limit = 2."""
+    b = _blank_batch(len(ARRIVALS), 1, 0)
+    b.n_humans[:] = 0
+    _robot_rows(b, 0.0, 0.0, ROBOT_RADIUS)
+    for e, t in enumerate(ARRIVALS):
+        b.robot[e, 5:7] = (FAR_GOAL if t is None else 0.375 + t, 0.0)
+    return b, ladder_params(1, time_limit=2.0, **TIME_REWARD)
+
+
+def time_reward_forms(make_env, forms=("step", "orca", "one_launch")):
+    """TIME_STEPS steps of time_reward_batch under ROBOT_LINEAR -> {form: {key: [K, E]}} (the look-ahead takes supplied
+    actions only and has no part in this one)."""
+    b, params = time_reward_batch()
+    res = {}
+    for form in forms:
+        env = make_env(params, b.n, b.N, b.S)
+        env.reset(b)
+        if form == "one_launch":
+            o = env.step_k(TIME_STEPS, OUTCOME_KEYS, human_policy=_abi.HUMAN_ORCA, robot_policy=_abi.ROBOT_LINEAR,
+                           flags=_abi.FLAG_ONE_LAUNCH)
+        else:
+            pol = _abi.HUMAN_LINEAR if form == "step" else _abi.HUMAN_ORCA
+            outs = [env.step(human_policy=pol, robot_policy=_abi.ROBOT_LINEAR) for _ in range(TIME_STEPS)]
+            o = {k: np.stack([s[k] for s in outs]) for k in OUTCOME_KEYS}
+        res[form] = {k: np.array(o[k]) for k in OUTCOME_KEYS}
+        _close(env)
+    return res
+
+
+def check_against_oracle(make_env, params, b, act, border, tag, forms=OUTCOME_FORMS):
+    """Every form at the bars of assert_outcome against the oracle's step, and byte for byte against each other."""
+    ref = oracle_outcome(params, b, act, border)
+    res = robot_outcome_forms(make_env, params, b, act, border, forms)
+    for form, o in res.items():
+        assert_outcome(o, ref, tag + " " + form)
+    assert_forms_agree(res, tag)
+    return ref, res
