@@ -192,3 +192,9 @@ class EbcLstmArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("out_offset", C.c_int32),
                 ("self_cols", C.c_int32), ("reserved", C.c_int32), ("out_stride", C.c_int64), ("self_stride", C.c_int64)] + [
         (k, C.c_void_p) for k in ("x", "n_valid", "out", "self_src")]
+
+
+class EbcCadrlArgs(C.Structure):
+    """include/ebcsim.h: one ebc_cadrl_decide (v [E][A][R] float32, n_valid [E] int64 or NULL, reward [E][A] -> values [E][A], choice [E])."""
+    _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("discount", C.c_double)] + [
+        (k, C.c_void_p) for k in ("v", "n_valid", "reward", "values", "choice")]

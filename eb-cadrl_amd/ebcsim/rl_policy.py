@@ -287,3 +287,96 @@ class LstmRL(Policy):
             return rows.to(self.device)
         rows = torch.Tensor([tuple(state.self_state + other) for other in state.agent_states])
         return self.rotate(rows).to(self.device)
+
+
+class CADRL(Policy):
+    """rl/policy/cadrl.py:34-234: the value network on every (robot, other) row separately, the minimum over the rows,
+    the first action above every earlier one — one look-ahead sweep and one batched forward per decision
+    (ebcsim.cadrl.CadrlValueNet).  The reference's own quirks are kept: configure() never reads with_agent_type (rows 13
+    wide), predict() never reads query_env and always takes the look-ahead, no value above -inf returns None instead of
+    raising, and transform() asserts exactly one other agent, so phase "train" works on one-human scenes only."""
+
+    def __init__(self):
+        Policy.__init__(self)
+        self.name = "CADRL"
+        self.trainable = True
+        self.multiagent_training = None
+        self.epsilon = self.gamma = None
+        self.sampling = self.speed_samples = self.rotation_samples = self.query_env = None
+        self.action_space = self.speeds = self.rotations = None
+        self.action_values = None
+        self.with_om = None
+        self.with_agent_type = False
+        self.cell_num = self.cell_size = self.om_channel_size = None
+        self.self_state_dim, self.agent_state_dim, self.agent_type_state_dim = 6, 7, 0
+        self.joint_state_dim = 13
+        self._net = None
+
+    def configure(self, config):
+        """cadrl.py:66-82"""
+        from .cadrl import CadrlModule
+        self.set_common_parameters(config)
+        self.model = CadrlModule(self.joint_state_dim, [int(x) for x in config.get("cadrl", "mlp_dims").split(", ")])
+        self.multiagent_training = config.getboolean("cadrl", "multiagent_training")
+
+    def set_common_parameters(self, config):
+        self.gamma = config.getfloat("rl", "gamma")
+        self.kinematics = config.get("action_space", "kinematics")
+        self.sampling = config.get("action_space", "sampling")
+        self.speed_samples = config.getint("action_space", "speed_samples")
+        self.rotation_samples = config.getint("action_space", "rotation_samples")
+        self.query_env = config.getboolean("action_space", "query_env")
+        self.cell_num = config.getint("om", "cell_num")
+        self.cell_size = config.getfloat("om", "cell_size")
+        self.om_channel_size = config.getint("om", "om_channel_size")
+
+    set_device = SARL.set_device
+    set_epsilon = SARL.set_epsilon
+    build_action_space = SARL.build_action_space
+    rotate = SARL.rotate
+
+    def _value_net(self):
+        """Inference view of the model's current weights; rebuilt when they were replaced (load_state_dict) or moved."""
+        version = tuple(p._version for p in self.model.parameters())
+        if self._net is None or self._net_version != version:
+            from .cadrl import CadrlValueNet
+            self._net = CadrlValueNet({k: v.detach() for k, v in self.model.state_dict().items()}, device=str(self.device))
+            self._net_version = version
+        return self._net
+
+    def predict(self, state, env=None):
+        """cadrl.py:167-222"""
+        if self.phase is None:
+            raise AttributeError("Phase attribute has to be set!")
+        if self.device is None:
+            raise AttributeError("Device attributes has to be set!")
+        if self.phase == "train" and self.epsilon is None:
+            raise AttributeError("Epsilon attribute has to be set in training phase")
+        if self.reach_destination(state):
+            return ActionXY(0, 0) if self.kinematics == "holonomic" else ActionRot(0, 0)
+        if self.action_space is None:
+            self.build_action_space(state.self_state.v_pref)
+        if env is None or not hasattr(env, "lookahead_all"):
+            raise ValueError("CADRL.predict needs the env it acts in: robot.act(ob, env=env)")
+        probability = np.random.random()
+        if self.phase == "train" and probability < self.epsilon:
+            chosen = self.action_space[np.random.choice(len(self.action_space))]
+        else:
+            sweep = env.lookahead_all(self._action_rows)
+            rows = torch.from_numpy(sweep["rows_rotated"][:, :sweep["n_rows"]]).to(self.device)
+            discount = pow(self.gamma, self.time_step * state.self_state.v_pref)
+            reward = torch.from_numpy(np.ascontiguousarray(sweep["reward"], dtype=np.float64)).to(self.device)
+            net = self._value_net()
+            values = net.action_values(rows[None], reward[None], discount)[0].cpu().numpy()
+            self.action_values = [float(x) for x in values]
+            pick = int(net.last_choice[0])
+            chosen = self.action_space[pick] if pick >= 0 else None  # max_action stays None (cadrl.py:193)
+        if self.phase == "train":
+            self.last_state = self.transform(state)
+        return chosen
+
+    def transform(self, state):
+        """cadrl.py:224-234: the one (robot, other) row of a two-agent state, rotated -> [13] float32."""
+        assert len(state.agent_states) == 1
+        row = torch.Tensor([tuple(state.self_state + state.agent_states[0])])
+        return self.rotate(row).squeeze(dim=0).to(self.device)

@@ -591,6 +591,29 @@ int ebc_lstm_update(void *lstm, void *stream, const float *w_ih, const float *w_
 int ebc_lstm_forward(void *lstm, void *stream, const EbcLstmArgs *args);
 int ebc_lstm_destroy(void *lstm);
 
+/* ---- the decision of the CADRL policy (rl/policy/cadrl.py:194-217): the value network runs on every (robot, other)
+ * row separately, an action is worth reward + discount * the MINIMUM over its rows, and the first action above every
+ * earlier one is taken (csrc/ebc_cadrl_rule.h: the rule, one definition for the kernel and for the host build
+ * tests/native/cadrl_host.cc compares it with byte for byte).
+ *   m[e][a]      = min of v[e][a][0 .. n_valid[e]) as torch.min computes it: a NaN among those rows makes it NaN; rows at
+ *                  or past n_valid[e] are never read; n_valid[e] = 0 gives NaN; values above R count as R, below 0 as 0
+ *   values[e][a] = reward[e][a] + discount * (double)m[e][a], two rounded float64 operations
+ *   choice[e]    = the first a whose value is greater than every earlier non-NaN value (a NaN is never chosen); -1
+ *                  where no value is above -inf
+ * Device pointers; 1 <= A <= 128 and 1 <= R <= 128, else EBC_ERR_UNSUPPORTED (ebc_last_error names the one).  A stream
+ * under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcCadrlArgs {
+  uint32_t struct_size;
+  int32_t E, A, R;
+  double discount;
+  const float *v;          /* device float32 [E][A][R]: the network's output per row, in the sweep's row slots */
+  const int64_t *n_valid;  /* device int64 [E]; NULL = all R rows */
+  const double *reward;    /* device float64 [E][A] */
+  double *values;          /* device float64 [E][A] */
+  int32_t *choice;         /* device int32 [E] */
+} EbcCadrlArgs;
+int ebc_cadrl_decide(void *stream, const EbcCadrlArgs *args);
+
 #ifdef __cplusplus
 }
 #endif

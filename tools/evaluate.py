@@ -11,6 +11,10 @@ reference's metrics at the end.
                                          (lstm_rl: the LSTM-RL value network, either of the reference's two; rows 13
                                           wide whatever [sarl] says.  The reference ships no trained LSTM-RL model and
                                           the repository carries none: --weights is required, what rl/train.py saved)
+    python3 tools/evaluate.py --policy cadrl --weights CADRL_STATE_DICT_FILE
+                                         (cadrl: the CADRL value network, value_network.{0,2,4,6}; the minimum over the
+                                          rows and the choice are one kernel.  Rows 13 wide; neither tree ships a
+                                          trained CADRL model: --weights is required)
 """
 import argparse
 import configparser
@@ -27,19 +31,21 @@ for p in (ROOT, os.path.join(ROOT, "eb-cadrl_amd")):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--weights", default=None, help="a reference state_dict file (default for sarl: tests/golden/weights/sarl_n10_ebcadrl.pth; "
-                    "required for --policy lstm_rl)")
+                    "required for --policy lstm_rl and --policy cadrl)")
     ap.add_argument("--env-config", default=os.path.join(ROOT, "eb-cadrl_amd", "configs", "bench_metric.config"))
     ap.add_argument("--policy-config", default=os.path.join(ROOT, "eb-cadrl_amd", "configs", "policy_agent_type.config"))
     ap.add_argument("--cases", type=int, default=1000)
     ap.add_argument("--first-case", type=int, default=0)
     ap.add_argument("--gamma", type=float, default=0.9)
-    ap.add_argument("--policy", default="sarl", choices=["sarl", "lstm_rl", "orca"])
+    ap.add_argument("--policy", default="sarl", choices=["sarl", "lstm_rl", "cadrl", "orca"])
     ap.add_argument("--safety-space", type=float, default=0.15)
     ap.add_argument("--device-scenes", action="store_true",
                     help="generate the test scenes on the device (ebc_generate_reset) instead of on the host")
     args = ap.parse_args()
     if args.policy == "lstm_rl" and not args.weights:
         ap.error("--policy lstm_rl needs --weights: a state_dict file of one of the reference's LSTM-RL networks")
+    if args.policy == "cadrl" and not args.weights:
+        ap.error("--policy cadrl needs --weights: a state_dict file of the reference's CADRL network")
     import torch
     from ebcsim import _abi, actions as ebc_actions, config as ebc_config, scene as ebc_scene
     from ebcsim.batched import BatchedEnv
@@ -66,13 +72,17 @@ def main():
         v_pref = float(batch.robot[0, 7])
     t1 = time.perf_counter()
     env.use_torch_stream()
-    if args.policy in ("sarl", "lstm_rl"):
+    if args.policy in ("sarl", "lstm_rl", "cadrl"):
+        make_policy = DeviceSarlPolicy
         if args.policy == "lstm_rl":
             from ebcsim.lstm_rl import LstmValueNet
             net = LstmValueNet.load(weights, device="cuda:0")
+        elif args.policy == "cadrl":
+            from ebcsim.cadrl import CadrlValueNet, DeviceCadrlPolicy
+            net, make_policy = CadrlValueNet.load(weights, device="cuda:0"), DeviceCadrlPolicy
         else:
             net = SarlValueNet.load(weights, device="cuda:0")
-        policy = DeviceSarlPolicy(net, ebc_actions.build_action_space(v_pref), args.gamma)
+        policy = make_policy(net, ebc_actions.build_action_space(v_pref), args.gamma)
         decide, hp = (lambda e: policy.decide(e)[0]), _abi.HUMAN_CACHED
     else:
         act = torch.zeros((args.cases, 2), dtype=torch.float64, device="cuda:0")
