@@ -198,3 +198,11 @@ class EbcCadrlArgs(C.Structure):
     """include/ebcsim.h: one ebc_cadrl_decide (v [E][A][R] float32, n_valid [E] int64 or NULL, reward [E][A] -> values [E][A], choice [E])."""
     _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("discount", C.c_double)] + [
         (k, C.c_void_p) for k in ("v", "n_valid", "reward", "values", "choice")]
+
+
+class EbcOmArgs(C.Structure):
+    """include/ebcsim.h: one ebc_occupancy_rows (next_ob [E][R][5] float64, n_valid [E] int64 or NULL, rows [E][A][R][T] or NULL
+    -> om [E][R][W], rows_wide [E][A][R][T + W])."""
+    _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("T", C.c_int32),
+                ("cell_num", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32), ("cell_size", C.c_double)] + [
+        (k, C.c_void_p) for k in ("next_ob", "n_valid", "rows", "om", "rows_wide")]

@@ -74,6 +74,7 @@ SYMBOLS = {
     "ebc_lstm_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_lstm_destroy": (C.c_int, [C.c_void_p]),
     "ebc_cadrl_decide": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ebc_occupancy_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -62,6 +62,15 @@ def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="
     return p
 
 
+def occupancy_from_config(policy_cfg, policy="sarl"):
+    """The occupancy maps a policy config asks for: an ebcsim.occupancy.OccupancySpec for policy "sarl" with [sarl]
+    with_om = true (OM-SARL, multi_human_rl.py:151-227), else None.  EbcParams has no field for them: the maps are built
+    from the look-ahead's next_ob by ebc_occupancy_rows, outside the env handle.  "lstm_rl" with with_om is refused by its
+    policy object, and the reference's CADRL.configure never reads with_om."""
+    from .occupancy import OccupancySpec
+    return OccupancySpec.from_config(policy_cfg) if policy == "sarl" else None
+
+
 _SCALARS = [n for n, t in _abi.EbcParams._fields_ if not hasattr(t, "_length_")]
 _ARRAYS = [n for n, t in _abi.EbcParams._fields_ if hasattr(t, "_length_")]
 

@@ -53,8 +53,6 @@ class SARL(Policy):
         self.cell_size = config.getfloat("om", "cell_size")
         self.om_channel_size = config.getint("om", "om_channel_size")
         self.with_om = config.getboolean("sarl", "with_om")
-        if self.with_om:
-            raise NotImplementedError("occupancy maps (OM-SARL) are outside the accelerated path")
         if not self.query_env:
             raise NotImplementedError("query_env = false ends in the reference's own NotImplementedError "
                                       "(multi_human_rl.py:89-91)")
@@ -66,9 +64,26 @@ class SARL(Policy):
                                 _dims(config, "mlp3_dims"), _dims(config, "attention_dims"),
                                 config.getboolean("sarl", "with_global_state"), self.self_state_dim)
         self.multiagent_training = config.getboolean("sarl", "multiagent_training")
+        if self.with_om:
+            self.name = "OM-SARL"
 
     def input_dim(self):
-        return self.joint_state_dim
+        """multi_human_rl.py:151-154"""
+        return self.joint_state_dim + (self.cell_num ** 2 * self.om_channel_size if self.with_om else 0)
+
+    def om_spec(self):
+        """The [om] section as an OccupancySpec, or None without occupancy maps."""
+        from .occupancy import OccupancySpec
+        return OccupancySpec(self.cell_num, self.cell_size, self.om_channel_size) if self.with_om else None
+
+    def build_occupancy_maps(self, agent_states):
+        """multi_human_rl.py:156-227 on a list of observable states -> [rows, W] float32 (ebcsim.occupancy: the same
+        cells from an algebraic frame).  A one-row state raises the reference's ValueError: np.concatenate of nothing."""
+        from .occupancy import occupancy_maps
+        if len(agent_states) == 1:
+            raise ValueError("need at least one array to concatenate")
+        ob = np.array([[s.px, s.py, s.vx, s.vy] for s in agent_states], dtype=np.float64).reshape(1, -1, 4)
+        return torch.from_numpy(occupancy_maps(ob, None, self.om_spec())[0])
 
     def set_device(self, device):
         self.device = torch.device(device) if not isinstance(device, torch.device) else device
@@ -127,7 +142,18 @@ class SARL(Policy):
         else:
             sweep = env.lookahead_all(self._action_rows)
             rows = torch.from_numpy(sweep["rows_rotated"][:, :sweep["n_rows"]]).to(self.device)
+            if self.with_om:
+                # the maps of the state every action shares (multi_human_rl.py:62-69: built once, from the first action's
+                # next_agent_states), appended to every action's rows
+                from .occupancy import occupancy_maps, widen
+                n = sweep["n_rows"]
+                if n == 1:
+                    raise ValueError("need at least one array to concatenate")
+                om = occupancy_maps(sweep["next_ob"][None, :n], None, self.om_spec())[0]
+                rows = widen(rows, torch.from_numpy(om).to(self.device))
             net = self._value_net()
+            if net.input_dim != rows.shape[-1]:
+                raise ValueError("the value network takes rows %d wide, this policy builds them %d wide" % (net.input_dim, rows.shape[-1]))
             # the attention weights of the network's last forward in the reference = of the last action
             _, w = net.forward(rows[-1:], want_weights=True, exact=True)
             self._weights = w[0].cpu().numpy()
@@ -146,9 +172,13 @@ class SARL(Policy):
         Explorer.update_memory's `target_policy.transform(state)` (rl/utils/explorer.py:162) — from `state`
         itself on the host, float32 like the reference's tensors."""
         if env is not None:
-            return torch.from_numpy(env.observe_rotated()).to(self.device)
-        rows = torch.Tensor([tuple(state.self_state + other) for other in state.agent_states])
-        return self.rotate(rows).to(self.device)
+            rows = torch.from_numpy(env.observe_rotated()).to(self.device)
+        else:
+            rows = torch.Tensor([tuple(state.self_state + other) for other in state.agent_states])
+            rows = self.rotate(rows).to(self.device)
+        if self.with_om:  # multi_human_rl.py:142-146: the maps of the state as it is handed in
+            rows = torch.cat([rows, self.build_occupancy_maps(state.agent_states).to(self.device)], dim=1)
+        return rows
 
     def rotate(self, rows):
         """cadrl.py:236-337 on [n, 15] float32 rows (robot FullState 9 | other ObservableState 5 + type): the

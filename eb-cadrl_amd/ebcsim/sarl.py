@@ -633,6 +633,13 @@ class SarlValueNet(object):
             self.native_forwards = getattr(self, "native_forwards", 0) + 1  # tests assert the HIP path ran
             h1 = nat[0](rows.reshape(B * R, T), True)
             feat = nat[1](h1, False).view(B, R, -1)
+        elif (exact and T > 32 and rows.is_cuda and not torch.is_grad_enabled() and getattr(self, "native_exact", True)
+              and self._native_blocks() is not None):
+            # rows wider than one input tile (occupancy maps appended) on a network the pair kernels do not take (mlp2
+            # with 50 outputs): mlp1, the one stack that sees the wide rows, still runs as the library's float32 form
+            self.native_exact_mlp1_forwards = getattr(self, "native_exact_mlp1_forwards", 0) + 1
+            h1 = self._native_blocks()[0].f32(rows.reshape(B * R, T), True)
+            feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
         else:
             h1 = _mlp(rows.reshape(B * R, T), self.mlp1, True)
             feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
@@ -693,11 +700,14 @@ class SarlValueNet(object):
 class DeviceSarlPolicy(object):
     """Greedy SARL decisions for a whole BatchedEnv (phase "test": no epsilon draw)."""
 
-    def __init__(self, net, actions, gamma, chunk_rows=1 << 21, refine=None):
+    def __init__(self, net, actions, gamma, chunk_rows=1 << 21, refine=None, om=None):
         """refine: None = every candidate within the matrix-core blocks' error bound of the env's best is recomputed in
         float32 before the argmax (SarlValueNet.action_values); an int k = the best k; 0 = the matrix-core values as
-        they are."""
+        they are.  om: an ebcsim.occupancy.OccupancySpec = OM-SARL (multi_human_rl.py:62-69): the sweep leaves next_ob
+        as well, ebc_occupancy_rows appends every env's maps to the rows of all its actions, and the network (whose
+        mlp1 is T + W wide) runs on those; None = no maps."""
         self.refine = None if refine is None else int(refine)
+        self.om = om
         self.net = net
         self.actions_np = np.ascontiguousarray(actions, dtype=np.float64)
         self.gamma = float(gamma)
@@ -724,16 +734,26 @@ class DeviceSarlPolicy(object):
         if self._bufs is None or getattr(self, "_env_key", None) != key:  # buffers are sized for ONE env batch
             self._env_key = key
             self._acts = torch.tensor(self.actions_np, dtype=torch.float64, device=dev)
-            self._bufs = env.alloc_lookahead_outputs(A, ("reward", "rows_rotated"))
+            self._bufs = env.alloc_lookahead_outputs(A, ("reward", "rows_rotated") + (("next_ob",) if self.om is not None else ()))
             self._n_valid = torch.full((env.E,), env.R, dtype=torch.int64, device=dev)
             self._v_pref = uniform_v_pref(env)
+            if self.om is not None:
+                wide = env.T + self.om.width
+                if getattr(self.net, "input_dim", wide) != wide:
+                    raise ValueError("the value network takes rows %d wide, occupancy maps make them %d + %d" % (
+                        self.net.input_dim, env.T, self.om.width))
+                self._wide = torch.empty((env.E, A, env.R, wide), dtype=torch.float32, device=dev)
         self.n_valid = None
         if getattr(env, "ragged", False):
             env.row_counts_device(self._n_valid)
             self.n_valid = self._n_valid
         env.lookahead_device(self._acts, self._bufs, human_policy=human_policy)
-        values = self.values_from(self._bufs["rows_rotated"], self._bufs["reward"], self.n_valid,
-                                  env.params.time_step, self._v_pref)
+        rows = self._bufs["rows_rotated"]
+        if self.om is not None:
+            from .occupancy import occupancy_rows_device
+            rows = occupancy_rows_device(self._bufs["next_ob"], self.n_valid, self.om, rows=rows, wide_out=self._wide,
+                                         want_om=False)[1]
+        values = self.values_from(rows, self._bufs["reward"], self.n_valid, env.params.time_step, self._v_pref)
         return self._acts[self.choose(values)], values
 
     def choose(self, values):

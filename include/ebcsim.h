@@ -614,6 +614,38 @@ typedef struct EbcCadrlArgs {
 } EbcCadrlArgs;
 int ebc_cadrl_decide(void *stream, const EbcCadrlArgs *args);
 
+/* ---- the occupancy maps of OM-SARL (rl/policy/multi_human_rl.py:156-227 build_occupancy_maps; :62-69 appends them to
+ * the rotated rows of every candidate action; :151-154 input_dim = T + cell_num^2 * om_channel_size).  The arithmetic is
+ * csrc/ebc_om_rule.h, one definition for the kernel and for the host build tests/native/om_host.cc compares it with
+ * byte for byte; it states the reference's arctan2 / cos / sin frame algebraically.
+ *   For every row a < n_valid[e] of next_ob[e] (px, py, vx, vy, radius: the look-ahead's next_ob as it stands) and
+ *   every OTHER row o < n_valid[e] (by index: two rows at the same place still see each other, :177): o's position in
+ *   the frame whose x axis is a's velocity, binned by floor(coord / cell_size + cell_num / 2) per axis (:192-198),
+ *   dropped outside [0, cell_num).  W = cell_num^2 * channels floats per row: channels 1 = occupied 0 / 1 (:199-201),
+ *   2 = the mean velocity of the cell's occupants in a's frame, 3 = (1, mean vx, mean vy) (:203-225); empty cells are 0;
+ *   float64 sums in row order, one cast to float32 (:227).
+ *   om[e][r][W]            the maps; rows at or past n_valid[e] are never read (a NaN there reaches nothing) and get 0
+ *   rows_wide[e][a][r][T + W] = rows[e][a][r][0 .. T) | om[e][r]: the maps are built once per env, from the state
+ *                          every action shares (:63-66), and appended to every action's rows
+ * Device pointers.  Either output may be NULL, not both; rows_wide needs rows.  No atomics: a result does not depend
+ * on the launch shape.  EBC_ERR_UNSUPPORTED (ebc_last_error names the one) for channels outside {1, 2, 3}, cell_num < 1,
+ * cell_size not a finite positive number, W > 192, R > 128 and, with rows_wide, A > 128 or T + W > 224 (the input limit
+ * of the two-layer blocks); a stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcOmArgs {
+  uint32_t struct_size;
+  int32_t E, A, R, T;
+  int32_t cell_num;        /* [om] cell_num */
+  int32_t channels;        /* [om] om_channel_size */
+  int32_t reserved;
+  double cell_size;        /* [om] cell_size */
+  const double *next_ob;   /* device float64 [E][R][5] */
+  const int64_t *n_valid;  /* device int64 [E]; NULL = all R rows; above R counts as R, below 0 as 0 */
+  const float *rows;       /* device float32 [E][A][R][T], or NULL */
+  float *om;               /* device float32 [E][R][W], or NULL */
+  float *rows_wide;        /* device float32 [E][A][R][T + W], or NULL */
+} EbcOmArgs;
+int ebc_occupancy_rows(int device_id, void *stream, const EbcOmArgs *args);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,6 +7,10 @@ reference's metrics at the end.
     python3 tools/evaluate.py --weights tests/golden/weights/sarl_n10_ebcadrl.pth \
         --env-config eb-cadrl_amd/configs/bench_metric.config --policy-config eb-cadrl_amd/configs/policy_agent_type.config \
         --cases 1000 [--policy orca]     (orca: the imitation-learning demonstrator instead of the network)
+    python3 tools/evaluate.py --policy-config OM_POLICY_CONFIG --weights OM_SARL_STATE_DICT_FILE
+                                         (sarl with [sarl] with_om = true in the policy config: OM-SARL, the occupancy maps
+                                          of its [om] section appended to every row on the device; no tree ships OM
+                                          weights: --weights is required, what rl/train.py saved)
     python3 tools/evaluate.py --policy lstm_rl --weights LSTM_RL_STATE_DICT_FILE
                                          (lstm_rl: the LSTM-RL value network, either of the reference's two; rows 13
                                           wide whatever [sarl] says.  The reference ships no trained LSTM-RL model and
@@ -46,6 +50,11 @@ def main():
         ap.error("--policy lstm_rl needs --weights: a state_dict file of one of the reference's LSTM-RL networks")
     if args.policy == "cadrl" and not args.weights:
         ap.error("--policy cadrl needs --weights: a state_dict file of the reference's CADRL network")
+    pol_cfg = configparser.RawConfigParser()
+    pol_cfg.read(args.policy_config)
+    with_om = args.policy == "sarl" and pol_cfg.getboolean("sarl", "with_om", fallback=False)
+    if with_om and not args.weights:
+        ap.error("--policy sarl with [sarl] with_om = true needs --weights: a state_dict file of an OM-SARL network (no tree ships one)")
     import torch
     from ebcsim import _abi, actions as ebc_actions, config as ebc_config, scene as ebc_scene
     from ebcsim.batched import BatchedEnv
@@ -82,7 +91,10 @@ def main():
             net, make_policy = CadrlValueNet.load(weights, device="cuda:0"), DeviceCadrlPolicy
         else:
             net = SarlValueNet.load(weights, device="cuda:0")
-        policy = make_policy(net, ebc_actions.build_action_space(v_pref), args.gamma)
+        kw = {}
+        if with_om:
+            kw["om"] = ebc_config.occupancy_from_config(pol, policy=args.policy)
+        policy = make_policy(net, ebc_actions.build_action_space(v_pref), args.gamma, **kw)
         decide, hp = (lambda e: policy.decide(e)[0]), _abi.HUMAN_CACHED
     else:
         act = torch.zeros((args.cases, 2), dtype=torch.float64, device="cuda:0")
