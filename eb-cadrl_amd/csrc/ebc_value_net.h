@@ -179,8 +179,10 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
   // inside the loop (four 16-byte loads per lane and hidden tile) their waits also waited for the weight staging
   // issued behind them (one in-order counter), and the loop ran at 0.42 instead of ~0.25 ms per 0.5 M rows.
   const int m0w = (blockIdx.x * NW + wave) * 32;
-  const bool g_lds = GROUP && (ex.H & 3) == 0 && ex.group_rows > 0 && (31 / ex.group_rows + 2) <= EBC_VN_GROUPS;
   const int Hp = (ex.H + 3) & ~3;  // floats per parked row
+  // (a hidden layer of more than 224 units does not fit a parked row: its lanes load their own terms)
+  const bool g_lds = GROUP && (ex.H & 3) == 0 && ex.group_rows > 0 && (31 / ex.group_rows + 2) <= EBC_VN_GROUPS &&
+                     Hp * 4 + 16 <= EBC_VN_GROUP_PITCH;
   const LdsF4 gt = (LdsF4)(reinterpret_cast<unsigned char *>(wbuf) + 2 * (size_t)PER_U * 16 + (size_t)hidden_tiles * 32 * 4 +
                            (size_t)wave * EBC_VN_GROUPS * EBC_VN_GROUP_PITCH);
   if (g_lds) {

@@ -84,6 +84,9 @@ class _NativeMlp2(object):
                      final[1].detach().to("cpu", torch.float32).reshape(-1).contiguous().numpy()]
         self._h = C.c_void_p()
         self.in_fragments = bool(in_fragments)
+        # what ebc_mlp2_forward_reduce / _ex ask of a block whose rows leave through the tile epilogue (partial sums,
+        # fragments): O a multiple of 4 and more than 1 + 1 tiles (the smallest block has no LDS tile per wave to park one)
+        self.tile_epilogue = self.O % 4 == 0 and (self.K0 + 31) // 32 + (self.O + 31) // 32 >= 3
         _capi.check(self._L.ebc_mlp2_create_ex(int(device_index), self.K0, self.H, self.O, host[0].ctypes.data,
                                                host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data,
                                                host[4].ctypes.data if final is not None else None,
@@ -228,15 +231,17 @@ class SarlValueNet(object):
         # and layer 1 form the block, g's half enters as a per-pair term, layer 2 is the block's tail
         att = [(self.attention[0][0][:, :H], torch.zeros_like(self.attention[0][1])), self.attention[1]]
         stacks = (self.mlp1, self.mlp2, att)
-        if not (self.attention[2][0].shape[0] == 1 and all(
-                st[0][0].shape[1] <= 224 and st[1][0].shape[0] <= 224 for st in stacks)):
+
+        def fits(st):  # what ebc_mlp2_create_ex takes: inputs and outputs of up to 7 tiles, a hidden layer of up to 10
+            return st[0][0].shape[1] <= 224 and st[0][0].shape[0] <= 320 and st[1][0].shape[0] <= 224
+        if not (self.attention[2][0].shape[0] == 1 and all(fits(st) for st in stacks)):
             return None
         specs = [(self.mlp1, None), (self.mlp2, None), (att, self.attention[2])]
         # mlp3's first two layers (the joint vector's widest ones) as a fourth block; its tail
         # (the reference's 200 -> 200 -> 1) stays with torch unless it is a two-layer block too
-        if len(self.mlp3) >= 3 and self.mlp3[0][0].shape[1] <= 224 and self.mlp3[1][0].shape[0] <= 224:
+        if len(self.mlp3) >= 3 and fits(self.mlp3[:2]):
             specs.append((self.mlp3[:2], None))
-            if len(self.mlp3) == 4 and self.mlp3[2][0].shape[1] <= 224 and self.mlp3[3][0].shape[0] <= 224:
+            if len(self.mlp3) == 4 and fits(self.mlp3[2:4]):
                 specs.append((self.mlp3[2:4], None))
         # the mean state's half of attention layer 0 (one 200 x 200 layer per PAIR) as a block too: the mean of
         # ReLU outputs is >= 0, so relu(I g) = g and [I | w0[:, H:]] is that layer in the two-layer form
@@ -573,7 +578,7 @@ class SarlValueNet(object):
         # mlp2 multiplies its rows by the attention weights and leaves only their pair sums — the [B * R][F]
         # features are never written, nothing reads h1 a second time for the mean.
         folded = (nat is not None and self.with_global_state and 16 <= R <= 32 and not want_weights
-                  and getattr(self, "fold_pairs", True) and nat[0].O % 4 == 0 and nat[1].O % 4 == 0)
+                  and getattr(self, "fold_pairs", True) and nat[0].tile_epilogue and nat[1].tile_epilogue)
         if folded:
             self.native_forwards = getattr(self, "native_forwards", 0) + 1
             self.folded_forwards = getattr(self, "folded_forwards", 0) + 1
