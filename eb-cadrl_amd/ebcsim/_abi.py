@@ -206,3 +206,19 @@ class EbcOmArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("A", C.c_int32), ("R", C.c_int32), ("T", C.c_int32),
                 ("cell_num", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32), ("cell_size", C.c_double)] + [
         (k, C.c_void_p) for k in ("next_ob", "n_valid", "rows", "om", "rows_wide")]
+
+
+SAIL_LAYERS = 14
+
+
+class EbcSailWeights(C.Structure):
+    """include/ebcsim.h: the 14 Linear layers of the SAIL network, host pointers in torch's layout [out][in]."""
+    _fields_ = [("struct_size", C.c_uint32), ("adult_num", C.c_int32), ("weight", C.c_void_p * SAIL_LAYERS),
+                ("bias", C.c_void_p * SAIL_LAYERS)]
+
+
+class EbcSailArgs(C.Structure):
+    """include/ebcsim.h: one ebc_sail_forward (robot [E][9] float64, ob [E][R][5] float64, n_rows [E] int64 or NULL
+    -> action [E][2] float64, feat_joint [E][64] float32 or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("R", C.c_int32), ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("robot", "ob", "n_rows", "action", "feat_joint")]

@@ -75,6 +75,9 @@ SYMBOLS = {
     "ebc_lstm_destroy": (C.c_int, [C.c_void_p]),
     "ebc_cadrl_decide": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ebc_occupancy_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "ebc_sail_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ebc_sail_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_sail_destroy": (C.c_int, [C.c_void_p]),
 }
 
 

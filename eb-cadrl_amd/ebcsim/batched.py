@@ -278,6 +278,24 @@ class BatchedEnv:
         """Rotated observation of the current state into a torch CUDA tensor [E, R, T]."""
         _capi.check(self._L.ebc_observe(self._h, _abi.DEVICE, None, obs_rotated.data_ptr()))
 
+    def observe_ob_device(self, ob):
+        """The world-frame observation rows of the current state (ebc_observe's `ob`) into a torch CUDA tensor
+        float64 [E, R, 5] (enqueued on the handle's stream); rows past an env's own are zeros."""
+        if ob.dtype.itemsize != 8 or ob.numel() != self.E * self.R * 5 or not ob.is_contiguous():
+            raise ValueError("ob must be a contiguous float64 [E, R, 5] tensor")
+        _capi.check(self._L.ebc_observe(self._h, _abi.DEVICE, ob.data_ptr(), None))
+
+    def robot_state_device(self, robot):
+        """The robot's FullState of every env (ebc_get_state's `robot`) into a torch CUDA tensor float64 [E, 9]
+        (enqueued on the handle's stream)."""
+        if robot.dtype.itemsize != 8 or robot.numel() != self.E * 9 or not robot.is_contiguous():
+            raise ValueError("robot must be a contiguous float64 [E, 9] tensor")
+        v = _abi.EbcStateView()
+        v.struct_size = C.sizeof(v)
+        v.location = _abi.DEVICE
+        v.robot = robot.data_ptr()
+        _capi.check(self._L.ebc_get_state(self._h, C.addressof(v)))
+
     def row_counts(self):
         """Observation rows that exist per env, int64 [E] (ebc_row_counts), from the device state."""
         n = np.zeros(self.E, dtype=np.int64)

@@ -23,8 +23,8 @@ def _opt(cfg, section, key, default=_NAN):
 
 def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="sarl"):
     """env_cfg / policy_cfg: RawConfigParser objects in the reference's schema.  policy: the robot's policy;
-    "lstm_rl" and "cadrl" never read with_agent_type (rl/policy/lstm_rl.py:79-100, rl/policy/cadrl.py:66-82), so their
-    rows are 13 wide whatever [sarl] says."""
+    "lstm_rl", "cadrl" and "sail" never read with_agent_type (rl/policy/lstm_rl.py:79-100, rl/policy/cadrl.py:66-82,
+    rl/policy/sail.py:109-112), so their rows are 13 wide whatever [sarl] says."""
     p = _abi.default_params()
     p.time_step = env_cfg.getfloat("env", "time_step")
     p.time_limit = env_cfg.getint("env", "time_limit")
@@ -52,7 +52,7 @@ def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="
             kin = policy_cfg.get("action_space", "kinematics")
         if policy_cfg.has_option("sarl", "with_agent_type"):
             p.with_agent_type = int(policy_cfg.getboolean("sarl", "with_agent_type"))
-        if policy in ("lstm_rl", "cadrl"):
+        if policy in ("lstm_rl", "cadrl", "sail"):
             p.with_agent_type = 0
     kin = kin or "holonomic"
     # agents treat every non-"holonomic" string as rotational (agent.py:166-169);

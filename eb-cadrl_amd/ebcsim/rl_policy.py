@@ -410,3 +410,80 @@ class CADRL(Policy):
         assert len(state.agent_states) == 1
         row = torch.Tensor([tuple(state.self_state + state.agent_states[0])])
         return self.rotate(row).squeeze(dim=0).to(self.device)
+
+
+class SAIL(Policy):
+    """rl/policy/sail.py:104-156: no look-ahead and no action space; one network (ebcsim.sail.SailModule, the
+    reference's ExtendedNetwork) maps the robot's state and the world-frame states of exactly `adult_num` others straight
+    to the action — one forward per decision (ebcsim.sail.SailNet: one kernel on a HIP device, torch on the CPU)."""
+
+    def __init__(self):
+        Policy.__init__(self)
+        self.name = "SAIL"
+        self.trainable = True
+        self.multiagent_training = None
+        self.epsilon = self.gamma = None
+        self.sampling = self.speed_samples = self.rotation_samples = self.query_env = None
+        self.action_space = self.speeds = self.rotations = None
+        self.action_values = None
+        self.with_om = None
+        self.with_agent_type = False
+        self.cell_num = self.cell_size = self.om_channel_size = None
+        self.self_state_dim, self.agent_state_dim, self.agent_type_state_dim = 6, 7, 0
+        self.joint_state_dim = 13
+        self.adult_num = None
+        self._net = None
+
+    def configure(self, config):
+        """sail.py:109-112"""
+        from .sail import SailModule, check_adult_num
+        self.set_common_parameters(config)
+        self.multiagent_training = config.getboolean("sail", "multiagent_training")
+        self.adult_num = config.getint("sail", "adult_num")
+        check_adult_num(self.adult_num)
+        self.model = SailModule(self.adult_num)
+
+    set_common_parameters = CADRL.set_common_parameters
+    set_device = SARL.set_device
+    set_epsilon = SARL.set_epsilon
+    build_action_space = SARL.build_action_space
+
+    def _value_net(self):
+        """Inference view of the model's current weights; rebuilt when they were replaced (load_state_dict) or moved."""
+        version = tuple(p._version for p in self.model.parameters())
+        if self._net is None or self._net_version != version:
+            from .sail import SailNet
+            self._net = SailNet({k: v.detach() for k, v in self.model.state_dict().items()}, device=str(self.device))
+            self._net_version = version
+        return self._net
+
+    def predict(self, state, env=None):
+        """sail.py:114-132"""
+        if self.phase is None:
+            raise AttributeError("Phase attribute has to be set!")
+        if self.device is None:
+            raise AttributeError("Device attributes has to be set!")
+        if self.phase == "train" and self.epsilon is None:
+            raise AttributeError("Epsilon attribute has to be set in training phase")
+        make = ActionXY if self.kinematics == "holonomic" else ActionRot
+        if self.reach_destination(state):
+            return make(0, 0)
+        self.last_state = self.transform(state)
+        net = self._value_net()
+        if len(state.agent_states) != net.adult_num:
+            raise ValueError("SAIL.predict: %d agents, the network takes exactly adult_num = %d (the reference raises "
+                             "there too)" % (len(state.agent_states), net.adult_num))
+        s = state.self_state
+        robot = torch.tensor([[s.px, s.py, s.vx, s.vy, s.radius, s.gx, s.gy, s.v_pref, s.theta]], dtype=torch.float64)
+        ob = torch.tensor([[[a.px, a.py, a.vx, a.vy, a.radius] for a in state.agent_states]], dtype=torch.float64)
+        action, self.feat_joint = net.forward(robot.to(self.device), ob.to(self.device))
+        return make(float(action[0, 0]), float(action[0, 1]))
+
+    def transform(self, state):
+        """sail.py:134-156: [robot (px, py, vx, vy, gx, gy) [6], agents (px, py, vx, vy) [N, 4]], float32"""
+        s = state.self_state
+        robot = torch.Tensor([s.px, s.py, s.vx, s.vy, s.gx, s.gy])
+        agents = torch.empty([len(state.agent_states), 4])
+        for k, a in enumerate(state.agent_states):
+            agents[k, 0], agents[k, 1], agents[k, 2], agents[k, 3] = a.px, a.py, a.vx, a.vy
+        return [robot, agents]

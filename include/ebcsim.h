@@ -646,6 +646,52 @@ typedef struct EbcOmArgs {
 } EbcOmArgs;
 int ebc_occupancy_rows(int device_id, void *stream, const EbcOmArgs *args);
 
+/* ---- the SAIL policy (rl/policy/sail.py): one small network from the robot's state and the world-frame states of
+ * exactly adult_num others straight to a continuous action, no look-ahead and no action space; one kernel per batch of
+ * decisions.  The arithmetic is csrc/ebc_sail_rule.h (one definition for the kernel and for the host build
+ * tests/native/sail_host.cc compares it with byte for byte): float32, every Linear a serial fmaf chain in ascending k
+ * from the bias, ReLU and the softmax's maximum by selection, exp without libm, sums ascending.
+ *
+ * EbcSailWeights: the 14 Linear layers of ExtendedNetwork (sail.py:15-60) in this order —
+ *   0 robot_encoder.0 [32][4]    1 robot_encoder.2 [32][32]   2 adult_encoder.0 [64][4 adult_num]   3 adult_encoder.2 [64][64]
+ *   4 adult_head.0 [32][64]      5 joint_embedding.0 [64][64] 6 pairwise.0 [64][64]    7 pairwise.2 [64][64]
+ *   8 attention.0 [64][64]       9 attention.2 [1][64]        10 task_encoder.0 [64][4] 11 task_encoder.2 [64][64]
+ *   12 joint_encoder.0 [64][128] 13 planner [2][64]
+ * — HOST pointers, torch's layout [out][in], widths the reference's fixed ones (local 32, embedding 64, hidden 64:
+ * SAIL.configure, sail.py:109-112, builds nothing else).  2 <= adult_num <= 32, else EBC_ERR_UNSUPPORTED and
+ * ebc_last_error names what was refused (at adult_num = 1 the reference's own reshape of an empty selection raises,
+ * rl/utils/transform.py:16-18).  ebc_sail_create (sail.py:109-112, the model) re-packs them for the kernel. */
+#define EBC_SAIL_LAYERS 14
+typedef struct EbcSailWeights {
+  uint32_t struct_size;
+  int32_t adult_num;                      /* [sail] adult_num */
+  const float *weight[EBC_SAIL_LAYERS];   /* host float32 [out][in] */
+  const float *bias[EBC_SAIL_LAYERS];     /* host float32 [out] */
+} EbcSailWeights;
+/* One ebc_sail_forward: SAIL.predict for E envs (sail.py:114-132 with transform :134-156, ExtendedNetwork.forward
+ * :62-101, transform_frame rl/utils/transform.py:11-20, reach_destination simulator/policy/policy.py:44-52).
+ *   rows at or past adult_num of an env are never read (a NaN there reaches nothing)
+ *   n_rows[e] != adult_num: action NaN, feat_joint zeros (the reference raises there)
+ *   an arrived env (float64 sqrt(dy*dy + dx*dx) < radius): action (0, 0); its feat_joint is still the network's
+ * An env's result depends on nothing but its own inputs.  Device pointers.  A stream under capture is refused with
+ * EBC_ERR_UNSUPPORTED. */
+typedef struct EbcSailArgs {
+  uint32_t struct_size;
+  int32_t E;
+  int32_t R;               /* row stride of ob, R >= adult_num */
+  int32_t reserved;
+  const double *robot;     /* device float64 [E][9] FullState order */
+  const double *ob;        /* device float64 [E][R][5] */
+  const int64_t *n_rows;   /* device int64 [E]; NULL = every env has adult_num rows */
+  double *action;          /* device float64 [E][2] */
+  float *feat_joint;       /* device float32 [E][64], or NULL */
+} EbcSailArgs;
+int ebc_sail_create(const EbcSailWeights *weights, int device_id, void **sail_out);
+/* SAIL.predict for a batch (sail.py:114-132): one launch on `stream` */
+int ebc_sail_forward(void *sail, void *stream, const EbcSailArgs *args);
+/* frees what ebc_sail_create (sail.py:109-112) made */
+int ebc_sail_destroy(void *sail);
+
 #ifdef __cplusplus
 }
 #endif
