@@ -8,6 +8,9 @@
 //
 //   P1   (pre-step state)
 //        all threads   state_rotated[k] rows -> LDS row buffer (they leave as 16-byte stores after the barrier)
+//        all waves     EBC_ROBOT_SAIL only (rollout_kernel<GS, true>): the attached network decides for the envs of the
+//                      workgroup, a chunk of envs at a time through one LDS area (sail_group, ebc_sail.h), from the
+//                      LDS state; the action goes to act[] and a barrier ends it
 //        last wave     the robot side of the step, which needs nothing from the humans' ORCA: n_rows[k]; the robot's
 //                      action (EBC_ROBOT_LINEAR / _EXTERNAL: a lane per env; EBC_ROBOT_ORCA: a 32-lane ORCA group per
 //                      env over the N + S observation rows, with the persistent simulator when it is enabled); swept
@@ -34,7 +37,10 @@
 // at +inf and are masked out of every ballot, so the width cannot change a result.
 #pragma once
 
+#include <type_traits>
+
 #include "ebc_kernels.h"
+#include "ebc_sail.h"
 
 namespace ebc {
 
@@ -147,8 +153,46 @@ __device__ __forceinline__ void rollout_put_row(float *dst, const float (&out)[E
     if (c < T) dst[c] = out[c];
 }
 
-template <int GS>
-__global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutIO io) {
+// EBC_ROBOT_SAIL: the attached network (ebc_robot_sail) and how many envs go through its LDS area at a time
+struct RolloutSail {
+  const float *P;  // the packed weight image (ebc_sail_rule.h), device
+  int N;           // adult_num
+  int chunk;       // envs per pass of the network: min(epg, group_envs(N)), fewer when LDS is short
+};
+
+// Inputs of sail_group (ebc_sail.h) from the rollout kernel's LDS state: the rows ebc_observe's `ob` would hold
+// (observe_kernel: the humans, then the static obstacles with zero velocity, then zeros), cast once.
+struct RolloutSailSrc {
+  const double *robot_base, *h_px, *h_py, *h_vx, *h_vy, *st_x, *st_y;
+  const int *n_h, *n_s;
+  int N, S, el0;
+  __device__ __forceinline__ const double *robot(int g) const { return robot_base + (el0 + g) * 9; }
+  __device__ __forceinline__ float frame(int g, int i, int c) const {
+    const int el = el0 + g, n = n_h[el], ns = n_s[el];
+    double v = 0.0;
+    if (i < n) {
+      const int h = el * N + i;
+      v = c == 0 ? h_px[h] : c == 1 ? h_py[h] : c == 2 ? h_vx[h] : h_vy[h];
+    } else if (i - n < ns) {
+      const int q = el * S + (i - n);
+      v = c == 0 ? st_x[q] : c == 1 ? st_y[q] : 0.0;
+    }
+    return (float)v;
+  }
+};
+
+// The kernel's third argument: RolloutIO, and with EBC_ROBOT_SAIL the network behind it
+struct RolloutIOSail : RolloutIO {
+  RolloutSail sail;
+};
+template <bool SAIL>
+using RolloutArg = typename std::conditional<SAIL, RolloutIOSail, RolloutIO>::type;
+
+// SAIL = false is the kernel of the three robot policies as it was measured; SAIL = true (EBC_ROBOT_SAIL) is an
+// instantiation of its own, so that theirs keeps its register allocation: it adds the network's decision in P1 and
+// nothing anywhere else.
+template <int GS, bool SAIL = false>
+__global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutArg<SAIL> io) {
   extern __shared__ __align__(16) unsigned char ro_lds[];
   const int tid = threadIdx.x, lane = tid & (EBC_WAVE - 1), wave = tid / EBC_WAVE;
   const int N = s.N, S = s.S, R = N + S, EPG = io.epg, T = io.T, E = s.E;
@@ -248,6 +292,24 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
         rollout_put_row(rows_state + (size_t)q * T, out, T);
       }
     }
+    if constexpr (SAIL) {
+      // The network's decision from the LDS state, on all four waves, a chunk of envs at a time; the action goes to
+      // act[] as the per-step form's sail_kernel would have written it.  The last wave reads act[] behind the barrier.
+      const SailLds SL = sail_lds(reinterpret_cast<float *>(ro_lds + L.bytes), io.sail.chunk, io.sail.N);
+      for (int c0 = 0; c0 < envs; c0 += io.sail.chunk) {
+        const int ne = min(io.sail.chunk, envs - c0);
+        const RolloutSailSrc src = {robot, h_px, h_py, h_vx, h_vy, st_x, st_y, n_h, n_s, N, S, c0};
+        sail_group<EBC_RO_WAVES>(io.sail.P, io.sail.N, SL, ne, src);
+        const float *planned = SL.planned();
+        for (int q = tid; q < ne * 2; q += EBC_RO_THREADS) {
+          const int g = q >> 1, c = q & 1, el = c0 + g;
+          const bool rows_ok = n_h[el] + n_s[el] == io.sail.N;
+          act[2 * el + c] = ebc_sail::action_of(planned[g * EBC_SAIL_HIDDEN + c], ebc_sail::arrived(robot + el * 9), rows_ok);
+        }
+        // the next chunk's first store to `planned` lies behind two barriers of sail_group
+      }
+      __syncthreads();
+    }
     if (wave == EBC_RO_WAVES - 1) {
       if (lane < envs && io.n_rows) io.n_rows[ke + lane] = (long long)n_h[lane] + n_s[lane];
       if (robot_orca) {
@@ -310,7 +372,7 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
             act[2 * el + 1] = (double)oy;
           }
         }
-      } else if (lane < envs) {  // robot_action(): env.py:388-392
+      } else if (!SAIL && lane < envs) {  // robot_action(): env.py:388-392
         const double *rb = robot + lane * 9;
         double a0, a1;
         if (io.robot_policy == EBC_ROBOT_LINEAR) {

@@ -15,6 +15,7 @@
 #include "ebc_kernels.h"
 #include "ebc_local_map_kernel.h"
 #include "ebc_rollout.h"
+#include "ebc_sail_api.h"
 
 namespace {
 
@@ -35,6 +36,12 @@ struct Handle {
   hipStream_t stream = nullptr;
   bool has_reset = false;
   double *act_scratch = nullptr;  // ebc_step_k: the ORCA robot's action when the caller keeps none
+  // ebc_robot_sail: the attached network's packed weights (owned by the ebc_sail_create handle) and adult_num; the
+  // per-step form's gathers of robot [E][9], ob [E][R][5] and the row counts [E], allocated on first use
+  const float *sail_P = nullptr;
+  int sail_N = 0;
+  double *sail_robot = nullptr, *sail_ob = nullptr;
+  long long *sail_rows = nullptr;
   int cus = 0;  // compute units of the device (EBC_FLAG_ONE_LAUNCH sizes its workgroups by them), read on first use
   int *robot_sim_rows = nullptr;
   ebc::RobotSim robot_sim = {nullptr, nullptr, nullptr};  // ebc_robot_orca_sim: the demonstrator's persistent rvo2 simulators
@@ -919,10 +926,14 @@ int launch_observe(Handle *h, double *d_ob, float *d_obs) {
 }
 
 // EBC_FLAG_ONE_LAUNCH: rollout_kernel (ebc_rollout.h), a workgroup per group of envs for all K steps.
+// EBC_ROBOT_SAIL: the network's LDS area for `chunk` envs, in bytes
+unsigned sail_area(const Handle *h, int chunk) { return (unsigned)(ebc::sail_lds_floats(chunk, h->sail_N) * sizeof(float)); }
+
 template <int GS>
 int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
   const int N = h->s.N, S = h->s.S, E = h->s.E;
   constexpr unsigned scratch = ebc::RolloutScratch<GS>::BYTES;
+  const bool sail = io.robot_policy == EBC_ROBOT_SAIL;
   // envs per workgroup.  Two lower bounds, the larger decides: (1) what gives every wave one pass of ORCA groups per
   // step (the robot's groups take a wave of their own): 2 at 10 humans in 9-lane groups; (2) enough that all workgroups
   // of the launch are resident at once, EBC_RO_OCC per CU — a workgroup stays for K steps, so a second round of
@@ -940,6 +951,30 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
   if (force && atoi(force) > 0) epg = atoi(force);
   epg = epg < 1 ? 1 : (epg > EBC_RO_MAX_EPG ? EBC_RO_MAX_EPG : epg);
   epg = epg > E ? E : epg;
+  if (sail) {
+    // The network's LDS area lies behind the rollout arrays.  One env of each has to fit; then as many envs per
+    // workgroup as fit beside a one-env area, then as many envs per pass of the network as fit beside those (at most
+    // group_envs, the rows that spread over sail_kernel's waves, and never more than the workgroup has).
+    auto bytes = [&](int g, int chunk) { return ebc::rollout_lds(g, N, S, h->T, scratch).bytes + sail_area(h, chunk); };
+    if (bytes(1, 1) > 48u * 1024u)
+      return fail(EBC_ERR_UNSUPPORTED, "EBC_FLAG_ONE_LAUNCH with EBC_ROBOT_SAIL: one env's rollout arrays (" +
+                                           std::to_string(ebc::rollout_lds(1, N, S, h->T, scratch).bytes) +
+                                           " bytes) and the network's LDS area for adult_num " + std::to_string(h->sail_N) + " (" +
+                                           std::to_string(sail_area(h, 1)) +
+                                           " bytes) exceed the kernel's 48 KB of LDS; the per-step form takes this call");
+    while (epg > 1 && bytes(epg, 1) > 48u * 1024u) --epg;
+    int chunk = ebc_sail::group_envs(h->sail_N);
+    chunk = chunk > epg ? epg : chunk;
+    while (chunk > 1 && bytes(epg, chunk) > 48u * 1024u) --chunk;
+    ebc::RolloutIOSail ios;
+    static_cast<ebc::RolloutIO &>(ios) = io;
+    ios.epg = epg;
+    ios.sail = ebc::RolloutSail{h->sail_P, h->sail_N, chunk};
+    hipLaunchKernelGGL((ebc::rollout_kernel<GS, true>), dim3((unsigned)((E + epg - 1) / epg)), dim3(EBC_RO_THREADS), bytes(epg, chunk),
+                       h->stream, h->p, h->s, ios);
+    HIP_TRY(hipGetLastError());
+    return EBC_OK;
+  }
   while (epg > 1 && ebc::rollout_lds(epg, N, S, h->T, scratch).bytes > 48u * 1024u) --epg;
   const unsigned lds = ebc::rollout_lds(epg, N, S, h->T, scratch).bytes;
   // one env always fits: ebc_create takes at most 33 humans and 128 rows, which is under 30 KB here (the two row
@@ -977,6 +1012,30 @@ int ebc_robot_orca(void *handle, double safety_space, int location, double *acti
   }
   if ((rc = launch_robot_orca(h, safety_space, d_act)) != EBC_OK) return rc;
   if (location != EBC_DEVICE) return st.finish();
+  return EBC_OK;
+}
+
+int ebc_robot_sail(void *handle, void *sail) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!sail) {
+    if (h->sail_P) HIP_TRY(hipStreamSynchronize(h->stream));  // nothing enqueued still reads the weights being detached
+    h->sail_P = nullptr;
+    h->sail_N = 0;
+    return EBC_OK;
+  }
+  const ebc_sail_api::View v = ebc_sail_api::view(sail);
+  if (v.P == h->sail_P && v.N == h->sail_N) return EBC_OK;  // attached already
+  if (v.device != h->device)
+    return fail(EBC_ERR_INVALID, "ebc_robot_sail: the network is on device " + std::to_string(v.device) + ", the env handle on device " +
+                                     std::to_string(h->device));
+  if (h->s.N + h->s.S < v.N)
+    return fail(EBC_ERR_INVALID, "ebc_robot_sail: the env has " + std::to_string(h->s.N + h->s.S) +
+                                     " observation rows (max_humans + max_static), the network takes exactly adult_num = " + std::to_string(v.N));
+  if (h->sail_P) HIP_TRY(hipStreamSynchronize(h->stream));  // as for a detach: another network takes its place
+  h->sail_P = v.P;
+  h->sail_N = v.N;
   return EBC_OK;
 }
 
@@ -1043,8 +1102,11 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
   if (a->K < 1) return fail(EBC_ERR_INVALID, "K");
   if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL)
     return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
-  if (a->robot_policy != EBC_ROBOT_EXTERNAL && a->robot_policy != EBC_ROBOT_LINEAR && a->robot_policy != EBC_ROBOT_ORCA)
+  if (a->robot_policy != EBC_ROBOT_EXTERNAL && a->robot_policy != EBC_ROBOT_LINEAR && a->robot_policy != EBC_ROBOT_ORCA &&
+      a->robot_policy != EBC_ROBOT_SAIL)
     return fail(EBC_ERR_INVALID, "robot_policy");
+  const bool sail = a->robot_policy == EBC_ROBOT_SAIL;
+  if (sail && !h->sail_P) return fail(EBC_ERR_STATE, "ebc_step_k: EBC_ROBOT_SAIL with no network attached (ebc_robot_sail)");
   if (a->robot_policy == EBC_ROBOT_EXTERNAL && !a->robot_action) return fail(EBC_ERR_INVALID, "robot_action is NULL");
   if (a->robot_policy == EBC_ROBOT_LINEAR && h->p.robot_kinematics != EBC_HOLONOMIC)
     return fail(EBC_ERR_UNSUPPORTED, "the linear robot policy is holonomic (simulator/policy/linear.py:11)");
@@ -1090,9 +1152,14 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     if (a->location != EBC_DEVICE) return st.finish();
     return EBC_OK;
   }
-  // the ORCA robot's action of step k needs a home when the caller does not ask for the actions
+  if (sail && !h->sail_rows) {  // the gathers the network reads (DeviceSailPolicy's buffers)
+    if ((rc = dev_alloc(h, &h->sail_robot, E * 9)) != EBC_OK) return rc;
+    if ((rc = dev_alloc(h, &h->sail_ob, E * R * 5)) != EBC_OK) return rc;
+    if ((rc = dev_alloc(h, &h->sail_rows, E)) != EBC_OK) return rc;
+  }
+  // the ORCA or SAIL robot's action of step k needs a home when the caller does not ask for the actions
   double *orca_act = nullptr;
-  if (a->robot_policy == EBC_ROBOT_ORCA && !d_act_out) {
+  if ((a->robot_policy == EBC_ROBOT_ORCA || sail) && !d_act_out) {
     if (a->location != EBC_DEVICE) {
       orca_act = (double *)((char *)h->stage + st.off);
       st.off += pad256(E * 2 * 8);
@@ -1120,6 +1187,16 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
       double *act = d_act_out ? d_act_out + k * E * 2 : orca_act;
       if ((rc = launch_robot_orca(h, a->robot_safety_space, act)) != EBC_OK) return rc;
       io.robot_action = act;
+    } else if (sail) {  // DeviceSailPolicy.decide: ebc_get_state's robot, ebc_observe's ob, ebc_row_counts, sail_kernel
+      double *act = d_act_out ? d_act_out + k * E * 2 : orca_act;
+      HIP_TRY(hipMemcpyAsync(h->sail_robot, h->s.robot, E * 9 * 8, hipMemcpyDeviceToDevice, h->stream));
+      if ((rc = launch_observe(h, h->sail_ob, nullptr)) != EBC_OK) return rc;
+      hipLaunchKernelGGL(ebc::row_counts_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, h->stream, h->s, h->sail_rows);
+      HIP_TRY(hipGetLastError());
+      if ((rc = ebc_sail_api::launch(h->sail_P, h->sail_N, h->stream, h->sail_robot, h->sail_ob, h->sail_rows, act, nullptr, (int)E,
+                                     (int)R)) != EBC_OK)
+        return rc;
+      io.robot_action = act;
     } else if (a->robot_policy == EBC_ROBOT_EXTERNAL) {
       io.robot_action = d_act_in + k * E * 2;
     }
@@ -1128,8 +1205,8 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     io.info = d_info ? d_info + k * E : nullptr;
     io.dmin = d_dmin ? d_dmin + k * E * 3 : nullptr;
     io.dist_to_goal = d_goal ? d_goal + k * E : nullptr;
-    // with EBC_ROBOT_ORCA the step reads the action from where robot ORCA left it (already robot_action_out[k])
-    io.robot_action_out = (a->robot_policy != EBC_ROBOT_ORCA && d_act_out) ? d_act_out + k * E * 2 : nullptr;
+    // with EBC_ROBOT_ORCA and _SAIL the step reads the action from where the policy left it (already robot_action_out[k])
+    io.robot_action_out = (a->robot_policy != EBC_ROBOT_ORCA && !sail && d_act_out) ? d_act_out + k * E * 2 : nullptr;
     io.obs_rotated = d_obs ? d_obs + k * E * R * T : nullptr;
     if ((rc = launch_step(h, io, a->human_policy)) != EBC_OK) return rc;
   }

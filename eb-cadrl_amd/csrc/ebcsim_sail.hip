@@ -5,7 +5,9 @@
 #include <vector>
 
 #include "ebc_host.h"
+#define EBC_SAIL_KERNEL  // this unit owns sail_kernel
 #include "ebc_sail.h"
+#include "ebc_sail_api.h"
 
 namespace {
 
@@ -17,6 +19,29 @@ struct Sail {
 };
 
 }  // namespace
+
+ebc_sail_api::View ebc_sail_api::view(void *sail) {
+  const Sail *s = static_cast<const Sail *>(sail);
+  return View{s->P, s->N, s->device};
+}
+
+int ebc_sail_api::launch(const float *P, int N, hipStream_t stream, const double *robot, const double *ob, const long long *n_rows,
+                         double *action, float *feat_joint, int E, int R) {
+  ebc::SailLaunch a;
+  a.robot = robot;
+  a.ob = ob;
+  a.n_rows = n_rows;
+  a.action = action;
+  a.feat_joint = feat_joint;
+  a.E = E;
+  a.R = R;
+  a.N = N;
+  const int G = ebc_sail::group_envs(N);
+  const size_t lds = ebc::sail_lds_floats(N) * sizeof(float);  // <= 48 KB
+  hipLaunchKernelGGL(ebc::sail_kernel, dim3((unsigned)(((long long)E + G - 1) / G)), dim3(64 * EBC_SAIL_WAVES), lds, stream, P, a);
+  HIP_TRY(hipGetLastError());
+  return EBC_OK;
+}
 
 extern "C" int ebc_sail_create(const EbcSailWeights *w, int device_id, void **sail_out) {
   if (!w || !sail_out) return fail(EBC_ERR_INVALID, "ebc_sail_create: null argument");
@@ -58,21 +83,8 @@ extern "C" int ebc_sail_forward(void *sail, void *stream, const EbcSailArgs *arg
     return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_forward: the stream is being captured into a HIP graph; the forward must be launched, not replayed");
   if (args->E == 0) return EBC_OK;
   HIP_TRY(hipSetDevice(s->device));
-  ebc::SailLaunch a;
-  a.robot = args->robot;
-  a.ob = args->ob;
-  a.n_rows = reinterpret_cast<const long long *>(args->n_rows);
-  a.action = args->action;
-  a.feat_joint = args->feat_joint;
-  a.E = args->E;
-  a.R = args->R;
-  a.N = s->N;
-  const int G = ebc_sail::group_envs(s->N);
-  const size_t lds = ebc::sail_lds_floats(s->N) * sizeof(float);  // <= 48 KB
-  hipLaunchKernelGGL(ebc::sail_kernel, dim3((unsigned)(((long long)args->E + G - 1) / G)), dim3(64 * EBC_SAIL_WAVES), lds, (hipStream_t)stream,
-                     s->P, a);
-  HIP_TRY(hipGetLastError());
-  return EBC_OK;
+  return ebc_sail_api::launch(s->P, s->N, (hipStream_t)stream, args->robot, args->ob, reinterpret_cast<const long long *>(args->n_rows),
+                              args->action, args->feat_joint, args->E, args->R);
 }
 
 extern "C" int ebc_sail_destroy(void *sail) {

@@ -78,6 +78,7 @@ SYMBOLS = {
     "ebc_sail_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_sail_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_destroy": (C.c_int, [C.c_void_p]),
+    "ebc_robot_sail": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 

@@ -34,6 +34,7 @@ class BatchedEnv:
         if getattr(self, "_h", None) is not None and self._h.value:
             self._L.ebc_destroy(self._h)
             self._h = C.c_void_p()
+        self._sail = None  # after the handle: the library read the attached network's weights until here
 
     def __del__(self):
         try:
@@ -339,6 +340,22 @@ class BatchedEnv:
             raise ValueError("actions must be a contiguous float64 [E, 2] tensor")
         _capi.check(self._L.ebc_robot_orca(self._h, float(safety_space), _abi.DEVICE, actions.data_ptr()))
 
+    def attach_sail(self, net):
+        """Attach a sail.SailNet on this env's device as the EBC_ROBOT_SAIL policy of step_k / step_k_device
+        (ebc_robot_sail); None detaches.  The env keeps a reference to the net, so the native handle outlives the
+        attachment; the library keeps only its device weights."""
+        if net is None:
+            _capi.check(self._L.ebc_robot_sail(self._h, None))
+            self._sail = None
+            return
+        if net is getattr(self, "_sail", None):
+            return
+        nat = net.native()
+        if nat is None:
+            raise NotImplementedError("attach_sail needs a SailNet on a HIP device")
+        _capi.check(self._L.ebc_robot_sail(self._h, nat._h))
+        self._sail = net
+
     def get_state(self):
         E, N = self.E, self.N
         f = lambda *s: np.zeros(s)  # noqa: E731
@@ -433,7 +450,8 @@ class BatchedEnv:
     def step_k(self, K, keys=("reward", "done", "info", "state_rotated"), robot_action=None,
                human_policy=_abi.HUMAN_ORCA, robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0):
         """K steps in one call (ebc_step_k), host buffers: returns {key: array [K, ...]}.  flags may carry
-        _abi.FLAG_ONE_LAUNCH: the K steps as one kernel launch, same results bit for bit (ORCA humans only)."""
+        _abi.FLAG_ONE_LAUNCH: the K steps as one kernel launch, same results bit for bit (ORCA humans only).
+        robot_policy=_abi.ROBOT_SAIL: the network attached with attach_sail decides every step."""
         shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
         out = {k: np.zeros((K,) + shapes[k][0], dtype=shapes[k][1]) for k in keys}
         ra = None

@@ -191,7 +191,7 @@ class SailNet(object):
 
 class DeviceSailPolicy(object):
     """SAIL decisions for a whole BatchedEnv from its device state: ebc_get_state (robot), ebc_observe (ob) and
-    ebc_row_counts into device buffers, then one kernel."""
+    ebc_row_counts into device buffers, then one kernel (decide); or K decisions and steps in one call (rollout)."""
 
     def __init__(self, net):
         self.net = net
@@ -223,3 +223,13 @@ class DeviceSailPolicy(object):
         native_forward(nat._h, b["robot"], b["ob"], b["n_rows"], b["action"], b["feat_joint"])
         self.feat_joint = b["feat_joint"]
         return b["action"], None
+
+    def rollout(self, env, K, outputs, flags=0, human_policy=_abi.HUMAN_ORCA):
+        """K closed-loop steps in ONE call: attaches the net to `env` (BatchedEnv.attach_sail) and enqueues
+        step_k_device(robot_policy=ROBOT_SAIL) writing into `outputs` (torch CUDA tensors [K, ...], e.g.
+        env.alloc_step_k_outputs).  Step for step what decide() followed by step_device computes, without the host in
+        the loop; flags may carry FLAG_AUTO_RESET and FLAG_ONE_LAUNCH (the network inside the rollout kernel)."""
+        if env.R < self.net.adult_num:
+            raise ValueError("DeviceSailPolicy: the env has %d rows, the network takes exactly adult_num = %d" % (env.R, self.net.adult_num))
+        env.attach_sail(self.net)
+        env.step_k_device(outputs, K, human_policy=human_policy, robot_policy=_abi.ROBOT_SAIL, flags=flags)

@@ -544,6 +544,70 @@ def run_training(env, model, actions, gamma, il_steps=0, il_epochs=0, il_learnin
     return hist
 
 
+class _EpisodeTally(object):
+    """What evaluate() keeps per env over one episode each: the first terminal step's signal and time, the
+    discounted reward up to it and the danger counts (explorer.py:33-131)."""
+
+    def __init__(self, env, gamma):
+        dev = torch.device("cuda", env.device)
+        E = self.E = env.E
+        self.dt = float(env.params.time_step)
+        self.limit = float(env.params.time_limit)
+        self.gamma_bar = gamma ** (self.dt * uniform_v_pref(env))
+        self.dd = torch.tensor(list(env.params.discomfort_dist), dtype=torch.float64, device=dev)  # adult, bicycle, child
+        self.alive = torch.ones(E, dtype=torch.bool, device=dev)
+        self.final = torch.full((E,), -1, dtype=torch.int64, device=dev)
+        self.end_time = torch.zeros(E, dtype=torch.float64, device=dev)
+        self.cumulative = torch.zeros(E, dtype=torch.float64, device=dev)
+        self.too_close = torch.zeros((), dtype=torch.int64, device=dev)
+        self.min_sum = torch.zeros((), dtype=torch.float64, device=dev)
+
+    def step(self, t, reward, done, info, dm):
+        """The outputs of step t ([E] each, dmin [E, 3]); an env that has ended is ignored from then on."""
+        alive, dd, limit = self.alive, self.dd, self.limit
+        info = info.to(torch.int64)
+        self.cumulative += torch.where(alive, (self.gamma_bar ** t) * reward, torch.zeros_like(self.cumulative))
+        danger = alive & (info == _abi.INFO_DANGER)
+        # Danger.min_dist: the first type under its discomfort distance, child > bicycle > adult
+        md = torch.where(dm[:, 2] < dd[2], dm[:, 2], torch.where(dm[:, 1] < dd[1], dm[:, 1], dm[:, 0]))
+        self.too_close += danger.sum()
+        self.min_sum += torch.where(danger, md, torch.zeros_like(md)).sum()
+        ended = alive & done.bool()
+        self.final = torch.where(ended, info, self.final)
+        self.end_time = torch.where(ended, torch.where(info == _abi.INFO_TIMEOUT, torch.full_like(self.end_time, limit),
+                                                       torch.full_like(self.end_time, (t + 1) * self.dt)), self.end_time)
+        self.alive = alive & ~ended
+
+    def metrics(self):
+        E, dt, limit = self.E, self.dt, self.limit
+        final, end_time = self.final.cpu().numpy(), self.end_time.cpu().numpy()
+        if (final < 0).any():
+            raise ValueError("Invalid end signal from environment")  # explorer.py:80: every episode must end
+        n = float(E)
+        count = lambda code: int((final == code).sum())  # noqa: E731
+        cases = lambda code: [str(i) for i in np.nonzero(final == code)[0]]  # noqa: E731
+        ok = final == _abi.INFO_REACH_GOAL
+        num_step = end_time.sum() / dt
+        tc = int(self.too_close)
+        return {
+            "success_rate": count(_abi.INFO_REACH_GOAL) / n, "collision_rate": 0.0,
+            "collision_rate_adult": count(_abi.INFO_COLLISION_ADULT) / n,
+            "collision_rate_bicycle": count(_abi.INFO_COLLISION_BICYCLE) / n,
+            "collision_rate_child": count(_abi.INFO_COLLISION_CHILD) / n,
+            "collision_rate_obstacle": count(_abi.INFO_COLLISION_OBSTACLE) / n,
+            "success": count(_abi.INFO_REACH_GOAL), "collision": 0, "timeout": count(_abi.INFO_TIMEOUT),
+            "avg_nav_time": float(end_time[ok].mean()) if ok.any() else limit,
+            "total_reward:": float(self.cumulative.mean()),
+            "Frequency of being in danger": tc / num_step if num_step else None,
+            "average min separate distance in danger": float(self.min_sum) / tc if tc else 0,
+            "Collision cases:": [], "Collision Adult cases:": cases(_abi.INFO_COLLISION_ADULT),
+            "Collision Bicycle cases:": cases(_abi.INFO_COLLISION_BICYCLE),
+            "Collision Child cases:": cases(_abi.INFO_COLLISION_CHILD),
+            "Collision Obstacle cases:": cases(_abi.INFO_COLLISION_OBSTACLE),
+            "Timeout cases": cases(_abi.INFO_TIMEOUT), "num_episodes": E,
+        }
+
+
 def evaluate(env, decide, gamma, max_steps=None, human_policy=_abi.HUMAN_ORCA):
     """Explorer.run_k_episodes on the `val` / `test` cases (explorer.py:33-131, :202-330), batched: one
     episode per env of a freshly reset BatchedEnv (no auto-reset; an env that has ended is ignored from
@@ -551,62 +615,36 @@ def evaluate(env, decide, gamma, max_steps=None, human_policy=_abi.HUMAN_ORCA):
     policy.decide(e)[0]` with human_policy=EBC_HUMAN_CACHED: the decision's sweep has already worked out
     the humans' velocities).  Returns the reference's compile_metrics() dictionary (same keys; the case
     lists hold env indices) plus "num_episodes"."""
-    dev = torch.device("cuda", env.device)
-    E = env.E
-    dt = float(env.params.time_step)
-    limit = float(env.params.time_limit)
-    steps = int(max_steps or round(limit / dt) + 2)
+    tally = _EpisodeTally(env, gamma)
+    steps = int(max_steps or round(tally.limit / tally.dt) + 2)
     outs = env.alloc_step_outputs(("reward", "done", "info", "dmin"))
-    v_pref = uniform_v_pref(env)
-    gamma_bar = gamma ** (dt * v_pref)
-    dd = torch.tensor(list(env.params.discomfort_dist), dtype=torch.float64, device=dev)  # adult, bicycle, child
-    alive = torch.ones(E, dtype=torch.bool, device=dev)
-    final = torch.full((E,), -1, dtype=torch.int64, device=dev)
-    end_time = torch.zeros(E, dtype=torch.float64, device=dev)
-    cumulative = torch.zeros(E, dtype=torch.float64, device=dev)
-    too_close = torch.zeros((), dtype=torch.int64, device=dev)
-    min_sum = torch.zeros((), dtype=torch.float64, device=dev)
     for t in range(steps):
         actions = decide(env)
         env.step_device(outs, robot_action=actions.contiguous(), human_policy=human_policy)
-        info = outs["info"].to(torch.int64)
-        cumulative += torch.where(alive, (gamma_bar ** t) * outs["reward"], torch.zeros_like(cumulative))
-        danger = alive & (info == _abi.INFO_DANGER)
-        dm = outs["dmin"]  # Danger.min_dist: the first type under its discomfort distance, child > bicycle > adult
-        md = torch.where(dm[:, 2] < dd[2], dm[:, 2], torch.where(dm[:, 1] < dd[1], dm[:, 1], dm[:, 0]))
-        too_close += danger.sum()
-        min_sum += torch.where(danger, md, torch.zeros_like(md)).sum()
-        ended = alive & outs["done"].bool()
-        final = torch.where(ended, info, final)
-        end_time = torch.where(ended, torch.where(info == _abi.INFO_TIMEOUT, torch.full_like(end_time, limit),
-                                                  torch.full_like(end_time, (t + 1) * dt)), end_time)
-        alive = alive & ~ended
-        if t % 8 == 7 and not bool(alive.any()):
+        tally.step(t, outs["reward"], outs["done"], outs["info"], outs["dmin"])
+        if t % 8 == 7 and not bool(tally.alive.any()):
             break
     env.synchronize()  # before the metrics: a broken step must not be counted
-    final, end_time = final.cpu().numpy(), end_time.cpu().numpy()
-    if (final < 0).any():
-        raise ValueError("Invalid end signal from environment")  # explorer.py:80: every episode must end
-    n = float(E)
-    count = lambda code: int((final == code).sum())  # noqa: E731
-    cases = lambda code: [str(i) for i in np.nonzero(final == code)[0]]  # noqa: E731
-    ok = final == _abi.INFO_REACH_GOAL
-    num_step = end_time.sum() / dt
-    tc = int(too_close)
-    return {
-        "success_rate": count(_abi.INFO_REACH_GOAL) / n, "collision_rate": 0.0,
-        "collision_rate_adult": count(_abi.INFO_COLLISION_ADULT) / n,
-        "collision_rate_bicycle": count(_abi.INFO_COLLISION_BICYCLE) / n,
-        "collision_rate_child": count(_abi.INFO_COLLISION_CHILD) / n,
-        "collision_rate_obstacle": count(_abi.INFO_COLLISION_OBSTACLE) / n,
-        "success": count(_abi.INFO_REACH_GOAL), "collision": 0, "timeout": count(_abi.INFO_TIMEOUT),
-        "avg_nav_time": float(end_time[ok].mean()) if ok.any() else limit,
-        "total_reward:": float(cumulative.mean()),
-        "Frequency of being in danger": tc / num_step if num_step else None,
-        "average min separate distance in danger": float(min_sum) / tc if tc else 0,
-        "Collision cases:": [], "Collision Adult cases:": cases(_abi.INFO_COLLISION_ADULT),
-        "Collision Bicycle cases:": cases(_abi.INFO_COLLISION_BICYCLE),
-        "Collision Child cases:": cases(_abi.INFO_COLLISION_CHILD),
-        "Collision Obstacle cases:": cases(_abi.INFO_COLLISION_OBSTACLE),
-        "Timeout cases": cases(_abi.INFO_TIMEOUT), "num_episodes": E,
-    }
+    return tally.metrics()
+
+
+def evaluate_windows(env, rollout, gamma, steps_per_call, max_steps=None):
+    """evaluate() for a policy that lives on the device, in windows of `steps_per_call` steps per call:
+    rollout(env, K, outputs) enqueues K closed-loop steps writing reward, done, info and dmin [K, ...] (e.g.
+    sail.DeviceSailPolicy.rollout).  The same first-terminal masking step by step, so the same metrics as evaluate()
+    with the per-step loop of the same policy; steps of a window past the end of every episode count for nothing."""
+    tally = _EpisodeTally(env, gamma)
+    steps = int(max_steps or round(tally.limit / tally.dt) + 2)
+    K = int(steps_per_call)
+    if K < 1:
+        raise ValueError("steps_per_call must be at least 1")
+    outs = env.alloc_step_k_outputs(min(K, steps), ("reward", "done", "info", "dmin"))
+    for t0 in range(0, steps, K):
+        k = min(K, steps - t0)
+        rollout(env, k, {name: v[:k] for name, v in outs.items()})
+        for i in range(k):
+            tally.step(t0 + i, outs["reward"][i], outs["done"][i], outs["info"][i], outs["dmin"][i])
+        if not bool(tally.alive.any()):
+            break
+    env.synchronize()  # before the metrics: a broken step must not be counted
+    return tally.metrics()

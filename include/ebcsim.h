@@ -82,7 +82,8 @@ enum {
 enum {
   EBC_ROBOT_EXTERNAL = 0, /* robot_action[E][2] supplied */
   EBC_ROBOT_LINEAR = 1,   /* simulator/policy/linear.py:17-23 applied to the robot, on device */
-  EBC_ROBOT_ORCA = 2      /* ebc_step_k only: the robot on ORCA (ebc_robot_orca), the imitation-learning demonstrator */
+  EBC_ROBOT_ORCA = 2,     /* ebc_step_k only: the robot on ORCA (ebc_robot_orca), the imitation-learning demonstrator */
+  EBC_ROBOT_SAIL = 3      /* ebc_step_k only: the SAIL network attached with ebc_robot_sail decides every step */
 };
 
 /* flags */
@@ -354,13 +355,31 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *args);
  *   - Strict: EBC_HUMAN_LINEAR and EBC_HUMAN_EXTERNAL return EBC_ERR_UNSUPPORTED; nothing else is left out (every
  *     handle ebc_create accepts fits).  The call never falls back to the per-step form.  Every refusal of ebc_step_k (capturing
  *     stream, EBC_FLAG_BORDER, K < 1, before reset, faulted handle) holds for it too.
- *   - No mailboxes, no polling, no give-up path: this launch cannot raise the handle's fault word. */
+ *   - No mailboxes, no polling, no give-up path: this launch cannot raise the handle's fault word.
+ *
+ * EBC_ROBOT_SAIL: the network attached with ebc_robot_sail (below) decides every step, a closed loop on the device.
+ *   - Per-step form: per step k the library enqueues the gathers of the robot state, the world-frame observation rows
+ *     and the row counts into scratch the handle owns (what ebc_get_state, ebc_observe and ebc_row_counts give), the
+ *     kernel of ebc_sail_forward writing the action into robot_action_out[k] (or the handle's scratch when that is
+ *     NULL), and ebc_step reading it: launch for launch ebc_sail_forward on the env's state followed by ebc_step.
+ *   - EBC_FLAG_ONE_LAUNCH: the network runs inside the rollout kernel from the LDS-resident state, on all four waves
+ *     of the workgroup before the humans' ORCA passes; outputs and state are the per-step form's bit for bit.  The
+ *     network's LDS area for one env is 4 * (adult_num * (max(4 adult_num, 64) + 134) + 272) bytes (2.6 KB at
+ *     adult_num 2, 4.9 KB at 5, 8.8 KB at 10, 13.4 KB at 16, 22.6 KB at 24, 33.8 KB at 32) behind the env's rollout
+ *     arrays, and one env of each has to fit the kernel's 48 KB.  With R = max_humans + max_static rows of 17 floats:
+ *     adult_num <= 10 fits every handle ebc_create accepts; adult_num 16 up to R = 125, 20 up to R = 98, 24 up to
+ *     R = 68, 28 up to R = 34 whatever max_humans is (more rows with more humans: R = 118, 112, 76 with max_humans =
+ *     adult_num); adult_num 32 only with R <= 36.  What does not fit returns EBC_ERR_UNSUPPORTED and ebc_last_error
+ *     gives both sizes; the call never falls back to the per-step form.
+ *   - The arrival rule ((0, 0) inside the goal radius), the NaN action of an env whose row count is not adult_num
+ *     and both kinematics (the two outputs are ActionXY or ActionRot as ebc_step takes them) are ebc_sail_forward's.
+ *   - Refused before anything is enqueued: no network attached (EBC_ERR_STATE), and every refusal above. */
 typedef struct EbcStepKArgs {
   uint32_t struct_size;
   int32_t location;      /* of every pointer below */
   int32_t K;             /* steps, >= 1 */
   int32_t human_policy;  /* EBC_HUMAN_ORCA, _LINEAR or _EXTERNAL (the same supplied velocities every step) */
-  int32_t robot_policy;  /* EBC_ROBOT_ORCA, _LINEAR or _EXTERNAL */
+  int32_t robot_policy;  /* EBC_ROBOT_ORCA, _LINEAR, _EXTERNAL or _SAIL */
   int32_t flags;
   double robot_safety_space;  /* EBC_ROBOT_ORCA: the policy's safety_space (rl/train.py:127-129) */
   const double *robot_action; /* [K][E][2], EBC_ROBOT_EXTERNAL only */
@@ -691,6 +710,11 @@ int ebc_sail_create(const EbcSailWeights *weights, int device_id, void **sail_ou
 int ebc_sail_forward(void *sail, void *stream, const EbcSailArgs *args);
 /* frees what ebc_sail_create (sail.py:109-112) made */
 int ebc_sail_destroy(void *sail);
+/* Attach a network made by ebc_sail_create to an env handle as its EBC_ROBOT_SAIL policy (ebc_step_k); sail = NULL
+ * detaches.  The env handle keeps the network's device weights and adult_num, not the network: DETACH (or destroy the
+ * env handle) BEFORE ebc_sail_destroy.  EBC_ERR_INVALID, with the attachment as it was: the network is on another device
+ * than the env handle; the env handle has max_humans + max_static < adult_num rows. */
+int ebc_robot_sail(void *handle, void *sail);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,10 @@ reference's metrics at the end.
                                           look-ahead; every scene must have exactly the network's adult_num rows, an
                                           env with another count gets a NaN action.  Neither tree ships SAIL weights:
                                           --weights is required)
+    python3 tools/evaluate.py --policy sail --weights SAIL_STATE_DICT_FILE --env-config ENV --steps-per-call 32 [--one-launch]
+                                         (the same episodes in windows of 32 steps per ebc_step_k call with the network
+                                          as the robot policy on the device, EBC_ROBOT_SAIL: same metrics, no host
+                                          work per step; --one-launch: each window as one kernel launch)
 """
 import argparse
 import configparser
@@ -50,7 +54,14 @@ def main():
     ap.add_argument("--safety-space", type=float, default=0.15)
     ap.add_argument("--device-scenes", action="store_true",
                     help="generate the test scenes on the device (ebc_generate_reset) instead of on the host")
+    ap.add_argument("--steps-per-call", type=int, default=0, metavar="K",
+                    help="--policy sail: advance in windows of K steps per ebc_step_k call (default 0: the per-step loop)")
+    ap.add_argument("--one-launch", action="store_true", help="with --steps-per-call: each window as one kernel launch")
     args = ap.parse_args()
+    if (args.steps_per_call or args.one_launch) and args.policy != "sail":
+        ap.error("--steps-per-call / --one-launch go with --policy sail, the policy ebc_step_k keeps on the device")
+    if args.one_launch and args.steps_per_call < 1:
+        ap.error("--one-launch needs --steps-per-call K")
     if args.policy == "lstm_rl" and not args.weights:
         ap.error("--policy lstm_rl needs --weights: a state_dict file of one of the reference's LSTM-RL networks")
     if args.policy == "cadrl" and not args.weights:
@@ -117,7 +128,13 @@ def main():
         hp = _abi.HUMAN_ORCA
     torch.cuda.synchronize()
     t2 = time.perf_counter()
-    m = evaluate(env, decide, args.gamma, human_policy=hp)
+    if args.steps_per_call > 0:
+        from ebcsim.train import evaluate_windows
+        flags = _abi.FLAG_ONE_LAUNCH if args.one_launch else 0
+        m = evaluate_windows(env, lambda e, K, outs: policy.rollout(e, K, outs, flags=flags, human_policy=hp), args.gamma,
+                             args.steps_per_call)
+    else:
+        m = evaluate(env, decide, args.gamma, human_policy=hp)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
     print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
