@@ -19,4 +19,8 @@ View view(void *sail);
 int launch(const float *P, int N, hipStream_t stream, const double *robot, const double *ob, const long long *n_rows,
            double *action, float *feat_joint, int E, int R);
 
+// device memory the network owns for ebc_sail_grad (ebcsim_sail_grad.hip), at least `bytes`, grown on demand and freed
+// by ebc_sail_destroy
+int grad_scratch(void *sail, size_t bytes, void **out);
+
 }  // namespace ebc_sail_api

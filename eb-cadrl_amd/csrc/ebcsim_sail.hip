@@ -16,6 +16,8 @@ using ebc_host::fail;
 struct Sail {
   int device = 0, N = 0;
   float *P = nullptr;
+  void *grad_scratch = nullptr;  // ebc_sail_grad's chunk partials, grown on demand
+  size_t grad_scratch_bytes = 0;
 };
 
 }  // namespace
@@ -23,6 +25,22 @@ struct Sail {
 ebc_sail_api::View ebc_sail_api::view(void *sail) {
   const Sail *s = static_cast<const Sail *>(sail);
   return View{s->P, s->N, s->device};
+}
+
+int ebc_sail_api::grad_scratch(void *sail, size_t bytes, void **out) {
+  Sail *s = static_cast<Sail *>(sail);
+  if (bytes > s->grad_scratch_bytes) {
+    (void)hipFree(s->grad_scratch);  // waits for the work that may still read it
+    s->grad_scratch = nullptr;
+    s->grad_scratch_bytes = 0;
+    if (hipMalloc(&s->grad_scratch, bytes) != hipSuccess) {
+      s->grad_scratch = nullptr;
+      return fail(EBC_ERR_DEVICE, "ebc_sail_grad: scratch allocation of " + std::to_string(bytes) + " bytes failed");
+    }
+    s->grad_scratch_bytes = bytes;
+  }
+  *out = s->grad_scratch;
+  return EBC_OK;
 }
 
 int ebc_sail_api::launch(const float *P, int N, hipStream_t stream, const double *robot, const double *ob, const long long *n_rows,
@@ -92,6 +110,7 @@ extern "C" int ebc_sail_destroy(void *sail) {
   if (!s) return EBC_OK;
   (void)hipSetDevice(s->device);
   (void)hipFree(s->P);
+  (void)hipFree(s->grad_scratch);
   delete s;
   return EBC_OK;
 }

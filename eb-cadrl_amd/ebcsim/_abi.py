@@ -222,3 +222,10 @@ class EbcSailArgs(C.Structure):
     -> action [E][2] float64, feat_joint [E][64] float32 or NULL)."""
     _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("R", C.c_int32), ("reserved", C.c_int32)] + [
         (k, C.c_void_p) for k in ("robot", "ob", "n_rows", "action", "feat_joint")]
+
+
+class EbcSailGradArgs(C.Structure):
+    """include/ebcsim.h: one ebc_sail_grad (robot, ob, n_rows or NULL, target [E][2] float64, sample_mask [E] uint8 or NULL
+    -> grad float32 [packed_floats], loss_sum float64 [1], count int64 [1], action [E][2] float64 or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("R", C.c_int32), ("grad_scale", C.c_float)] + [
+        (k, C.c_void_p) for k in ("robot", "ob", "n_rows", "target", "sample_mask", "grad", "loss_sum", "count", "action")]

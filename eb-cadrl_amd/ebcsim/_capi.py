@@ -79,6 +79,10 @@ SYMBOLS = {
     "ebc_sail_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_destroy": (C.c_int, [C.c_void_p]),
     "ebc_robot_sail": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ebc_sail_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_sail_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ebc_sail_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_sail_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -716,6 +716,49 @@ int ebc_sail_destroy(void *sail);
  * than the env handle; the env handle has max_humans + max_static < adult_num rows. */
 int ebc_robot_sail(void *handle, void *sail);
 
+/* ---- training the SAIL network by imitation: the gradient of the regression loss on a demonstrator's action with
+ * respect to every weight, in one launch that runs the forward with every activation kept on chip and then the backward,
+ * and a second small launch that adds the partial sums.  The arithmetic is csrc/ebc_sail_grad_rule.h (one definition for
+ * the kernel and for the host build tests/native/sail_grad_host.cc compares it with byte for byte).
+ *   w_e = 0 for an env that has arrived, whose n_rows is not adult_num, or whose sample_mask is 0; such an env enters no
+ *     sum (a selection, never a product with 0: its NaNs reach nothing but its own `action`)
+ *   loss_sum = the sum over envs of w_e * ((planned[0] - (float)target[0])^2 + (planned[1] - (float)target[1])^2)
+ *   grad     = d/dweights of grad_scale / 2 * loss_sum (the seed is grad_scale * (planned - target)): grad_scale =
+ *              1 / count is the mean squared error over 2 * count elements, torch's MSELoss
+ *   count    = the sum of w_e
+ *   action   = what ebc_sail_forward gives on the same inputs, byte for byte (NULL: not written)
+ * The batch is cut into chunks of 16 consecutive envs; a weight's float32 sum runs over a chunk's envs (and their rows)
+ * ascending, the chunks are added ascending in float64 and rounded once: the result depends on the inputs alone, never
+ * on the grid or on timing.  grad has the layout of the packed image (ebc_sail_packed_floats floats: the 14 layers in
+ * the order of EbcSailWeights, each as W[k][64] — unit u of input k at k * 64 + u — followed by bias[64]; entries past
+ * a layer's width are exactly 0).  Scratch for the partial sums belongs to the network and grows on demand (growing
+ * waits for the device).  Device pointers.  A stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcSailGradArgs {
+  uint32_t struct_size;
+  int32_t E;
+  int32_t R;                    /* row stride of ob, R >= adult_num */
+  float grad_scale;
+  const double *robot;          /* device float64 [E][9] FullState order */
+  const double *ob;             /* device float64 [E][R][5] */
+  const int64_t *n_rows;        /* device int64 [E]; NULL = every env has adult_num rows */
+  const double *target;         /* device float64 [E][2]: the demonstrator's action */
+  const uint8_t *sample_mask;   /* device uint8 [E]; NULL = every env counts */
+  float *grad;                  /* device float32 [ebc_sail_packed_floats] */
+  double *loss_sum;             /* device float64 [1] */
+  int64_t *count;               /* device int64 [1] */
+  double *action;               /* device float64 [E][2], or NULL */
+} EbcSailGradArgs;
+int ebc_sail_grad(void *sail, void *stream, const EbcSailGradArgs *args);
+/* floats of the network's packed image */
+int ebc_sail_packed_floats(void *sail, int64_t *floats_out);
+/* the packed image into dst_dev (device float32 [ebc_sail_packed_floats]): a copy enqueued on `stream` */
+int ebc_sail_get_packed(void *sail, void *stream, float *dst_dev);
+/* src_dev (device float32, the packed layout, pad entries 0) becomes the network's weights: a stream-ordered copy into
+ * the network's own image, enqueued on `stream`.  Everything enqueued after it on that stream (or ordered after it)
+ * computes with the new weights, also an env handle the network is attached to (ebc_robot_sail keeps a pointer to the
+ * image, not a copy): its next enqueued ebc_step_k decides with them.  Work on other streams is not ordered with it. */
+int ebc_sail_set_packed(void *sail, void *stream, const float *src_dev);
+
 #ifdef __cplusplus
 }
 #endif

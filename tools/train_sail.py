@@ -1,0 +1,100 @@
+#!/usr/bin/env python3
+"""Train the SAIL network by imitation of the ORCA robot on the device and score it: demonstrations from `--envs` envs on
+device-generated train scenes (ebcsim.sail_train.collect_sail_demos), `--epochs` passes of minibatch regression with the
+fused gradient kernel (ebc_sail_grad) and Adam, the weights saved in the reference's ExtendedNetwork layout, then the
+evaluation tools/evaluate.py --policy sail runs on the test cases, with the reference's metrics.
+
+    python3 tools/train_sail.py --env-config ENV_WITH_ADULT_NUM_ROWS --device-scenes [--envs 1024] [--demo-steps 120]
+                                [--epochs 50] [--batch-size 1024] [--lr 1e-3] [--cases 500] [--out sail_model.pth]
+
+The env config's scenes must have exactly adult_num rows each (the network takes no other count)."""
+import argparse
+import configparser
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "eb-cadrl_amd")):
+    sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--env-config", required=True)
+    ap.add_argument("--policy-config", default=os.path.join(ROOT, "eb-cadrl_amd", "configs", "policy_agent_type.config"))
+    ap.add_argument("--device-scenes", action="store_true", help="generate the scenes on the device (required: the only form built)")
+    ap.add_argument("--envs", type=int, default=1024)
+    ap.add_argument("--demo-steps", type=int, default=120)
+    ap.add_argument("--epochs", type=int, default=50)
+    ap.add_argument("--batch-size", type=int, default=1024)
+    ap.add_argument("--lr", type=float, default=1e-3)
+    ap.add_argument("--safety-space", type=float, default=0.15)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--cases", type=int, default=500, help="test cases of the closing evaluation")
+    ap.add_argument("--gamma", type=float, default=0.9)
+    ap.add_argument("--autograd", action="store_true", help="torch autograd instead of the kernel (the comparison path)")
+    ap.add_argument("--out", default="sail_model.pth")
+    args = ap.parse_args()
+    if not args.device_scenes:
+        ap.error("--device-scenes is required: demonstrations restart from a pool of device-generated scenes")
+    import torch
+    from ebcsim import _abi, config as ebc_config, scene as ebc_scene
+    from ebcsim.batched import BatchedEnv
+    from ebcsim.sail import DeviceSailPolicy, SailModule, SailNet
+    from ebcsim.sail_train import SailTrainer, collect_sail_demos, fit
+    from ebcsim.train import evaluate
+    cfg, pol = configparser.RawConfigParser(), configparser.RawConfigParser()
+    cfg.read(args.env_config)
+    pol.read(args.policy_config)
+    params = ebc_config.params_from_config(cfg, pol, policy="sail")
+    sc = ebc_scene.SceneConfig.from_config(cfg)
+    gen = ebc_scene.gen_struct(sc, "train")
+    N = sum(gen.count)
+    if ebc_scene.max_static_rows(sc):
+        ap.error("the env config has static rows: SAIL takes exactly adult_num rows per scene")
+    E = args.envs
+    env = BatchedEnv(params, E, N, 0)
+    env.use_torch_stream()
+    seed0 = ebc_scene.COUNTER_OFFSET["train"]
+    env.generate_reset(gen, seed0)
+    env.generate_pool(gen, seed0 + E, 4 * E)
+    t0 = time.perf_counter()
+    demos = collect_sail_demos(env, args.demo_steps, args.safety_space)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    print("demonstrations: %d envs x %d steps, %d episodes ended, %d steps kept (ReachGoal episodes) in %.2f s"
+          % (E, args.demo_steps, demos["episodes"], demos["steps"], t1 - t0))
+    env.close()
+    torch.manual_seed(args.seed)
+    trainer = SailTrainer(SailModule(N), device="cuda:0", optimizer="adam", lr=args.lr, native=not args.autograd)
+    losses = fit(trainer, demos, args.epochs, args.batch_size, generator=torch.Generator(device="cuda:0").manual_seed(args.seed))
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print("fit: %d epochs of %d batches (%s) in %.2f s; mean squared error per epoch: first %.6f, last %.6f"
+          % (args.epochs, -(-demos["steps"] // args.batch_size), "torch autograd" if args.autograd else "ebc_sail_grad", t2 - t1,
+             losses[0], losses[-1]))
+    trainer.save(args.out)
+    print("saved %s" % args.out)
+    # what tools/evaluate.py --policy sail --device-scenes runs
+    test = ebc_scene.gen_struct(sc, "test")
+    env = BatchedEnv(params, args.cases, sum(test.count), 0)
+    env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
+    env.synchronize()
+    env.use_torch_stream()
+    policy = DeviceSailPolicy(SailNet.load(args.out, device="cuda:0"))
+    m = evaluate(env, lambda e: policy.decide(e)[0], args.gamma, human_policy=_abi.HUMAN_ORCA)
+    torch.cuda.synchronize()
+    print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
+          "timeout: %d, nav time: %.2f, total reward: %.4f" % (
+              m["success_rate"], m["collision_rate_adult"], m["collision_rate_bicycle"], m["collision_rate_child"],
+              m["collision_rate_obstacle"], m["timeout"], m["avg_nav_time"], m["total_reward:"]))
+    print("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f" % (
+        m["Frequency of being in danger"] or 0.0, m["average min separate distance in danger"]))
+    print(json.dumps({"envs": E, "demo_steps": args.demo_steps, "kept": demos["steps"], "epochs": args.epochs, "losses": [losses[0], losses[-1]],
+                      "cases": args.cases, "metrics": {k: v for k, v in m.items() if not isinstance(v, list)}}))
+
+
+if __name__ == "__main__":
+    main()
