@@ -313,43 +313,81 @@ struct RobotSim {
   float2 *self;
 };
 
+// Where a lane of a robot group stands: env ee (0 on an idle lane, e_ok false), row j of its observation, the env's
+// humans n and static rows ns.
+struct RobotLane {
+  bool e_ok;
+  size_t ee;
+  int group, j, n, ns;
+};
 template <int GS>
-__global__ __launch_bounds__(EBC_WAVE) void orca_robot_kernel(EbcParams p, DevState s, double safety_space, double *act, RobotSim sim) {
-  using L = OrcaLds<GS>;
+__device__ __forceinline__ RobotLane robot_lane(const DevState &s) {
   constexpr int EPW = EBC_WAVE / GS;
-  __shared__ __align__(16) unsigned char scratch[L::BYTES];
+  RobotLane l;
+  l.group = threadIdx.x / GS;
+  l.j = threadIdx.x - l.group * GS;
+  const int e = (int)blockIdx.x * EPW + l.group;
+  l.e_ok = l.group < EPW && e < s.E;  // lanes past EPW * GS idle
+  l.ee = l.e_ok ? (size_t)e : 0;
+  l.n = l.e_ok ? s.n_humans[l.ee] : 0;
+  l.ns = (l.e_ok && s.S) ? s.n_static[l.ee] : 0;
+  return l;
+}
+
+// Row j of the env's observation in the world frame (env.py:381-382, :457-458): px, py, vx, vy, radius as the state
+// holds them (float64); a row that does not exist is zeros, which is also what ebc_observe writes for it.
+struct RobotRow {
+  double px, py, vx, vy, radius;
+};
+__device__ __forceinline__ RobotRow robot_row_load(const DevState &s, const RobotLane &l, bool &valid) {
+  RobotRow r = {0, 0, 0, 0, 0};
+  valid = l.e_ok && l.j < l.n + l.ns;
+  if (valid && l.j < l.n) {
+    const size_t k = l.ee * s.N + l.j;
+    r.px = s.px[k];
+    r.py = s.py[k];
+    r.vx = s.vx[k];
+    r.vy = s.vy[k];
+    r.radius = s.radius[k];
+  } else if (valid) {
+    const size_t q = l.ee * s.S + (l.j - l.n);
+    r.px = s.spx[q];
+    r.py = s.spy[q];
+    r.radius = s.sradius[q];
+  }
+  return r;
+}
+
+// The robot's ORCA solve of one GS-lane group, from the values the caller loaded: rb = the robot's FullState (entries
+// 0 .. 7 are read), row = this lane's observation row.  The ONE definition of that arithmetic for orca_robot_kernel and
+// dagger_label_kernel (ebc_dagger.h), the persistent simulator's read-before-replace included.  before_solve() runs once
+// every global load of the function has been consumed and before the LDS-bound solve: where a caller issues stores
+// that nothing here waits for.
+template <int GS, typename Hook = NoHook>
+__device__ __forceinline__ void orca_robot_solve(const EbcParams &p, const DevState &s, double safety_space, const RobotSim &sim,
+                                                 unsigned char *scratch, const RobotLane &l, const double *rb, const RobotRow &row,
+                                                 bool valid, float &ox, float &oy, Hook before_solve = Hook()) {
+  using L = OrcaLds<GS>;
   float *dist_lds = reinterpret_cast<float *>(scratch);
   float4 *lines_lds = reinterpret_cast<float4 *>(scratch + L::DIST);
   float4 *segs_lds = lines_lds + L::GROUPS * L::Sh::LINES;
   float4 *proj_lds = segs_lds + L::GROUPS * L::Sh::LINES;
-  const int group = threadIdx.x / GS, j = threadIdx.x - group * GS;
-  const int e = (int)blockIdx.x * EPW + group;
-  const bool e_ok = group < EPW && e < s.E;  // lanes past EPW * GS idle
-  const size_t ee = e_ok ? (size_t)e : 0;
+  const int group = l.group, j = l.j, n = l.n, ns = l.ns;
+  const size_t ee = l.ee;
   const int N = s.N, S = s.S;
-  const int n = e_ok ? s.n_humans[ee] : 0;
-  const int ns = (e_ok && S) ? s.n_static[ee] : 0;
-  const double *rb = s.robot + ee * 9;
   const float posx = (float)rb[0], posy = (float)rb[1], velx = (float)rb[2], vely = (float)rb[3];
   float radius = (float)(rb[4] + 0.01 + safety_space), maxSpeed = (float)rb[7];
   float prefx, prefy;
   orca_pref_velocity(rb[0], rb[1], rb[5], rb[6], prefx, prefy);
-  const bool valid = e_ok && j < n + ns;
   float opx = 0, opy = 0, ovx = 0, ovy = 0, orad = 0;
-  if (valid && j < n) {
-    const size_t k = ee * N + j;
-    opx = (float)s.px[k];
-    opy = (float)s.py[k];
-    ovx = (float)s.vx[k];
-    ovy = (float)s.vy[k];
-    orad = (float)(s.radius[k] + 0.01 + safety_space);
-  } else if (valid) {
-    const size_t q = ee * S + (j - n);
-    opx = (float)s.spx[q];
-    opy = (float)s.spy[q];
-    orad = (float)(s.sradius[q] + 0.01 + safety_space);
+  if (valid) {  // a static row's velocity is the 0 robot_row_load left
+    opx = (float)row.px;
+    opy = (float)row.py;
+    ovx = (float)row.vx;
+    ovy = (float)row.vy;
+    orad = (float)(row.radius + 0.01 + safety_space);
   }
-  if (sim.rows && e_ok) {
+  if (sim.rows && l.e_ok) {
     // every lane of the group reads the simulator's row count before lane 0 of the group replaces it (one wave)
     const bool rebuild = sim.rows[ee] != n + ns;  // sim is None, or getNumAgents() != len(agent_states) + 1
     const size_t q = ee * (size_t)(N + S) + j;
@@ -366,14 +404,24 @@ __global__ __launch_bounds__(EBC_WAVE) void orca_robot_kernel(EbcParams p, DevSt
       maxSpeed = me.y;
     }
   }
-  float ox, oy;
+  before_solve();
   orca_group<GS>(p, j, group, valid, posx, posy, velx, vely, radius, maxSpeed, prefx, prefy, opx, opy, ovx, ovy,
                  orad, dist_lds + group * L::Sh::DIST, lines_lds + group * L::Sh::LINES,
                  segs_lds + group * L::Sh::LINES, proj_lds + group * L::Sh::LINES, N + S, s.range_sq,
                  s.inv_time_horizon, s.inv_time_step, ox, oy);
-  if (e_ok && j == 0) {
-    act[2 * ee] = (double)ox;  // getAgentVelocity -> Python float
-    act[2 * ee + 1] = (double)oy;
+}
+
+template <int GS>
+__global__ __launch_bounds__(EBC_WAVE) void orca_robot_kernel(EbcParams p, DevState s, double safety_space, double *act, RobotSim sim) {
+  __shared__ __align__(16) unsigned char scratch[OrcaLds<GS>::BYTES];
+  const RobotLane l = robot_lane<GS>(s);
+  bool valid;
+  const RobotRow row = robot_row_load(s, l, valid);
+  float ox, oy;
+  orca_robot_solve<GS>(p, s, safety_space, sim, scratch, l, s.robot + l.ee * 9, row, valid, ox, oy);
+  if (l.e_ok && l.j == 0) {
+    act[2 * l.ee] = (double)ox;  // getAgentVelocity -> Python float
+    act[2 * l.ee + 1] = (double)oy;
   }
 }
 

@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "ebc_host.h"
+#include "ebc_dagger.h"
 #include "ebc_kernels.h"
 #include "ebc_local_map_kernel.h"
 #include "ebc_rollout.h"
@@ -1211,6 +1212,62 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     if ((rc = launch_step(h, io, a->human_policy)) != EBC_OK) return rc;
   }
   if (a->location != EBC_DEVICE) return st.finish();
+  return EBC_OK;
+}
+
+// K closed-loop steps of the attached SAIL network with the ORCA robot labelling every state (csrc/ebc_dagger.h): per
+// step the label kernel, the network, the select and the step, four launches.
+int ebc_sail_dagger_k(void *handle, const EbcSailDaggerArgs *a) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!a || a->struct_size != sizeof(EbcSailDaggerArgs)) return fail(EBC_ERR_INVALID, "EbcSailDaggerArgs.struct_size");
+  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k: the handle reported a mailbox fault; ebc_reset re-arms it");
+  if ((rc = refuse_capture(h, "ebc_sail_dagger_k")) != EBC_OK) return rc;
+  if (a->K < 1) return fail(EBC_ERR_INVALID, "K");
+  if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL)
+    return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
+  if (!h->sail_P) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k: no network attached (ebc_robot_sail)");
+  if ((rc = check_robot_orca(h, a->expert_safety_space)) != EBC_OK) return rc;
+  if (a->flags & EBC_FLAG_BORDER) return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_dagger_k: no border");
+  if (a->flags & EBC_FLAG_ONE_LAUNCH)
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_dagger_k: EBC_FLAG_ONE_LAUNCH (the labelled rollout has the per-step form only)");
+  if (a->flags & ~EBC_FLAG_AUTO_RESET) return fail(EBC_ERR_INVALID, "flags");
+  if (!a->robot || !a->ob || !a->n_rows || !a->learner_action || !a->expert_action || !a->robot_action_out)
+    return fail(EBC_ERR_INVALID, "ebc_sail_dagger_k: a required output is NULL (robot, ob, n_rows, learner_action, expert_action, robot_action_out)");
+  const size_t E = h->s.E, R = h->s.N + h->s.S, K = (size_t)a->K;
+  const int gs = group_size_for((int)R);
+  const int epw = EBC_WAVE / gs;
+  const unsigned label_blocks = (unsigned)((E + epw - 1) / epw);
+  const unsigned select_blocks = (unsigned)((2 * E + 255) / 256);
+  for (size_t k = 0; k < K; ++k) {
+    double *robot = a->robot + k * E * 9, *ob = a->ob + k * E * R * 5;
+    long long *rows = a->n_rows + k * E;
+    double *learner = a->learner_action + k * E * 2, *expert = a->expert_action + k * E * 2, *act = a->robot_action_out + k * E * 2;
+    rc = with_group_size<kDevRobotGs>(gs, [&](auto g) -> int {
+      hipLaunchKernelGGL((ebc::dagger_label_kernel<decltype(g)::value>), dim3(label_blocks), dim3(EBC_WAVE), 0, h->stream, h->p, h->s,
+                         a->expert_safety_space, h->robot_sim, robot, ob, rows, expert);
+      HIP_TRY(hipGetLastError());
+      return EBC_OK;
+    });
+    if (rc != EBC_OK) return rc;
+    // the network reads the step's records where the label kernel left them
+    if ((rc = ebc_sail_api::launch(h->sail_P, h->sail_N, h->stream, robot, ob, rows, learner, nullptr, (int)E, (int)R)) != EBC_OK) return rc;
+    hipLaunchKernelGGL(ebc::dagger_select_kernel, dim3(select_blocks), dim3(256), 0, h->stream, (int)E,
+                       a->take_expert ? a->take_expert + k * E : nullptr, reinterpret_cast<const unsigned long long *>(learner),
+                       reinterpret_cast<const unsigned long long *>(expert), reinterpret_cast<unsigned long long *>(act));
+    HIP_TRY(hipGetLastError());
+    StepIO io;
+    memset(&io, 0, sizeof(io));
+    io.auto_reset = (a->flags & EBC_FLAG_AUTO_RESET) ? 1 : 0;
+    io.robot_policy = EBC_ROBOT_EXTERNAL;
+    io.robot_action = act;
+    io.reward = a->reward ? a->reward + k * E : nullptr;
+    io.done = a->done ? a->done + k * E : nullptr;
+    io.info = a->info ? a->info + k * E : nullptr;
+    if ((rc = launch_step(h, io, a->human_policy)) != EBC_OK) return rc;
+  }
   return EBC_OK;
 }
 

@@ -229,3 +229,13 @@ class EbcSailGradArgs(C.Structure):
     -> grad float32 [packed_floats], loss_sum float64 [1], count int64 [1], action [E][2] float64 or NULL)."""
     _fields_ = [("struct_size", C.c_uint32), ("E", C.c_int32), ("R", C.c_int32), ("grad_scale", C.c_float)] + [
         (k, C.c_void_p) for k in ("robot", "ob", "n_rows", "target", "sample_mask", "grad", "loss_sum", "count", "action")]
+
+
+class EbcSailDaggerArgs(C.Structure):
+    """include/ebcsim.h: one ebc_sail_dagger_k (K closed-loop steps of the attached SAIL network, the ORCA robot labelling
+    every state; device pointers: take_expert [K][E] uint8 or NULL -> robot [K][E][9], ob [K][E][R][5], n_rows [K][E],
+    learner_action / expert_action / robot_action_out [K][E][2], and reward / done / info [K][E] or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("K", C.c_int32), ("human_policy", C.c_int32), ("flags", C.c_int32),
+                ("expert_safety_space", C.c_double)] + [
+        (k, C.c_void_p) for k in ("take_expert", "robot", "ob", "n_rows", "learner_action", "expert_action",
+                                  "robot_action_out", "reward", "done", "info")]

@@ -83,6 +83,7 @@ SYMBOLS = {
     "ebc_sail_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ebc_sail_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_sail_dagger_k": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 

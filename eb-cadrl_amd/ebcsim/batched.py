@@ -483,6 +483,50 @@ class BatchedEnv:
                                  None if robot_action is None else robot_action.data_ptr())
         _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
 
+    _DAGGER_SHAPES = staticmethod(lambda E, R: dict(
+        robot=((E, 9), "float64"), ob=((E, R, 5), "float64"), n_rows=((E,), "int64"), learner_action=((E, 2), "float64"),
+        expert_action=((E, 2), "float64"), robot_action_out=((E, 2), "float64"), reward=((E,), "float64"),
+        done=((E,), "uint8"), info=((E,), "uint8")))
+    _DAGGER_REQUIRED = ("robot", "ob", "n_rows", "learner_action", "expert_action", "robot_action_out")
+
+    def alloc_sail_dagger_outputs(self, K, optional=("reward", "done", "info")):
+        """torch CUDA tensors [K, ...] for sail_dagger_k_device(): the six required outputs of ebc_sail_dagger_k and the
+        listed optional ones; the caller owns them."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        shapes = self._DAGGER_SHAPES(self.E, self.R)
+        for k in optional:
+            if k not in ("reward", "done", "info"):
+                raise ValueError("optional outputs are reward, done, info; got %r" % (k,))
+        return {k: torch.zeros((int(K),) + shapes[k][0], dtype=getattr(torch, shapes[k][1]), device=dev)
+                for k in self._DAGGER_REQUIRED + tuple(optional)}
+
+    def sail_dagger_k_device(self, outputs, K, take_expert=None, safety_space=0.15, human_policy=_abi.HUMAN_ORCA, flags=0):
+        """Enqueue K closed-loop steps of the attached SAIL network with the ORCA robot (safety_space) labelling every
+        state (ebc_sail_dagger_k), writing into torch CUDA tensors [K, ...] (not copied).  take_expert: uint8 / bool
+        [K, E] on the device, nonzero where the step executes the expert's action; None: the network always acts."""
+        import torch
+        shapes = self._DAGGER_SHAPES(self.E, self.R)
+        args = _abi.EbcSailDaggerArgs()
+        args.struct_size = C.sizeof(args)
+        args.K, args.human_policy, args.flags = int(K), int(human_policy), int(flags)
+        args.expert_safety_space = float(safety_space)
+        for k, t in outputs.items():
+            if k not in shapes:
+                raise ValueError("unknown output %r" % (k,))
+            if t is None:
+                continue
+            if (tuple(t.shape) != (int(K),) + shapes[k][0] or t.dtype != getattr(torch, shapes[k][1]) or not t.is_contiguous()
+                    or not t.is_cuda):
+                raise ValueError("%s must be a contiguous %s %r tensor on the device" % (k, shapes[k][1], (int(K),) + shapes[k][0]))
+            setattr(args, k, t.data_ptr())
+        if take_expert is not None:
+            if (tuple(take_expert.shape) != (int(K), self.E) or take_expert.dtype.itemsize != 1 or not take_expert.is_cuda
+                    or not take_expert.is_contiguous()):
+                raise ValueError("take_expert must be a contiguous uint8 or bool [K, E] tensor on the device")
+            args.take_expert = take_expert.data_ptr()
+        _capi.check(self._L.ebc_sail_dagger_k(self._h, C.addressof(args)))
+
     def alloc_lookahead_outputs(self, n_actions, keys=("reward", "done", "info", "rows_rotated")):
         """torch CUDA tensors for lookahead_device(); the caller owns them."""
         import torch

@@ -9,7 +9,11 @@ loss and gradient with torch's autograd on SailModule: the comparison path, and 
 
 The loss is a plain regression on the demonstrator's action: mean squared error over the live envs' two outputs.  An env
 is live (w_e = 1) unless it has arrived (SAIL's action is the constant (0, 0) there), its row count is not adult_num, or
-its mask is 0; an env that is not live enters nothing."""
+its mask is 0; an env that is not live enters nothing.
+
+After the behaviour cloning, DAgger (collect_dagger, DaggerDataset, dagger): the network drives the training envs, the ORCA
+robot labels every state it visits in one ebc_sail_dagger_k call per round (csrc/ebc_dagger.h), and the fit runs on the
+aggregate."""
 import collections
 import ctypes as C
 
@@ -267,3 +271,117 @@ def fit(trainer, demos, epochs, batch_size, generator=None):
 def train_sail(env, trainer, demo_steps, epochs, batch_size, generator=None, safety_space=0.15, persistent_sim=True):
     """Demonstrations from `env`, then the fit -> the per-epoch mean losses."""
     return fit(trainer, collect_sail_demos(env, demo_steps, safety_space, persistent_sim), epochs, batch_size, generator)
+
+
+# ---------------------------------------------------------------------- DAgger (Ross, Gordon and Bagnell 2011)
+# Behaviour cloning sees the demonstrator's own states only.  A DAgger round lets the LEARNER drive (mixed with the expert
+# with probability beta), has the expert label every state the learner visits, adds those to the aggregate and fits again.
+
+def dagger_beta(round_index, beta0=0.5, beta_decay=0.5):
+    """The probability that a step of round i >= 1 executes the expert's action: beta0 * beta_decay ** (i - 1)."""
+    if round_index < 1:
+        raise ValueError("round 0 is behaviour cloning: the expert drives every step")
+    return float(beta0) * float(beta_decay) ** (int(round_index) - 1)
+
+
+def dagger_mask(steps, n_envs, beta, device, generator=None):
+    """take_expert [K, E] bool on `device`: torch.rand < beta from the generator (reproducible from its seed); None at
+    beta <= 0 (the learner always acts, the entry's NULL)."""
+    if not beta > 0.0:
+        return None
+    return torch.rand((int(steps), int(n_envs)), device=device, generator=generator) < float(beta)
+
+
+def collect_dagger(env, steps, beta, generator=None, safety_space=0.15, human_policy=_abi.HUMAN_ORCA):
+    """One DAgger window: `steps` closed-loop steps of every env of a BatchedEnv (HIP device, auto-reset) in ONE
+    ebc_sail_dagger_k call — the network attached to `env` drives, a step executes the expert's action instead with
+    probability beta, and the ORCA robot labels every visited state.  Kept: the samples whose env is live (live_envs:
+    not arrived, adult_num rows) and whose expert action is finite; there is no ReachGoal filter, the states where the
+    learner went wrong are the point.
+    -> the dict of collect_sail_demos (robot [M, 9], ob [M, R, 5], n_rows [M], target [M, 2] = the expert's action,
+    steps, episodes) plus executed [M, 2], learner [M, 2], `window` = the [K, E, ...] outputs and `take_expert` as the
+    call had them, `keep` [K * E] bool, and the window's outcome counts success / collision / timeout."""
+    if int(env.params.robot_kinematics) != _abi.HOLONOMIC:
+        raise NotImplementedError("collect_dagger: holonomic robots only: the expert's action is (vx, vy)")
+    net = getattr(env, "_sail", None)
+    if net is None:
+        raise ValueError("collect_dagger: no SAIL network attached to the env (BatchedEnv.attach_sail)")
+    dev = torch.device("cuda", env.device)
+    K, E, R = int(steps), env.E, env.R
+    out = env.alloc_sail_dagger_outputs(K)
+    take = dagger_mask(K, E, beta, dev, generator)
+    # the mask and the trainer's last weights are work of torch's stream; the handle's stream may be another
+    torch.cuda.current_stream(dev).synchronize()
+    env.sail_dagger_k_device(out, K, take_expert=take, safety_space=safety_space, human_policy=human_policy,
+                             flags=_abi.FLAG_AUTO_RESET)
+    env.synchronize()
+    robot, n_rows, expert = out["robot"].reshape(K * E, 9), out["n_rows"].reshape(-1), out["expert_action"].reshape(K * E, 2)
+    keep = live_envs(robot, n_rows, None, net.adult_num) & torch.isfinite(expert).all(dim=1)
+    done, info = out["done"].bool(), out["info"]
+    collision = (info >= _abi.INFO_COLLISION_OBSTACLE) & (info <= _abi.INFO_COLLISION_CHILD)
+    return dict(robot=robot[keep], ob=out["ob"].reshape(K * E, R, 5)[keep], n_rows=n_rows[keep], target=expert[keep],
+                executed=out["robot_action_out"].reshape(K * E, 2)[keep], learner=out["learner_action"].reshape(K * E, 2)[keep],
+                steps=int(keep.sum()), episodes=int(done.sum()), success=int((done & (info == _abi.INFO_REACH_GOAL)).sum()),
+                collision=int((done & collision).sum()), timeout=int((done & (info == _abi.INFO_TIMEOUT)).sum()),
+                keep=keep, window=out, take_expert=take)
+
+
+_SAMPLE_KEYS = ("robot", "ob", "n_rows", "target")
+
+
+class DaggerDataset(object):
+    """The aggregate of DAgger: samples appended in order, on whatever device they arrive on; past `capacity` samples the
+    oldest leave first (FIFO)."""
+
+    def __init__(self, capacity):
+        if int(capacity) < 1:
+            raise ValueError("capacity >= 1")
+        self.capacity = int(capacity)
+        self.data = None
+
+    def __len__(self):
+        return 0 if self.data is None else int(self.data["robot"].shape[0])
+
+    def append(self, samples):
+        new = {k: samples[k] for k in _SAMPLE_KEYS}
+        if self.data is not None:
+            new = {k: torch.cat([self.data[k], new[k]], dim=0) for k in _SAMPLE_KEYS}
+        n = int(new["robot"].shape[0])
+        if n > self.capacity:
+            new = {k: v[n - self.capacity:].clone() for k, v in new.items()}  # a copy: the dropped samples' memory goes
+        self.data = new
+        return len(self)
+
+    def as_demos(self):
+        """The dict fit() takes."""
+        if self.data is None:
+            raise ValueError("the dataset is empty")
+        return dict(self.data, steps=len(self))
+
+
+def dagger(env, trainer, rounds, demo_steps, dagger_steps, epochs, dagger_epochs, batch_size, beta0=0.5, beta_decay=0.5,
+           capacity=1 << 20, generator=None, safety_space=0.15, on_round=None, persistent_sim=True):
+    """Round 0: collect_sail_demos + fit, exactly train_sail.  Round i >= 1: collect_dagger at beta0 * beta_decay^(i - 1)
+    on `env` (the env trainer.net is attached to: SailTrainer.step has already handed it the new weights), append to the
+    aggregate, fit on all of it for dagger_epochs.  on_round(i, info) runs after every round's fit; info holds round,
+    beta, losses, samples (this round's), aggregate, episodes and, from round 1 on, the window's outcome counts.
+    -> (per-round list of the per-epoch losses, the DaggerDataset).  rounds = 0 is train_sail."""
+    data = DaggerDataset(capacity)
+    demos = collect_sail_demos(env, demo_steps, safety_space, persistent_sim)
+    if int(rounds) > 0:
+        data.append(demos)
+    losses = [fit(trainer, demos, epochs, batch_size, generator)]
+    if on_round is not None:
+        on_round(0, dict(round=0, beta=1.0, losses=losses[0], samples=demos["steps"], aggregate=demos["steps"],
+                         episodes=demos["episodes"]))
+    for i in range(1, int(rounds) + 1):
+        env.attach_sail(trainer.net)
+        beta = dagger_beta(i, beta0, beta_decay)
+        got = collect_dagger(env, dagger_steps, beta, generator, safety_space)
+        data.append(got)
+        losses.append(fit(trainer, data.as_demos(), dagger_epochs, batch_size, generator))
+        if on_round is not None:
+            on_round(i, dict(round=i, beta=beta, losses=losses[-1], samples=got["steps"], aggregate=len(data),
+                             episodes=got["episodes"], success=got["success"], collision=got["collision"],
+                             timeout=got["timeout"]))
+    return losses, data

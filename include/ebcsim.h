@@ -759,6 +759,45 @@ int ebc_sail_get_packed(void *sail, void *stream, float *dst_dev);
  * image, not a copy): its next enqueued ebc_step_k decides with them.  Work on other streams is not ordered with it. */
 int ebc_sail_set_packed(void *sail, void *stream, const float *src_dev);
 
+
+/* ---- DAgger for the SAIL network (Ross, Gordon and Bagnell 2011): K closed-loop steps in which the attached network
+ * (ebc_robot_sail) drives while the ORCA robot of ebc_robot_orca labels every state the network visits, recorded as the
+ * dataset ebc_sail_grad trains on.  Device pointers only; everything is enqueued on the handle's stream.  Per step k:
+ *   1. robot[k], ob[k], n_rows[k] receive the bytes ebc_get_state (robot), ebc_observe (ob: the static rows too, zeros
+ *      for rows that do not exist) and ebc_row_counts give on the current state;
+ *   2. expert_action[k] receives the bytes of ebc_robot_orca(handle, expert_safety_space, ...) on that state; the
+ *      persistent simulators of ebc_robot_orca_sim are left as one ebc_robot_orca call per step leaves them;
+ *   3. learner_action[k] receives the bytes of ebc_sail_forward reading robot[k], ob[k], n_rows[k] in place (its arrival
+ *      rule and its NaN action for a row count other than adult_num unchanged);
+ *   4. robot_action_out[k][e] = take_expert[k][e] ? expert_action[k][e] : learner_action[k][e], chosen as bits, never
+ *      arithmetic: a NaN of the side not taken reaches nothing;
+ *   5. ebc_step takes that action with `flags` and writes the optional outputs at index k.
+ * Steps 1 and 2 are one kernel that reads the state once; a step is four launches (label, network, select, step).
+ * Refused before anything is enqueued, nothing written, the state untouched: no network attached (EBC_ERR_STATE); a
+ * unicycle robot or max_humans + max_static > 32 (EBC_ERR_UNSUPPORTED, as ebc_robot_orca); EBC_FLAG_ONE_LAUNCH or
+ * EBC_FLAG_BORDER (EBC_ERR_UNSUPPORTED: the labelled rollout has the per-step form only); a stream under capture
+ * (EBC_ERR_UNSUPPORTED); K < 1, a NULL required output, a wrong struct_size, a negative or NaN safety space
+ * (EBC_ERR_INVALID); before ebc_reset or on a faulted handle as ebc_step_k (EBC_ERR_STATE). */
+typedef struct EbcSailDaggerArgs {
+  uint32_t struct_size;
+  int32_t K;                     /* steps, >= 1 */
+  int32_t human_policy;          /* as ebc_step_k */
+  int32_t flags;                 /* EBC_FLAG_AUTO_RESET or 0 */
+  double expert_safety_space;    /* the ORCA robot's safety_space, >= 0 */
+  const uint8_t *take_expert;    /* device [K][E], or NULL = the learner always acts;
+                                    != 0: step k of env e executes the expert's action */
+  /* required outputs, device pointers */
+  double *robot;                 /* [K][E][9]    FullState before step k (ebc_get_state's robot) */
+  double *ob;                    /* [K][E][R][5] world-frame rows before step k (ebc_observe's ob) */
+  long long *n_rows;             /* [K][E]       (ebc_row_counts) */
+  double *learner_action;        /* [K][E][2]    ebc_sail_forward on robot[k], ob[k], n_rows[k] */
+  double *expert_action;         /* [K][E][2]    ebc_robot_orca on the same state */
+  double *robot_action_out;      /* [K][E][2]    the action the step took */
+  /* optional outputs */
+  double *reward; uint8_t *done; uint8_t *info;   /* [K][E] each, or NULL */
+} EbcSailDaggerArgs;
+int ebc_sail_dagger_k(void *handle, const EbcSailDaggerArgs *args);
+
 #ifdef __cplusplus
 }
 #endif

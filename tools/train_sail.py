@@ -6,6 +6,13 @@ evaluation tools/evaluate.py --policy sail runs on the test cases, with the refe
 
     python3 tools/train_sail.py --env-config ENV_WITH_ADULT_NUM_ROWS --device-scenes [--envs 1024] [--demo-steps 120]
                                 [--epochs 50] [--batch-size 1024] [--lr 1e-3] [--cases 500] [--out sail_model.pth]
+                                [--dagger-rounds N] [--dagger-steps 60] [--dagger-epochs 10] [--beta0 0.5] [--beta-decay 0.5]
+                                [--capacity 1000000]
+
+--dagger-rounds N > 0 continues with N rounds of DAgger (ebcsim.sail_train.dagger): the network drives the training envs
+(mixed with the demonstrator with probability beta0 * beta_decay^(i - 1)), the demonstrator labels every state it
+visits in one ebc_sail_dagger_k call per round, and the fit runs on the aggregate.  The closing evaluation then runs after
+every round (round 0 = the behaviour-cloning baseline of the same run) and the JSON line gains the per-round list.
 
 The env config's scenes must have exactly adult_num rows each (the network takes no other count)."""
 import argparse
@@ -36,6 +43,12 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.9)
     ap.add_argument("--autograd", action="store_true", help="torch autograd instead of the kernel (the comparison path)")
     ap.add_argument("--out", default="sail_model.pth")
+    ap.add_argument("--dagger-rounds", type=int, default=0, help="rounds of DAgger after the behaviour cloning (0: none)")
+    ap.add_argument("--dagger-steps", type=int, default=60, help="steps of every env per DAgger round")
+    ap.add_argument("--dagger-epochs", type=int, default=10, help="passes over the aggregate per DAgger round")
+    ap.add_argument("--beta0", type=float, default=0.5, help="probability that a step of round 1 executes the expert's action")
+    ap.add_argument("--beta-decay", type=float, default=0.5, help="factor on that probability from round to round")
+    ap.add_argument("--capacity", type=int, default=1000000, help="samples the aggregate keeps (the oldest leave first)")
     args = ap.parse_args()
     if not args.device_scenes:
         ap.error("--device-scenes is required: demonstrations restart from a pool of device-generated scenes")
@@ -43,7 +56,7 @@ def main():
     from ebcsim import _abi, config as ebc_config, scene as ebc_scene
     from ebcsim.batched import BatchedEnv
     from ebcsim.sail import DeviceSailPolicy, SailModule, SailNet
-    from ebcsim.sail_train import SailTrainer, collect_sail_demos, fit
+    from ebcsim.sail_train import SailTrainer, collect_sail_demos, dagger, fit
     from ebcsim.train import evaluate
     cfg, pol = configparser.RawConfigParser(), configparser.RawConfigParser()
     cfg.read(args.env_config)
@@ -55,11 +68,61 @@ def main():
     if ebc_scene.max_static_rows(sc):
         ap.error("the env config has static rows: SAIL takes exactly adult_num rows per scene")
     E = args.envs
+    test = ebc_scene.gen_struct(sc, "test")
+
+    def evaluate_saved():
+        """what tools/evaluate.py --policy sail --device-scenes runs, on the file just saved -> the metrics, printed"""
+        env = BatchedEnv(params, args.cases, sum(test.count), 0)
+        env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
+        env.synchronize()
+        env.use_torch_stream()
+        policy = DeviceSailPolicy(SailNet.load(args.out, device="cuda:0"))
+        m = evaluate(env, lambda e: policy.decide(e)[0], args.gamma, human_policy=_abi.HUMAN_ORCA)
+        torch.cuda.synchronize()
+        env.close()
+        print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
+              "timeout: %d, nav time: %.2f, total reward: %.4f" % (
+                  m["success_rate"], m["collision_rate_adult"], m["collision_rate_bicycle"], m["collision_rate_child"],
+                  m["collision_rate_obstacle"], m["timeout"], m["avg_nav_time"], m["total_reward:"]))
+        print("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f" % (
+            m["Frequency of being in danger"] or 0.0, m["average min separate distance in danger"]))
+        return {k: v for k, v in m.items() if not isinstance(v, list)}
+
     env = BatchedEnv(params, E, N, 0)
     env.use_torch_stream()
     seed0 = ebc_scene.COUNTER_OFFSET["train"]
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 4 * E)
+    if args.dagger_rounds > 0:
+        torch.manual_seed(args.seed)
+        trainer = SailTrainer(SailModule(N), device="cuda:0", optimizer="adam", lr=args.lr, native=not args.autograd)
+        per_round = []
+
+        def on_round(i, info):
+            torch.cuda.synchronize()
+            trainer.save(args.out)
+            print("round %d: beta %.3f, %d episodes ended in the window%s, %d samples kept, aggregate %d; mean squared error "
+                  "first %.6f, last %.6f; saved %s" % (
+                      i, info["beta"], info["episodes"],
+                      "" if i == 0 else " (%d success, %d collision, %d timeout)" % (info["success"], info["collision"], info["timeout"]),
+                      info["samples"], info["aggregate"], info["losses"][0], info["losses"][-1], args.out))
+            row = {k: v for k, v in info.items() if k != "losses"}
+            row.update(losses=[info["losses"][0], info["losses"][-1]], metrics=evaluate_saved())
+            per_round.append(row)
+
+        t0 = time.perf_counter()
+        dagger(env, trainer, args.dagger_rounds, args.demo_steps, args.dagger_steps, args.epochs, args.dagger_epochs, args.batch_size,
+               beta0=args.beta0, beta_decay=args.beta_decay, capacity=args.capacity,
+               generator=torch.Generator(device="cuda:0").manual_seed(args.seed), safety_space=args.safety_space, on_round=on_round)
+        torch.cuda.synchronize()
+        print("%d rounds of DAgger after the behaviour cloning in %.2f s (the evaluations included)" % (args.dagger_rounds, time.perf_counter() - t0))
+        env.close()
+        print(json.dumps({"envs": E, "demo_steps": args.demo_steps, "kept": per_round[0]["samples"], "epochs": args.epochs,
+                          "losses": per_round[0]["losses"], "cases": args.cases, "metrics": per_round[-1]["metrics"],
+                          "dagger": {"rounds": args.dagger_rounds, "steps": args.dagger_steps, "epochs": args.dagger_epochs,
+                                     "beta0": args.beta0, "beta_decay": args.beta_decay, "capacity": args.capacity},
+                          "rounds": per_round}))
+        return
     t0 = time.perf_counter()
     demos = collect_sail_demos(env, args.demo_steps, args.safety_space)
     torch.cuda.synchronize()
@@ -77,23 +140,9 @@ def main():
              losses[0], losses[-1]))
     trainer.save(args.out)
     print("saved %s" % args.out)
-    # what tools/evaluate.py --policy sail --device-scenes runs
-    test = ebc_scene.gen_struct(sc, "test")
-    env = BatchedEnv(params, args.cases, sum(test.count), 0)
-    env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
-    env.synchronize()
-    env.use_torch_stream()
-    policy = DeviceSailPolicy(SailNet.load(args.out, device="cuda:0"))
-    m = evaluate(env, lambda e: policy.decide(e)[0], args.gamma, human_policy=_abi.HUMAN_ORCA)
-    torch.cuda.synchronize()
-    print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
-          "timeout: %d, nav time: %.2f, total reward: %.4f" % (
-              m["success_rate"], m["collision_rate_adult"], m["collision_rate_bicycle"], m["collision_rate_child"],
-              m["collision_rate_obstacle"], m["timeout"], m["avg_nav_time"], m["total_reward:"]))
-    print("Frequency of being in danger: %.2f and average min separate distance in danger: %.2f" % (
-        m["Frequency of being in danger"] or 0.0, m["average min separate distance in danger"]))
+    m = evaluate_saved()
     print(json.dumps({"envs": E, "demo_steps": args.demo_steps, "kept": demos["steps"], "epochs": args.epochs, "losses": [losses[0], losses[-1]],
-                      "cases": args.cases, "metrics": {k: v for k, v in m.items() if not isinstance(v, list)}}))
+                      "cases": args.cases, "metrics": m}))
 
 
 if __name__ == "__main__":
