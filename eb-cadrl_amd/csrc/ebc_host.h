@@ -18,6 +18,17 @@ inline int fail(int code, const std::string &msg) {
   return code;
 }
 
+// A launch gets 64 KB of dynamic LDS by default; a kernel that needs more has that raised as a function attribute, which
+// is per device: done when a launch asks for more than this kernel has on that device so far.
+template <class Kernel>
+hipError_t raise_dynamic_lds(Kernel *kernel, int device, size_t lds, size_t (&raised)[64]) {
+  size_t &have = raised[device & 63];
+  if (lds <= 65536 || lds <= have) return hipSuccess;
+  const hipError_t err = hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (err == hipSuccess) have = lds;
+  return err;
+}
+
 }  // namespace ebc_host
 
 #define HIP_TRY(x)                                                                                    \

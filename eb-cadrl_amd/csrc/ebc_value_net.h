@@ -30,27 +30,22 @@ namespace ebc {
 // between — and double-buffered: while the waves work on hidden tile u from one buffer, tile u + 1
 // arrives in the other.  (With the weights coming from L2 per wave and per k-step a wave spent nine
 // tenths of its time waiting for them.)
-// NW waves per workgroup: 8 (two per SIMD sharing one copy of the weights) when the tiles fit 256
-// registers and the double buffer is too big for two workgroups per CU; else 4 (two workgroups per CU when
-// LDS allows, one wave per SIMD with up to 512 registers when the tiles need them).
-// LEAN: the L2 halves share ONE LDS slot (staged at the start of the hidden phase of their own tile) instead of
-// two: 2 A + B instead of 2 A + 2 B bytes, which lets TWO independent 4-wave workgroups live on a CU where one
-// lock-stepped 8-wave workgroup did (the 17 -> 300 -> 200 shape, whose full layout already fits twice, is the most
-// efficient of the three for that reason: its two workgroups drift apart and fill each other's waits).
-// LEAN 2: ONE slot for the L1 halves too (A | B): every half is staged one phase ahead into the slot the barrier just
-// passed has freed; for the shape whose lean layout is still too big to fit a CU twice (7 + 7 tiles).
+// The waves per workgroup (NW: 4 or 8) and the LDS layout (full: both halves of a hidden tile's weights double-buffered;
+// LEAN: the L2 halves share ONE slot, staged at the start of the hidden phase of their own tile) follow from (TI, TO):
+// VnLayout, ebc_vn_layout.h, which the launcher reads too.
 // KIN: the input is at most 32 TI - 16 wide, i.e. the second k-step of its last tile multiplies zeros: left out at
 // compile time (one layer-1 MFMA triple in 2 TI, and the eight registers of that fragment).
-template <int TI, int TO, int NW, bool GROUP, int LEAN = 0, int KIN = 0>
-__global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 : 1)) void mlp2_split_wg_kernel(const float *X, int M, int K0, PackedLayer L1,
-                                                           PackedLayer L2, int relu_out, float *Y, int O, MlpExtra ex) {
+template <int TI, int TO, bool GROUP, int KIN = 0>
+__global__ __launch_bounds__((64 * VnLayout{TI, TO}.nw()), ((VnLayout{TI, TO}.lean() || (TI + TO) * 16 + 64 <= 256) ? 2 : 1))
+void mlp2_split_wg_kernel(const float *X, int M, int K0, PackedLayer L1, PackedLayer L2, int relu_out, float *Y, int O, MlpExtra ex) {
   extern __shared__ uint4 wbuf[];  // weights: A0 | B0 | A1 | B1 (LEAN: A0 | B | A1), then the hidden layer's biases
-  constexpr int PART = 64;                          // uint4 per fragment half (hi or lo) = 1 KB
-  constexpr int A_SIZE = TI * 2 * 2 * PART, B_SIZE = TO * 2 * 2 * PART;  // uint4 per L1 / L2 half
-  constexpr int PER_U = LEAN == 2 ? (A_SIZE + B_SIZE + 1) / 2 : LEAN ? (2 * A_SIZE + B_SIZE + 1) / 2 : A_SIZE + B_SIZE;  // half the weight region, in uint4
-  // uint4 free for the input tiles: from A1 on; LEAN 2 has no idle slot: the whole region, weights staged afterwards
-  constexpr int XCAP = LEAN == 2 ? A_SIZE + B_SIZE : LEAN ? A_SIZE : A_SIZE + B_SIZE;
-  auto off_a = [](int buf) { return (LEAN != 2 && buf) ? A_SIZE + B_SIZE : 0; };
+  constexpr VnLayout LY{TI, TO};
+  constexpr int NW = LY.nw();
+  constexpr bool LEAN = LY.lean();
+  constexpr int PART = 64;  // uint4 per fragment half (hi or lo) = 1 KB
+  constexpr int A_SIZE = LY.a_size(), B_SIZE = LY.b_size();  // uint4 per L1 / L2 half
+  static_assert(A_SIZE == TI * 4 * PART && B_SIZE == TO * 4 * PART, "a fragment: 2 k-steps x hi / lo x PART");
+  auto off_a = [](int buf) { return buf ? A_SIZE + B_SIZE : 0; };
   auto off_b = [](int buf) { return LEAN ? A_SIZE : (buf ? 2 * A_SIZE + B_SIZE : A_SIZE); };
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, col = lane & 31, half = lane >> 5;
   const int m = (blockIdx.x * NW + wave) * 32 + col;
@@ -66,14 +61,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
       const uint4 *src = blk < TI ? L1.frag + ((((size_t)u * TI + blk) * 2 + s) * 2 + part) * PART
                                   : L2.frag + ((((size_t)(blk - TI) * hidden_tiles + u) * 2 + s) * 2 + part) * PART;
       uint4 *dst = wbuf + (which ? off_b(buf) + (size_t)q * PART : off_a(buf) + (size_t)q * PART);
-      // As an asm statement: the builtin makes the compiler drain every outstanding load before the
-      // next LDS read (it cannot tell the two buffers apart), which is the overlap this kernel is
-      // built for.  M0 = the wave-uniform LDS byte address; each lane supplies its source address.
-      unsigned keep;
-      const uint4 *gsrc = src + lane;
-      const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)dst);  // wave-uniform: a scalar register
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+      lds_dma_piece(src, dst, lane);
     }
   };
   // Pipelining across barriers: a phase ends with a COUNTED wait that leaves the stage issued at its start in
@@ -101,12 +89,10 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
   // No ordinary global load inside the loop: while a global_load_lds is in flight the compiler waits
   // for ALL outstanding loads at the next use of a load result, and the overlap would be gone.  The
   // hidden biases therefore wait in LDS.
-  float *hbias = reinterpret_cast<float *>(wbuf + 2 * PER_U);
+  float *hbias = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(wbuf) + LY.weight_bytes());
   for (int q = threadIdx.x; q < hidden_tiles * 32; q += 64 * NW) hbias[q] = L1.bias[q];
-  if (LEAN != 2) {
-    stage_half(0, 0, 0);
-    stage_half(0, 1, 0);
-  }
+  stage_half(0, 0, 0);
+  stage_half(0, 1, 0);
   // the input tile as B fragments, natural k order: element j of k-step s is k = 16 s + 8 half + j
   Frag2 x[TI][2][1];
   if (ex.frag_in) {
@@ -122,7 +108,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
         x[i][s2][0].hi = *reinterpret_cast<const bf16x8 *>(&h);
         x[i][s2][0].lo = *reinterpret_cast<const bf16x8 *>(&l);
       }
-  } else if (TI >= 2 && (K0 & 3) == 0 && (size_t)NW * 32 * EBC_VN_XROW <= (size_t)XCAP * 16) {
+  } else if (LY.rows_through_lds(K0)) {
     // Wide inputs (the 200-float h1 rows of mlp2 / attention) through LDS.  A lane needs ITS row, 8 consecutive
     // floats per k-step: read straight from memory that is 28 16-byte loads per lane at a row stride, every
     // 128-byte line touched by eight different wave instructions with 200+ KB per CU in flight — the lines
@@ -131,7 +117,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
     // one row's 128 bytes (each line exactly once), the wave parks the block in its own LDS tile (row pitch
     // 144 B: the 16-byte reads of 16 lanes then fall in 16 different bank groups) and reads it back row per lane.
     // the tiles live in weight buffer 1: nothing is staged into it before the barrier in front of the loop
-    const LdsF4 xt = (LdsF4)(reinterpret_cast<unsigned char *>(wbuf + (LEAN == 2 ? 0 : A_SIZE + B_SIZE)) + (size_t)wave * 32 * EBC_VN_XROW);
+    const LdsF4 xt = (LdsF4)(reinterpret_cast<unsigned char *>(wbuf + LY.xoff()) + (size_t)wave * 32 * EBC_VN_XROW);
     const int m0 = (blockIdx.x * NW + wave) * 32;
     const int piece = lane & 7, rsub = lane >> 3;
 #pragma unroll
@@ -183,18 +169,9 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
   // (a hidden layer of more than 224 units does not fit a parked row: its lanes load their own terms)
   const bool g_lds = GROUP && (ex.H & 3) == 0 && ex.group_rows > 0 && (31 / ex.group_rows + 2) <= EBC_VN_GROUPS &&
                      Hp * 4 + 16 <= EBC_VN_GROUP_PITCH;
-  const LdsF4 gt = (LdsF4)(reinterpret_cast<unsigned char *>(wbuf) + 2 * (size_t)PER_U * 16 + (size_t)hidden_tiles * 32 * 4 +
+  const LdsF4 gt = (LdsF4)(reinterpret_cast<unsigned char *>(wbuf) + LY.group_offset(hidden_tiles) +
                            (size_t)wave * EBC_VN_GROUPS * EBC_VN_GROUP_PITCH);
-  if (g_lds) {
-    const int first = m0w / ex.group_rows;
-    const int groups_total = (M + ex.group_rows - 1) / ex.group_rows;
-    for (int q = lane; q < EBC_VN_GROUPS * (Hp / 4); q += 64) {
-      const int gq = q / (Hp / 4), c4 = q - gq * (Hp / 4);
-      vn_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (first + gq < groups_total) v = *reinterpret_cast<const vn_f32x4 *>(ex.row_bias + (size_t)(first + gq) * ex.H + 4 * c4);
-      gt[(gq * EBC_VN_GROUP_PITCH) / 16 + c4] = v;
-    }
-  }
+  if (g_lds) park_group_terms(gt, ex, m0w, M, Hp, lane);
   const int g_local = (GROUP && m < M) ? m / ex.group_rows - m0w / ex.group_rows : 0;
   auto group_bias = [&](int u, float4 (&v)[4]) {
 #pragma unroll
@@ -222,14 +199,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
   for (int t = 0; t < TO; ++t) asm volatile("" : "+v"(out[t][0]));
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the compiler does not count the asm loads
   __syncthreads();                                   // tile 0's weights are in; the input tiles (weight buffer 1) are done with
-  if (LEAN == 2) {  // the input tiles had the weight region: tile 0's weights now
-    stage_half(0, 0, 0);
-    stage_half(0, 1, 0);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-  } else if (hidden_tiles > 1) {
-    stage_half(1, 0, 1);                             // tile 1's L1 block: read a whole iteration from now
-  }
+  if (hidden_tiles > 1) stage_half(1, 0, 1);         // tile 1's L1 block: read a whole iteration from now
   // Shapes whose input fragments + output accumulators leave few of the 256 registers two waves per SIMD get
   // (7 + 7 tiles: 224): one hidden accumulator instead of two, output tiles two at a time, the group term
   // read after the hidden MFMAs instead of held across them — the partner wave covers the dependent issue.
@@ -238,11 +208,6 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
   // first half of its last tile, that tile's second k-step multiplies zeros — skipped (200 = 6 tiles + 8: one
   // k-step in 14 of either layer; wave-uniform conditions).
   constexpr bool skip_in = KIN != 0;
-#ifdef EBC_VN_HSKIP  // experiment: the last hidden tile's empty second k-step skipped at run time
-  const int last_full = (ex.H <= 32 * hidden_tiles - 16) ? hidden_tiles - 1 : hidden_tiles;
-#else
-  const int last_full = hidden_tiles;
-#endif
   for (int u = 0; u < hidden_tiles; ++u) {
     const int buf = u & 1;
     // this tile's group term first (its wait, after the first batch of MFMAs below, then also waits for
@@ -291,11 +256,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
     // ---- between the phases: this tile's L2 block (staged during the hidden phase of u - 1) has landed; every
     // wave is done reading this tile's L1 block, so its buffer takes the L1 block of tile u + 2
     phase_end(!LEAN && more1, N_L2);  // LEAN: this tile's L2 block is the newest stage: wait for everything
-    if (LEAN == 2) {
-      if (more1) stage_half(u + 1, 0, 0);  // the one L1 slot is free: next tile's L1 block, due after the output phase
-    } else if (more2) {
-      stage_half(u + 2, 0, buf);
-    }
+    if (more2) stage_half(u + 2, 0, buf);
     f32x16 hid;
 #pragma unroll
     for (int r = 0; r < 16; ++r) hid[r] = TIGHT ? hacc[0][r] : hacc[0][r] + hacc[1][r];
@@ -310,7 +271,6 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
     if (!TIGHT) tile_frags(hid, true, hf);
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
-      if (s == 1 && u >= last_full) continue;
       if (TIGHT) {  // one k-step's fragment at a time: eight registers fewer live across the output MFMAs
         float v[8];
 #pragma unroll
@@ -335,7 +295,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
           if (t0 + c < TO) out[t0 + c][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[c].hi, hf[s].hi, out[t0 + c][0], 0, 0, 0);
       }
     }
-    phase_end(LEAN != 2 && more2, N_L1);  // tile u + 1's L1 block (staged during the output phase of u - 1) has landed
+    phase_end(more2, N_L1);  // tile u + 1's L1 block (staged during the output phase of u - 1) has landed
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
@@ -352,7 +312,7 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
     if (m < M && half == 0) Y[m] = acc + ex.final_b;
     return;
   }
-  if ((O & 3) == 0 && (size_t)NW * 32 * EBC_VN_XROW <= (size_t)PER_U * 2 * 16) {
+  if (LY.has_tile_epilogue(O)) {
     // Rows leave coalesced: an output tile (32 rows x 32 units) is parked in the wave's LDS tile — the weight
     // buffers are free behind the loop's last barrier — and read back with 8 consecutive lanes per row, so
     // every 128-byte line of Y is written by one instruction instead of by eight.
@@ -361,31 +321,13 @@ __global__ __launch_bounds__(64 * NW, ((LEAN || (TI + TO) * 16 + 64 <= 256) ? 2 
     const int piece = lane & 7, rsub = lane >> 3;
     // The row-group sums (MlpExtra.partial).  Lane (col, half) owns unit `col` of the parked tile and walks rows
     // 16 half .. 16 half + 15 down its column: 16 rows meet at most two groups (seg_rows >= 16), so two float64
-    // accumulators and the index of the first row of the second group do; the rows' weights wait, as float64, in the
-    // 16 spare bytes each 144-byte tile row has.  One exchange between the halves per tile and group finishes it.
+    // accumulators and the index of the first row of the second group do; the rows' weights wait, as float64 pairs, in
+    // the 16 spare bytes each 144-byte tile row has (park_row_weights).  One exchange between the halves per tile and
+    // group finishes it.
     const bool reduce = ex.partial != nullptr;
-    typedef float __attribute__((address_space(3))) *LdsF;
-    typedef double __attribute__((address_space(3))) *LdsD;
     const LdsF ytf = (LdsF)yt;
     const LdsD ytd = (LdsD)yt;
-    int seg_lo = 0;
-    if (reduce) {
-      // Row r's weight is parked TWICE in the spare bytes, as the pair (w, 0) if the row belongs to the first group its
-      // 16-row half meets and (0, w) if to the second: the column walk below is then two fused multiply-adds per row
-      // (the product of two float32 is exact in float64, so fma(w, y, a) IS a + w * y) instead of a multiply, two adds
-      // and four 32-bit selects.
-      if (lane < 32) {
-        const int row = m0 + lane, hrow0 = m0 + (lane & 16);
-        const int hnext = (hrow0 / ex.seg_rows + 1) * ex.seg_rows - hrow0;  // rows of this row's half before the next group starts
-        const double w = row < M ? (ex.row_weight ? (double)ex.row_weight[row] : 1.0) : 0.0;
-        const bool first = (lane & 15) < hnext;
-        ytd[(lane * EBC_VN_XROW + 128) / 8] = first ? w : 0.0;
-        ytd[(lane * EBC_VN_XROW + 136) / 8] = first ? 0.0 : w;
-      }
-      const int row0 = m0 + 16 * half, s0 = row0 / ex.seg_rows;
-      seg_lo = s0 - m0 / ex.seg_rows;
-      __builtin_amdgcn_wave_barrier();
-    }
+    const int seg_lo = reduce ? park_row_weights(yt, ex, m0, M, lane) : 0;
     // relu_out as the lower bound of ONE integer max on the bits (0: ReLU; INT_MIN: the value as it is)
     const int relu_lo = relu_out ? 0 : (int)0x80000000;
     auto act = [&](float v) {

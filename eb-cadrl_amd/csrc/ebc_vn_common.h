@@ -1,18 +1,18 @@
-// ebc_vn_common.h — types and fragment helpers shared by the value-network kernels (ebc_value_net.h: the general
-// two-layer block; ebc_vn_stream.h: the streamed attention block).  Conventions: the header of ebc_value_net.h.
+// ebc_vn_common.h — types, fragment helpers, weight staging and the parking of group terms and row weights shared by the
+// value-network kernels (ebc_value_net.h: the general two-layer block; ebc_vn_stream.h: the
+// streamed blocks).  Conventions: the header of ebc_value_net.h.
 #pragma once
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+
+#include "ebc_vn_layout.h"
 
 namespace ebc {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float vn_f32x4 __attribute__((ext_vector_type(4)));
 typedef vn_f32x4 __attribute__((address_space(3))) *LdsF4;  // explicit LDS pointers: no flat-address casts in the loops
-#define EBC_VN_XROW 144  // bytes per row of a wave's input transposition tile: 128 + 16 (conflict-free 16-byte reads)
-#define EBC_VN_GROUPS 4         // group-term rows a wave parks in LDS (its 32 rows span at most that many groups)
-#define EBC_VN_GROUP_PITCH 912  // bytes per parked row: 224 floats + 16
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 struct Frag2 {  // one operand fragment, split
@@ -97,6 +97,55 @@ __device__ __forceinline__ void tile_frags(const f32x16 &acc, bool relu, Frag2 (
     for (int j = 0; j < 8; ++j) v[j] = relu ? relu_bits(acc[8 * s + j]) : acc[8 * s + j];
     out[s] = split8(v);
   }
+}
+
+// ---- pieces shared by the general block (ebc_value_net.h) and the streamed one (ebc_vn_stream.h) -------------------
+typedef float __attribute__((address_space(3))) *LdsF;
+typedef double __attribute__((address_space(3))) *LdsD;
+constexpr int VN_PART = 64;  // uint4 per fragment half (hi or lo) = 1 KB
+
+// One piece (1 KB) of packed weights, global -> LDS without registers (global_load_lds: a wave instruction).  As an asm
+// statement: the builtin makes the compiler drain every outstanding load before the next LDS read (it cannot tell the
+// buffers apart), which is the overlap the kernels are built for.  M0 = the wave-uniform LDS byte address; each lane
+// supplies its source address.
+__device__ __forceinline__ void lds_dma_piece(const uint4 *src, uint4 *dst, int lane) {
+  unsigned keep;
+  const uint4 *gsrc = src + lane;
+  const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)dst);  // wave-uniform: a scalar register
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+}
+
+// The group terms (MlpExtra.row_bias) of the at most EBC_VN_GROUPS groups the wave's 32 rows (from row m0 on) belong to,
+// parked in the wave's LDS rows `gt` (pitch EBC_VN_GROUP_PITCH, Hp = H rounded up to 4 floats each; groups past the last: 0).
+__device__ __forceinline__ void park_group_terms(LdsF4 gt, const MlpExtra &ex, int m0, int M, int Hp, int lane) {
+  const int first = m0 / ex.group_rows;
+  const int groups_total = (M + ex.group_rows - 1) / ex.group_rows;
+  for (int q = lane; q < EBC_VN_GROUPS * (Hp / 4); q += 64) {
+    const int gq = q / (Hp / 4), c4 = q - gq * (Hp / 4);
+    vn_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (first + gq < groups_total) v = *reinterpret_cast<const vn_f32x4 *>(ex.row_bias + (size_t)(first + gq) * ex.H + 4 * c4);
+    gt[(gq * EBC_VN_GROUP_PITCH) / 16 + c4] = v;
+  }
+}
+
+// The row weights of the pair sums (MlpExtra.partial), parked as float64 in the 16 spare bytes each 144-byte row of the
+// wave's LDS tile `yt` has.  Row r's weight is parked TWICE, as the pair (w, 0) if the row belongs to the first group its
+// 16-row half meets and (0, w) if to the second: the column walk of the tile epilogue is then two fused multiply-adds per row
+// (the product of two float32 is exact in float64, so fma(w, y, a) IS a + w * y) instead of a multiply, two adds and four
+// 32-bit selects.  Returns seg_lo: which of the tile's groups the first group of this lane's half is.
+__device__ __forceinline__ int park_row_weights(LdsF4 yt, const MlpExtra &ex, int m0, int M, int lane) {
+  const LdsD ytd = (LdsD)yt;
+  if (lane < 32) {
+    const int row = m0 + lane, hrow0 = m0 + (lane & 16);
+    const int hnext = (hrow0 / ex.seg_rows + 1) * ex.seg_rows - hrow0;  // rows of this row's half before the next group starts
+    const double w = row < M ? (ex.row_weight ? (double)ex.row_weight[row] : 1.0) : 0.0;
+    const bool first = (lane & 15) < hnext;
+    ytd[(lane * EBC_VN_XROW + 128) / 8] = first ? w : 0.0;
+    ytd[(lane * EBC_VN_XROW + 136) / 8] = first ? 0.0 : w;
+  }
+  __builtin_amdgcn_wave_barrier();
+  return (m0 + 16 * (lane >> 5)) / ex.seg_rows - m0 / ex.seg_rows;
 }
 
 template <int I>

@@ -72,8 +72,6 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp2_stream_kernel(int M, PackedLa
   // the wave's parked output tile of the pair-sum epilogue: 32 rows x 144 bytes (128 of the tile + the row's weight pair)
   constexpr size_t GT_BYTES = GROUP ? (size_t)NW * EBC_VN_GROUPS * EBC_VN_GROUP_PITCH : 0;
   const LdsF4 yt = (LdsF4)(reinterpret_cast<unsigned char *>(fwl + TO * 32) + GT_BYTES + (size_t)wave * 32 * EBC_VN_XROW);
-  typedef float __attribute__((address_space(3))) *LdsF;
-  typedef double __attribute__((address_space(3))) *LdsD;
   const LdsF ytf = (LdsF)yt;
   const LdsD ytd = (LdsD)yt;
 #ifdef EBC_VNS_TRACE  // measurement build (tools/vn_stream_timeline.py): per wave and period, the clock before the
@@ -97,11 +95,7 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp2_stream_kernel(int M, PackedLa
       // phase A slab i: pieces (u, s, hi/lo) of L1 [u][i][s][hi/lo]; phase C slab t: L2 [t][u][s][hi/lo], contiguous
       const uint4 *src = p < TI ? L1.frag + ((size_t)(q >> 2) * TI + p) * 4 * PART + (size_t)(q & 3) * PART
                                 : L2.frag + (size_t)(p - TI) * SLAB + (size_t)q * PART;
-      unsigned keep;
-      const uint4 *gsrc = src + lane;
-      const unsigned lds_dst = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(dst + (size_t)q * PART));
-      asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                   : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
+      lds_dma_piece(src, dst + (size_t)q * PART, lane);
     }
   };
   // the wave's input fragments: [row tile][input tile][k-step][hi, lo][lane] (a tile past M reads tile 0: the tensor has
@@ -131,28 +125,9 @@ __global__ __launch_bounds__(64 * NW, 2) void mlp2_stream_kernel(int M, PackedLa
     }
   }
   const int Hp = (ex.H + 3) & ~3;  // floats per parked row
-  int seg_lo = 0;
-  if (!FINAL) {  // the rows' weights, as (w, 0) / (0, w) by the group a row belongs to (the general block's epilogue)
-    if (lane < 32) {
-      const int row = m0w + lane, hrow0 = m0w + (lane & 16);
-      const int hnext = (hrow0 / ex.seg_rows + 1) * ex.seg_rows - hrow0;
-      const double w = row < M ? (ex.row_weight ? (double)ex.row_weight[row] : 1.0) : 0.0;
-      const bool first = (lane & 15) < hnext;
-      ytd[(lane * EBC_VN_XROW + 128) / 8] = first ? w : 0.0;
-      ytd[(lane * EBC_VN_XROW + 136) / 8] = first ? 0.0 : w;
-    }
-    seg_lo = (m0w + 16 * half) / ex.seg_rows - m0w / ex.seg_rows;
-  }
-  if (GROUP) {
-    const int first = m0w / ex.group_rows;
-    const int groups_total = (M + ex.group_rows - 1) / ex.group_rows;
-    for (int q = lane; q < EBC_VN_GROUPS * (Hp / 4); q += 64) {
-      const int gq = q / (Hp / 4), c4 = q - gq * (Hp / 4);
-      vn_f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
-      if (first + gq < groups_total) v = *reinterpret_cast<const vn_f32x4 *>(ex.row_bias + (size_t)(first + gq) * ex.H + 4 * c4);
-      gt[(gq * EBC_VN_GROUP_PITCH) / 16 + c4] = v;
-    }
-  }
+  // the rows' weights of the pair sums, the group terms
+  const int seg_lo = FINAL ? 0 : park_row_weights(yt, ex, m0w, M, lane);
+  if (GROUP) park_group_terms(gt, ex, m0w, M, Hp, lane);
   const int g_local = (GROUP && m < M) ? m / ex.group_rows - m0w / ex.group_rows : -1;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   // ---- prologue: the loads of periods 0 and 1

@@ -4,7 +4,6 @@
 
 #include <cmath>
 #include <cstdio>
-#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -107,64 +106,32 @@ int pack_f32(Mlp2 *m, const float *W, const float *b, int out, int in, ebc::F32L
   return EBC_OK;
 }
 
-template <int TI, int TO, int NW, int LEAN, int KIN>
-int launch_mlp2_kin(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu_out, float *y, const ebc::MlpExtra &ex) {
-  const size_t weights = LEAN == 2 ? (size_t)(TI + TO) * 4096 : LEAN ? (size_t)(2 * TI + TO) * 4096 : 2 * (size_t)(TI + TO) * 4096;
-  const size_t lds = (weights + 31) / 32 * 32 + (size_t)m->L1.out_tiles * 32 * 4 +
-                     (ex.row_bias ? (size_t)NW * EBC_VN_GROUPS * EBC_VN_GROUP_PITCH : 0);  // + the waves' parked group terms
-  static size_t raised_dev[64][2] = {{0}};  // more than the 64 KB a launch gets by default; a function attribute is per device
-  size_t &raised = raised_dev[m->device & 63][ex.row_bias ? 1 : 0];
-  if (lds > 65536 && lds > raised) {
-    if (ex.row_bias)
-      HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_split_wg_kernel<TI, TO, NW, true, LEAN, KIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    else
-      HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_split_wg_kernel<TI, TO, NW, false, LEAN, KIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised = lds;
-  }
-  constexpr int rows = 32 * NW;
-  {  // the row-group sums live in the coalesced-output epilogue (ebc_value_net.h): the block must be one that takes it
-    constexpr size_t a_size = (size_t)TI * 256, b_size = (size_t)TO * 256;
-    constexpr size_t per_u = LEAN == 2 ? (a_size + b_size + 1) / 2 : LEAN ? (2 * a_size + b_size + 1) / 2 : a_size + b_size;
-    if (ex.partial && !((m->O & 3) == 0 && (size_t)NW * 32 * EBC_VN_XROW <= per_u * 2 * 16))
-      return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_reduce: this block shape has no tile epilogue");
-  }
-  const dim3 grid((unsigned)((M + rows - 1) / rows)), block(64 * NW);
-  if (ex.row_bias)
-    hipLaunchKernelGGL((ebc::mlp2_split_wg_kernel<TI, TO, NW, true, LEAN, KIN>), grid, block, lds, st, x, M, m->K0, m->L1, m->L2, relu_out, y, m->O, ex);
-  else
-    hipLaunchKernelGGL((ebc::mlp2_split_wg_kernel<TI, TO, NW, false, LEAN, KIN>), grid, block, lds, st, x, M, m->K0, m->L1, m->L2, relu_out, y, m->O, ex);
+// One (TI, TO, GROUP, KIN) = one kernel: the waves per workgroup, the LDS layout and its bytes are VnLayout's
+// (ebc_vn_layout.h), which the kernel reads too.
+template <int TI, int TO, bool GROUP, int KIN>
+int launch_mlp2_kernel(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu_out, float *y, const ebc::MlpExtra &ex) {
+  constexpr ebc::VnLayout ly{TI, TO};
+  const size_t lds = ly.lds_bytes(m->L1.out_tiles, GROUP);
+  static size_t raised[64] = {0};
+  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::mlp2_split_wg_kernel<TI, TO, GROUP, KIN>, m->device, lds, raised));
+  constexpr int rows = 32 * ly.nw();
+  const dim3 grid((unsigned)((M + rows - 1) / rows)), block(64 * ly.nw());
+  hipLaunchKernelGGL((ebc::mlp2_split_wg_kernel<TI, TO, GROUP, KIN>), grid, block, lds, st, x, M, m->K0, m->L1, m->L2, relu_out, y, m->O, ex);
   HIP_TRY(hipGetLastError());
   return EBC_OK;
 }
 
-// 200-wide inputs (the h1 rows of mlp2 and of the attention stack) end in the first half of their seventh tile
-template <int TI, int TO, int NW, int LEAN>
-int launch_mlp2_shape(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu_out, float *y, const ebc::MlpExtra &ex) {
-  if constexpr (TI == 7) {
-    if (m->K0 <= 32 * TI - 16) return launch_mlp2_kin<TI, TO, NW, LEAN, 1>(m, st, x, M, relu_out, y, ex);
-  }
-  return launch_mlp2_kin<TI, TO, NW, LEAN, 0>(m, st, x, M, relu_out, y, ex);
-}
-
 template <int TI, int TO>
 int launch_mlp2_to(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu_out, float *y, const ebc::MlpExtra &ex) {
-  // Workgroup shape by LDS: the full layout (both halves of the weights double-buffered) twice per CU where it
-  // fits (4 waves each); else the lean layout (one slot for the L2 halves) twice per CU where THAT fits: two
-  // independent 4-wave workgroups fill each other's waits, which one lock-stepped 8-wave workgroup cannot; else
-  // 8 waves sharing one full layout (two waves per SIMD with 256 registers each: measured faster than 4 waves
-  // with 512 for the widest shape, spills included).
-  constexpr size_t full = 2 * (size_t)(TI + TO) * 4096, lean = (size_t)(2 * TI + TO) * 4096, half_cu = 78 * 1024;
-#ifdef EBC_MLP_NO_LEAN
-  constexpr bool use_lean = false;
-#else
-  constexpr bool use_lean = full > half_cu && lean <= half_cu;
-#endif
-  if (use_lean) return launch_mlp2_shape<TI, TO, 4, 1>(m, st, x, M, relu_out, y, ex);
-#ifdef EBC_MLP_LEAN2  // A/B: one slot per half for shapes whose lean layout does not fit twice (7 + 7 tiles)
-  constexpr size_t lean2 = (size_t)(TI + TO) * 4096;
-  if (full > half_cu && lean2 + 16 * 1024 <= half_cu) return launch_mlp2_shape<TI, TO, 4, 2>(m, st, x, M, relu_out, y, ex);
-#endif
-  return launch_mlp2_shape<TI, TO, (full > 80 * 1024 ? 8 : 4), 0>(m, st, x, M, relu_out, y, ex);
+  // the row-group sums live in the coalesced-output epilogue (ebc_value_net.h): the block must be one that takes it
+  if (ex.partial && !ebc::VnLayout{TI, TO}.has_tile_epilogue(m->O))
+    return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_reduce: this block shape has no tile epilogue");
+  // 200-wide inputs (the h1 rows of mlp2 and of the attention stack) end in the first half of their seventh tile
+  if constexpr (TI == 7) {
+    if (m->K0 <= 32 * TI - 16)
+      return ex.row_bias ? launch_mlp2_kernel<TI, TO, true, 1>(m, st, x, M, relu_out, y, ex) : launch_mlp2_kernel<TI, TO, false, 1>(m, st, x, M, relu_out, y, ex);
+  }
+  return ex.row_bias ? launch_mlp2_kernel<TI, TO, true, 0>(m, st, x, M, relu_out, y, ex) : launch_mlp2_kernel<TI, TO, false, 0>(m, st, x, M, relu_out, y, ex);
 }
 
 template <int TI>
@@ -290,17 +257,12 @@ int ebc_mlp2_forward_f32(void *mlp, void *stream, const float *x, int M, int rel
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = (hipStream_t)stream;
   // few rows: a workgroup per 32-row tile, its waves sharing the tile (the form a decision's re-evaluation gets); many
-  // rows: four tiles per workgroup walking the hidden tiles together on weights staged in LDS.  EBCSIM_F32_FORM=1/2
-  // forces the many-/few-row form (measurements).
-  static const int form = [] { const char *e = getenv("EBCSIM_F32_FORM"); return e ? atoi(e) : 0; }();
-  if (form == 2 || (form == 0 && M <= EBC_F32_TILE_ROWS)) {
+  // rows: four tiles per workgroup walking the hidden tiles together on weights staged in LDS.
+  if (M <= EBC_F32_TILE_ROWS) {
     constexpr int NW = 8;
     const size_t tl = ((size_t)((m->K0 + 3) & ~3) * 32 + (size_t)((m->H + 31) / 32) * 1024 + NW * 32) * 4;
     static size_t raised_tile[64] = {0};
-    if (tl > 65536 && tl > raised_tile[m->device & 63]) {
-      HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_tile_kernel<NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tl));
-      raised_tile[m->device & 63] = tl;
-    }
+    HIP_TRY(ebc_host::raise_dynamic_lds(ebc::mlp2_f32_tile_kernel<NW>, m->device, tl, raised_tile));
     hipLaunchKernelGGL((ebc::mlp2_f32_tile_kernel<NW>), dim3((unsigned)((M + 31) / 32)), dim3(NW * 64), tl, st, x, M, m->F1, m->F2,
                        relu_out, y, row_bias, group_rows, (const float *)m->final_w, m->final_b);
     HIP_TRY(hipGetLastError());
@@ -308,19 +270,11 @@ int ebc_mlp2_forward_f32(void *mlp, void *stream, const float *x, int M, int rel
   }
   const size_t lds = ((size_t)((m->K0 + 3) & ~3) * 32 + (size_t)32 * m->F2.out_pad) * 4;  // a hidden tile's W1 columns + W2 rows
   const dim3 grid((unsigned)((M + 127) / 128)), block(256);
-  static size_t raised_dev[64] = {0};  // more than the 64 KB a launch gets by default (per device)
-  if (lds > 65536 && lds > raised_dev[m->device & 63]) {
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<5>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_f32_kernel<7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised_dev[m->device & 63] = lds;
-  }
-#define F32_(T2) hipLaunchKernelGGL((ebc::mlp2_f32_kernel<T2>), grid, block, lds, st, x, M, m->F1, m->F2, relu_out, y, row_bias, \
-                                    group_rows, (const float *)m->final_w, m->final_b)
+  static size_t raised[8][64] = {{0}};  // per output-tile count: a kernel each
+#define F32_(T2)                                                                                                         \
+  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::mlp2_f32_kernel<T2>, m->device, lds, raised[T2]));                            \
+  hipLaunchKernelGGL((ebc::mlp2_f32_kernel<T2>), grid, block, lds, st, x, M, m->F1, m->F2, relu_out, y, row_bias, group_rows, \
+                     (const float *)m->final_w, m->final_b)
   switch ((m->O + 31) / 32) {
     case 1: F32_(1); break;
     case 2: F32_(2); break;

@@ -4,7 +4,6 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdlib>
 
 #include "ebc_vn_stream.h"
 #include "ebc_vn_stream_api.h"
@@ -23,11 +22,8 @@ int launch(int device, hipStream_t st, int M, const ebc::PackedLayer &L1, const 
                          + (size_t)NW * (TI + TO) * 4 * 8
 #endif
       ;
-  static bool raised[64] = {false};  // more than the 64 KB a launch gets by default; a function attribute is per device
-  if (lds > 65536 && !raised[device & 63]) {
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::mlp2_stream_kernel<TI, TH, TO, NW, KIN, KH, GROUP, FINAL, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised[device & 63] = true;
-  }
+  static size_t raised[64] = {0};
+  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::mlp2_stream_kernel<TI, TH, TO, NW, KIN, KH, GROUP, FINAL, ROWS>, device, lds, raised));
   const dim3 grid((unsigned)((M + 32 * NW - 1) / (32 * NW))), block(64 * NW);
   hipLaunchKernelGGL((ebc::mlp2_stream_kernel<TI, TH, TO, NW, KIN, KH, GROUP, FINAL, ROWS>), grid, block, lds, st, M, L1, L2, y, O, ex, relu_out, x, K0);
   HIP_TRY(hipGetLastError());
@@ -48,8 +44,6 @@ int launch_k(int device, hipStream_t st, int M, const ebc::PackedLayer &L1, cons
 
 int vn_stream_launch(int device, hipStream_t st, int M, const ebc::PackedLayer &L1, const ebc::PackedLayer &L2, int K0, int H, int O,
                      float *y, const ebc::MlpExtra &ex, int relu_out, const float *x) {
-  static const bool off = [] { const char *e = getenv("EBCSIM_VN_STREAM"); return e && atoi(e) == 0; }();  // measurements: the general block
-  if (off) return EBC_VN_STREAM_NA;
   // `mlp1` as SarlValueNet calls it: observation rows in, its output as the consumers' fragments and as masked pair sums
   if (!ex.frag_in && x && L1.in_tiles == 1 && K0 > 16 && L1.out_tiles == 10 && L2.out_tiles == 7 && !ex.row_bias && !ex.final_w &&
       ex.partial && !y && !ex.store_y && ex.seg_rows >= 16 && (O & 3) == 0) {

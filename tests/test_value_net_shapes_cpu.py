@@ -1,13 +1,15 @@
 """What the case tables of tests/value_net_cases.py reach: a property of the TABLES, asserted without a GPU.  The
-selector of the two-layer blocks (mlp2_dispatch -> launch_mlp2 -> launch_mlp2_to -> launch_mlp2_shape -> launch_mlp2_kin in
-csrc/ebcsim_value_net.hip, the input paths of mlp2_split_wg_kernel in csrc/ebc_value_net.h, vn_stream_launch in
+selector of the two-layer blocks (mlp2_dispatch -> launch_mlp2 -> launch_mlp2_to -> launch_mlp2_kernel in
+csrc/ebcsim_value_net.hip, the layout of mlp2_split_wg_kernel in csrc/ebc_vn_layout.h, vn_stream_launch in
 csrc/ebcsim_vn_stream.hip) is restated in value_net_cases.py in a few lines; here that restatement is held to a reading
-of the arithmetic in closed form and to the constants in the sources, and the tables to the instantiations, layouts,
+of the arithmetic in closed form, to the layout header's own answers (tests/native/vn_layout_host.cc) and to the
+constants in the sources, and the tables to the instantiations, layouts,
 input paths and selector branches they are there for.  The conditions are requirements on the tables: when one is
 missed, change the table, not the condition.
 
 The counts go to profiles/value_net_shape_coverage.txt."""
 import os
+import subprocess
 from collections import Counter
 
 import numpy as np
@@ -26,19 +28,40 @@ def _src(name):
         return f.read()
 
 
-def test_the_restated_constants_are_the_sources():
-    common, vn, host, stream = _src("ebc_vn_common.h"), _src("ebc_value_net.h"), _src("ebcsim_value_net.hip"), _src("ebcsim_vn_stream.hip")
-    assert "#define EBC_VN_XROW %d " % vc.XROW in common and "#define EBC_VN_GROUPS %d " % vc.VN_GROUPS in common
-    assert "#define EBC_VN_GROUP_PITCH %d " % vc.VN_GROUP_PITCH in common and "Hp * 4 + 16 <= EBC_VN_GROUP_PITCH" in vn
+def _layout_program(tmp_path):
+    """tests/native/vn_layout_host.cc — csrc/ebc_vn_layout.h as the kernel and the launcher compile it — built with g++ as
+    a program of its own under -fsanitize=address,undefined (a finding ends it with a non-zero status); its lines."""
+    exe = str(tmp_path / "vn_layout_host")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-fno-omit-frame-pointer", os.path.join(ROOT, "tests", "native", "vn_layout_host.cc"), "-o", exe], check=True, timeout=300)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0 and "runtime error" not in r.stderr and "Sanitizer" not in r.stderr, (r.stdout + r.stderr)[-4000:]
+    return r.stdout.splitlines()
+
+
+def test_the_restated_constants_are_the_sources(tmp_path):
+    """The layout of the general block — class, waves, input path, tile epilogue — against what csrc/ebc_vn_layout.h itself
+    answers over the whole lattice (every K0 of the input tile; O = 32 TO, 32 (TO - 1) + 4 and 32 TO - 3); the other
+    constants against the lines of the sources that hold them."""
+    vn, host, stream = _src("ebc_value_net.h"), _src("ebcsim_value_net.hip"), _src("ebcsim_vn_stream.hip")
+    lines = _layout_program(tmp_path)
+    assert lines[-1] == "EBC_VN_XROW %d EBC_VN_GROUPS %d EBC_VN_GROUP_PITCH %d" % (vc.XROW, vc.VN_GROUPS, vc.VN_GROUP_PITCH)
+    assert len(lines) == len(LATTICE) + 1
+    for (TI, TO), line in zip(LATTICE, lines):
+        ti, to, cls, nw, weights, xcap, region, lds_plain, lds_group, rows, epi = line.split()
+        assert (int(ti), int(to)) == (TI, TO) and (cls, int(nw)) == vc.layout(TI, TO), line
+        k0s = range(32 * (TI - 1) + 1, 32 * TI + 1)
+        assert rows == "rows=" + "".join("1" if vc.input_path(TI, TO, K0) == "lds" else "0" for K0 in k0s), line
+        assert epi == "epilogue=" + "".join(str(int(vc.tile_epilogue(TI, TO, O))) for O in (32 * TO, 32 * (TO - 1) + 4, 32 * TO - 3)), line
+        # the region the parked tiles take is the weight region; the launch's LDS: + the biases of 7 hidden tiles, + NW waves' group terms
+        assert int(region) == int(weights) == ((2 * TI + TO) * 4096 if cls == "lean" else (TI + TO) * 8192), line
+        assert int(xcap) == (TI * 4096 if cls == "lean" else (TI + TO) * 4096), line
+        assert int(lds_plain) == int(weights) + 7 * 32 * 4 and int(lds_group) == int(lds_plain) + int(nw) * vc.VN_GROUPS * vc.VN_GROUP_PITCH, line
+    assert "Hp * 4 + 16 <= EBC_VN_GROUP_PITCH" in vn
     assert "(ex.H & 3) == 0 && ex.group_rows > 0 && (31 / ex.group_rows + 2) <= EBC_VN_GROUPS" in vn
     assert "#define EBC_F32_TILE_ROWS (1 << 16)" in vn and vc.F32_TILE_ROWS == 1 << 16
     assert "K0 > %d || O > %d || H > %d" % (vc.MAX_IN, vc.MAX_OUT, vc.MAX_HIDDEN) in host
-    assert "full = 2 * (size_t)(TI + TO) * 4096, lean = (size_t)(2 * TI + TO) * 4096, half_cu = 78 * 1024" in host
-    assert "use_lean = full > half_cu && lean <= half_cu" in host and "(full > 80 * 1024 ? 8 : 4)" in host
-    assert "if (m->K0 <= 32 * TI - 16) return launch_mlp2_kin<TI, TO, NW, LEAN, 1>" in host
-    assert "XCAP = LEAN == 2 ? A_SIZE + B_SIZE : LEAN ? A_SIZE : A_SIZE + B_SIZE" in vn
-    assert "TI >= 2 && (K0 & 3) == 0 && (size_t)NW * 32 * EBC_VN_XROW <= (size_t)XCAP * 16" in vn
-    assert "(O & 3) == 0 && (size_t)NW * 32 * EBC_VN_XROW <= (size_t)PER_U * 2 * 16" in vn
+    assert "if constexpr (TI == 7) {\n    if (m->K0 <= 32 * TI - 16)" in host
     assert "L1.in_tiles == 1 && K0 > 16 && L1.out_tiles == 10 && L2.out_tiles == 7" in stream
     assert "kin = K0 <= 32 * 7 - 16, kh = H <= 32 * 7 - 16" in stream and "if (H <= 32 * 10 - 16)" in stream
 

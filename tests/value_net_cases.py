@@ -5,20 +5,20 @@ selector below) that they reach every instantiation, layout, input path and sele
 import numpy as np
 
 # ---- the selector, restated -----------------------------------------------------------------------------------------
-XROW = 144                 # ebc_vn_common.h:13  EBC_VN_XROW
-VN_GROUPS = 4              # ebc_vn_common.h:14  EBC_VN_GROUPS
-VN_GROUP_PITCH = 912       # ebc_vn_common.h:15  EBC_VN_GROUP_PITCH
-F32_TILE_ROWS = 1 << 16    # ebc_value_net.h:623 EBC_F32_TILE_ROWS
-MAX_IN, MAX_HIDDEN, MAX_OUT = 224, 320, 224  # ebcsim_value_net.hip:212 (ebc_mlp2_create_ex)
+XROW = 144                 # ebc_vn_layout.h:10  EBC_VN_XROW
+VN_GROUPS = 4              # ebc_vn_layout.h:11  EBC_VN_GROUPS
+VN_GROUP_PITCH = 912       # ebc_vn_layout.h:12  EBC_VN_GROUP_PITCH
+F32_TILE_ROWS = 1 << 16    # ebc_value_net.h:567 EBC_F32_TILE_ROWS
+MAX_IN, MAX_HIDDEN, MAX_OUT = 224, 320, 224  # ebcsim_value_net.hip:179 (ebc_mlp2_create_ex)
 
 
 def tiles(n):
-    """pack_layer, ebcsim_value_net.hip:49: a dimension in tiles of 32."""
+    """pack_layer, ebcsim_value_net.hip:48: a dimension in tiles of 32."""
     return (n + 31) // 32
 
 
 def layout(TI, TO):
-    """launch_mlp2_to, ebcsim_value_net.hip:156-167 -> (class, NW): "lean" (4 waves) where the full layout does not fit
+    """VnLayout::lean / nw, ebc_vn_layout.h:30-33 -> (class, NW): "lean" (4 waves) where the full layout does not fit
     half a CU's LDS and the lean one does; else the full layout, with 8 waves ("full8") where it is over 80 KB."""
     full, lean, half_cu = 2 * (TI + TO) * 4096, (2 * TI + TO) * 4096, 78 * 1024
     if full > half_cu and lean <= half_cu:
@@ -27,13 +27,14 @@ def layout(TI, TO):
 
 
 def kin(TI, K0):
-    """launch_mlp2_shape, ebcsim_value_net.hip:143-146: the last input tile's second k-step left out."""
+    """launch_mlp2_to, ebcsim_value_net.hip:129-133: the last input tile's second k-step left out."""
     return int(TI == 7 and K0 <= 32 * TI - 16)
 
 
 def input_path(TI, TO, K0, frag_in=False):
-    """mlp2_split_wg_kernel, ebc_value_net.h:112-172: "frag" (the hand-off tensor), "lds" (rows parked in a wave's LDS tile:
-    TI >= 2, 16-byte rows, and XCAP — ebc_value_net.h:52 — holds NW tiles of 32 x XROW bytes) or "lane" (scalar loads)."""
+    """mlp2_split_wg_kernel, ebc_value_net.h:98-158: "frag" (the hand-off tensor), "lds" (rows parked in a wave's LDS tile:
+    VnLayout::rows_through_lds, ebc_vn_layout.h:55 — TI >= 2, 16-byte rows, and xcap, :42, holds NW tiles of 32 x XROW bytes)
+    or "lane" (scalar loads)."""
     if frag_in:
         return "frag"
     cls, NW = layout(TI, TO)
@@ -42,21 +43,22 @@ def input_path(TI, TO, K0, frag_in=False):
 
 
 def tile_epilogue(TI, TO, O):
-    """launch_mlp2_kin, ebcsim_value_net.hip:125-130 / ebc_value_net.h:353: the coalesced epilogue (partial sums, fragments
-    out) exists where O is a multiple of 4 and the weight region holds NW parked tiles."""
+    """VnLayout::has_tile_epilogue, ebc_vn_layout.h:57 (launch_mlp2_to, ebcsim_value_net.hip:126-128 / ebc_value_net.h:315):
+    the coalesced epilogue (partial sums, fragments out) exists where O is a multiple of 4 and the weight region holds NW
+    parked tiles."""
     cls, NW = layout(TI, TO)
     region = (2 * TI + TO) * 4096 if cls == "lean" else (TI + TO) * 8192
     return O % 4 == 0 and NW * 32 * XROW <= region
 
 
 def group_path(H, group_rows):
-    """ebc_value_net.h:181-185: the group terms wait in LDS when H is a multiple of 4, a wave's 32 rows meet at most
+    """ebc_value_net.h:164-171: the group terms wait in LDS when H is a multiple of 4, a wave's 32 rows meet at most
     EBC_VN_GROUPS groups and a parked row holds H floats (H <= 224); else each lane loads its own."""
     return "lds" if H % 4 == 0 and 31 // group_rows + 2 <= VN_GROUPS and H * 4 + 16 <= VN_GROUP_PITCH else "lane"
 
 
 def stream_branch(K0, H, O, frag_in, group, tail, partial, y, frag_out, seg_rows=18, group_rows=18):
-    """vn_stream_launch, ebcsim_vn_stream.hip:49-70 -> None (the general kernel) or (name, KIN, KH)."""
+    """vn_stream_launch, ebcsim_vn_stream.hip:45-64 -> None (the general kernel) or (name, KIN, KH)."""
     ti, th, to = tiles(K0), tiles(H), tiles(O)
     if (not frag_in and ti == 1 and K0 > 16 and th == 10 and to == 7 and not group and not tail and partial and not y
             and seg_rows >= 16 and O % 4 == 0):
@@ -87,7 +89,7 @@ def make_block(K0, H, O, tail=False, seed=None):
 
 def mlp2_ref(x, w, relu_out, row_bias=None, group_rows=0):
     """The block on rows x in float64: relu(x W1' + b1 [+ the row's group term]) W2' + b2, then ReLU when relu_out, or the
-    one-output tail w3 . relu(.) + b3 (which rectifies whatever relu_out says: ebc_value_net.h:340-350)."""
+    one-output tail w3 . relu(.) + b3 (which rectifies whatever relu_out says: ebc_value_net.h:302-313)."""
     f = lambda a: np.asarray(a, dtype=np.float64)  # noqa: E731
     h = f(x) @ f(w["w1"]).T + f(w["b1"])
     if row_bias is not None:
@@ -153,8 +155,8 @@ HIDDEN = (7, 64, 200, 305, 320)   # not a multiple of 4, an exact tile, 7 tiles,
 GROUP_ROWS = (5, 18, 32)
 SEG_ROWS = (16, 18, 32)
 FORMS = ("plain0", "plain1+reduce_y", "group", "tail", "reduce_noy", "group+tail")
-NO_EPILOGUE = "no tile epilogue"  # the refusal of a block of 1 + 1 tiles (ebcsim_value_net.hip:129)
-NEEDS_O4 = "multiple of 4"        # the refusal of the epilogues for an odd O (ebcsim_value_net.hip:345, :363)
+NO_EPILOGUE = "no tile epilogue"  # the refusal of a block of 1 + 1 tiles (ebcsim_value_net.hip:128)
+NEEDS_O4 = "multiple of 4"        # the refusal of the epilogues for an odd O (ebcsim_value_net.hip:299, :317)
 
 
 def k0_edges(TI):

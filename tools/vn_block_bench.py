@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """The attention block alone at the decision's chunk size: the streamed kernel against the general block (same bits),
-microseconds per launch.  EBCSIM_LIB selects an A/B library.   python3 tools/vn_block_bench.py [rows]"""
+microseconds per launch, and a SHA-256 of the scores and of the fragments the first block handed on.  EBCSIM_LIB selects
+an A/B library.   python3 tools/vn_block_bench.py [rows]"""
+import hashlib
 import os
 import sys
 
@@ -37,8 +39,10 @@ def main():
         ev[1].record()
         torch.cuda.synchronize()
         out[general] = (ev[0].elapsed_time(ev[1]) * 50, y)
-    print("%s: %d rows: streamed %.1f us, general %.1f us, same bits: %s" % (
-        os.path.basename(os.environ.get("EBCSIM_LIB", "libebcsim.so")), M, out[False][0], out[True][0], bool(torch.equal(out[False][1], out[True][1]))))
+    sha = [hashlib.sha256(t.cpu().numpy()).hexdigest()[:16] for t in (out[False][1], out[True][1], frag)]
+    print("%s: %d rows: streamed %.1f us, general %.1f us, same bits: %s  sha256 streamed %s general %s fragments %s" % (
+        os.path.basename(os.environ.get("EBCSIM_LIB", "libebcsim.so")), M, out[False][0], out[True][0],
+        bool(torch.equal(out[False][1], out[True][1])), sha[0], sha[1], sha[2]))
 
 
 if __name__ == "__main__":
