@@ -13,7 +13,8 @@ import torch
 
 from . import _abi
 from .lstm_rl import _sequential, _stack
-from .sarl import DeviceSarlPolicy, _NativeMlp2
+from .mlp2 import Mlp2Block
+from .sarl import DeviceSarlPolicy
 
 
 def min_over_rows(v, n_valid=None):
@@ -119,7 +120,7 @@ class CadrlValueNet(object):
             if len(layers) != 4 or int(layers[-1][0].shape[0]) != 1:
                 raise NotImplementedError("CadrlValueNet on a HIP device: value_network is four layers ending in one "
                                           "output (two two-layer blocks)")
-            self._native = tuple(_NativeMlp2(layers[i:i + 2], idx) for i in (0, 2))
+            self._native = tuple(Mlp2Block(layers[i:i + 2], idx) for i in (0, 2))
         return self._native
 
     def _check_width(self, T):

@@ -13,7 +13,8 @@ kernel (ebc_lstm_forward), which also writes the joint vector; on the CPU it is 
 import torch
 
 from . import _abi
-from .sarl import _NativeMlp2
+from .mlp2 import Mlp2Block
+from .sarl import chunk_values
 
 
 def _sequential(input_dim, dims):
@@ -180,8 +181,8 @@ class LstmValueNet(object):
             mlp, mlp1 = _stack(m.mlp), (_stack(m.mlp1) if m.with_interaction_module else [])
             if len(mlp) != 4 or len(mlp1) not in (0, 4) or int(mlp[-1][0].shape[0]) != 1:
                 raise NotImplementedError("LstmValueNet on a HIP device: mlp1 and mlp are four layers each (two two-layer blocks)")
-            pre = tuple(_NativeMlp2(mlp1[i:i + 2], idx) for i in (0, 2)) if mlp1 else ()
-            self._native = (pre, _NativeLstm(m.lstm, idx), tuple(_NativeMlp2(mlp[i:i + 2], idx) for i in (0, 2)))
+            pre = tuple(Mlp2Block(mlp1[i:i + 2], idx) for i in (0, 2)) if mlp1 else ()
+            self._native = (pre, _NativeLstm(m.lstm, idx), tuple(Mlp2Block(mlp[i:i + 2], idx) for i in (0, 2)))
         return self._native
 
     def forward(self, rows, n_valid=None):
@@ -207,12 +208,6 @@ class LstmValueNet(object):
         """reward + discount * V(rows) for every candidate action (multi_human_rl.py:72-76): rows [E, A, R, T] float32,
         reward [E, A] float64 -> values [E, A] float64.  Every value is the float32 network's: `refine` (SARL's
         re-evaluated candidate set) has nothing to do here and is ignored."""
-        E, A, R, T = rows.shape
-        step = E if not chunk_pairs else max(1, int(chunk_pairs) // A)
-        v = torch.empty((E, A), dtype=torch.float32, device=rows.device)
-        for e0 in range(0, E, step):
-            e1 = min(E, e0 + step)
-            nv = None if n_valid is None else n_valid[e0:e1].repeat_interleave(A)
-            v[e0:e1] = self.forward(rows[e0:e1].reshape(-1, R, T), nv).view(e1 - e0, A)
+        v, _ = chunk_values(self.forward, rows, n_valid, chunk_pairs)
         self.values_decidable = False  # the reference's rule (NaN never chosen, no value above -inf raises) decides
         return reward.to(torch.float64) + float(discount) * v.to(torch.float64)

@@ -138,7 +138,7 @@ def occupancy_rows_device(next_ob, n_valid, spec, rows=None, om_out=None, wide_o
     om_out / wide_out: the caller's buffers (contiguous, of those shapes)."""
     import torch
     from . import _capi
-    from .sarl import _out
+    from .mlp2 import _out
     dev = next_ob.device
     assert next_ob.dtype == torch.float64 and next_ob.dim() == 3 and next_ob.shape[2] == 5 and next_ob.is_contiguous()
     E, R = int(next_ob.shape[0]), int(next_ob.shape[1])

@@ -7,12 +7,16 @@ one ebc_lookahead launch that leaves rows_rotated[E][A][R][T] in HBM, and the va
 network is rebuilt functionally from the reference's state_dict, so its .pth files load as they
 are.  Rows beyond an env's n_humans + n_static are masked out of the mean / softmax (the
 reference never creates them)."""
+import collections
 import contextlib
 
 import numpy as np
 import torch
 
-from . import _abi
+from . import _abi, _capi
+from .mlp2 import Mlp2Block, pair_attend, pair_combine, pair_mask, pair_mean, pair_weights
+
+_NativeMlp2 = Mlp2Block  # the block's name while it lived in this module
 
 
 def uniform_v_pref(env):
@@ -43,14 +47,6 @@ def reference_choice(values, check=True):
     return torch.argmax(v, dim=1)  # the first maximal index
 
 
-def _out(out, shape, dtype, device):
-    """A wrapper's output: `out` when the caller passes one (checked: shape, dtype, contiguous), else a new tensor."""
-    if out is None:
-        return torch.empty(shape, dtype=dtype, device=device)
-    assert tuple(out.shape) == tuple(shape) and out.dtype == dtype and out.is_contiguous(), (tuple(out.shape), shape, out.dtype)
-    return out
-
-
 def _mlp(x, layers, last_relu):
     """Linear (+ ReLU) stack.  On the GPU the bias and the ReLU ride in the GEMM's epilogue
     (torch._addmm_activation -> hipBLASLt): same values, no separate pass over the activations."""
@@ -66,157 +62,114 @@ def _mlp(x, layers, last_relu):
     return x
 
 
-class _NativeMlp2(object):
-    """A two-layer block on the bf16 matrix cores with split operands (libebcsim ebc_mlp2_*)."""
+# What select_path knows of a network.  n_blocks: its libebcsim blocks (0: none — a CPU device, another dtype, shapes the
+# blocks do not take, a training view that did not ask for them); gterm, frag: the gterm block / the fragment twins exist
+PathFacts = collections.namedtuple("PathFacts", "with_global_state n_blocks mlp1_out mlp2_out mlp1_epilogue mlp2_epilogue gterm frag")
+PATHS = ("folded_frag", "folded_rows", "exact_native", "blocks", "exact_mlp1", "torch")
 
-    def __init__(self, layers, device_index, final=None, in_fragments=False):
-        """layers: [(w1, b1), (w2, b2)]; final: optional (w3 [1, O], b3 [1]) third layer with one output.
-        in_fragments: the block's input is the fragment tensor another block left with `frag_out` (ebc_mlp2_forward_ex)."""
-        import ctypes as C
-        from . import _capi
-        (w1, b1), (w2, b2) = layers
-        self._L, self._C = _capi.lib(), C
-        self.K0, self.H, self.O = int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0])
-        host = [t.detach().to("cpu", torch.float32).contiguous().numpy() for t in (w1, b1, w2, b2)]
-        self.has_final = final is not None
-        if final is not None:
-            host += [final[0].detach().to("cpu", torch.float32).reshape(-1).contiguous().numpy(),
-                     final[1].detach().to("cpu", torch.float32).reshape(-1).contiguous().numpy()]
-        self._h = C.c_void_p()
-        self.in_fragments = bool(in_fragments)
-        # what ebc_mlp2_forward_reduce / _ex ask of a block whose rows leave through the tile epilogue (partial sums,
-        # fragments): O a multiple of 4 and more than 1 + 1 tiles (the smallest block has no LDS tile per wave to park one)
-        self.tile_epilogue = self.O % 4 == 0 and (self.K0 + 31) // 32 + (self.O + 31) // 32 >= 3
-        _capi.check(self._L.ebc_mlp2_create_ex(int(device_index), self.K0, self.H, self.O, host[0].ctypes.data,
-                                               host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data,
-                                               host[4].ctypes.data if final is not None else None,
-                                               host[5].ctypes.data if final is not None else None,
-                                               _abi.MLP_IN_FRAGMENTS if in_fragments else 0, C.byref(self._h)))
 
-    @staticmethod
-    def frag_buffer(M, width, device):
-        """Storage for an [M, width] activation handed on in fragment order: [row tiles][column tiles][2][2][64] x 16 B."""
-        return torch.empty(((M + 31) // 32, (width + 31) // 32, 2, 2, 64, 4), dtype=torch.int32, device=device)
+def select_path(net, device_type, frag_handoff, native_exact, R, T, exact, want_weights, grad):
+    """Which body SarlValueNet._forward runs -> one of PATHS.  net: PathFacts; device_type: of the rows; frag_handoff,
+    native_exact: the network's two switches; R, T: the rows' shape; grad: torch.is_grad_enabled().  No device work."""
+    if device_type != "cuda" or grad or not net.n_blocks:
+        return "torch"  # every other path is the library's: inference on device rows, on blocks that exist
+    if not exact:
+        # folded: 16 <= R <= 32 (a 32-row tile touches at most three pairs) and the tile epilogue of both blocks
+        if net.with_global_state and 16 <= R <= 32 and not want_weights and net.mlp1_epilogue and net.mlp2_epilogue:
+            return "folded_frag" if frag_handoff and net.frag else "folded_rows"
+        return "blocks"
+    if not native_exact:
+        return "torch"
+    # every block in its float32 form: what the pair kernels between them take (else torch's float32 GEMMs)
+    if (not want_weights and net.with_global_state and net.n_blocks >= 5 and net.gterm and net.mlp1_out % 4 == 0
+            and net.mlp2_out % 4 == 0 and net.mlp2_out <= 256):
+        return "exact_native"
+    return "exact_mlp1" if T > 32 else "torch"  # rows wider than one input tile: mlp1 stays in the library
 
-    def forward_ex(self, M, relu_out, x=None, frag_in=None, row_bias=None, group_rows=0, want_y=True, seg_rows=0,
-                   row_weight=None, want_partial=False, frag_out=None, general=False, y_out=None, partial_out=None):
-        """Every form of the forward in one call (ebc_mlp2_forward_ex): rows or fragments in; rows, per-group partial
-        sums and / or fragments out.  -> (y or None, partial or None); y_out / partial_out: the caller's buffers."""
-        from . import _capi
-        dev = (x if x is not None else frag_in).device
-        a = _abi.EbcMlpArgs()
-        a.struct_size = self._C.sizeof(a)
-        a.M, a.relu_out, a.group_rows, a.seg_rows = int(M), int(bool(relu_out)), int(group_rows), int(seg_rows)
-        a.flags = _abi.MLP_GENERAL_KERNEL if general else 0  # the general block where a specialised kernel exists
-        keep = []
-        if x is not None:
-            x = x.contiguous(); keep.append(x); a.x = x.data_ptr()
-        if frag_in is not None:
-            a.frag_in = frag_in.data_ptr()
-        if row_bias is not None:
-            row_bias = row_bias.contiguous(); keep.append(row_bias); a.row_bias = row_bias.data_ptr()
-        if row_weight is not None:
-            row_weight = row_weight.contiguous(); keep.append(row_weight); a.row_weight = row_weight.data_ptr()
-        y = partial = None
-        if want_y:
-            y = _out(y_out, (M,) if self.has_final else (M, self.O), torch.float32, dev)
-            a.y = y.data_ptr()
-        if want_partial:
-            partial = _out(partial_out, ((M + 31) // 32, 3, self.O), torch.float64, dev)
-            a.partial = partial.data_ptr()
-        if frag_out is not None:
-            a.frag_out = frag_out.data_ptr()
-        _capi.check(self._L.ebc_mlp2_forward_ex(self._h, torch.cuda.current_stream(dev).cuda_stream, self._C.addressof(a)))
-        return y, partial
 
-    def __call__(self, x, relu_out, row_bias=None, group_rows=0, out=None):
-        from . import _capi
-        x = x.contiguous()
-        shape = (x.shape[0],) if self.has_final else (x.shape[0], self.O)
-        y = _out(out, shape, torch.float32, x.device)
-        if row_bias is not None:
-            row_bias = row_bias.contiguous()
-        _capi.check(self._L.ebc_mlp2_forward(self._h, torch.cuda.current_stream(x.device).cuda_stream,
-                                             x.data_ptr(), int(x.shape[0]), int(bool(relu_out)),
-                                             None if row_bias is None else row_bias.data_ptr(), int(group_rows),
-                                             y.data_ptr()))
-        return y
+def _attention_weights(scores, n_valid):
+    """The reference's masked softmax (sarl.py:69-71) over the rows that exist: scores [B, R] -> weights [B, R]."""
+    e = torch.exp(scores) * (scores != 0).to(scores.dtype)
+    if n_valid is not None:
+        e = e * (torch.arange(scores.shape[1], device=scores.device)[None, :] < n_valid[:, None])
+    return e / e.sum(dim=1, keepdim=True)
 
-    def update(self, layers, final=None):
-        """Refresh the packed weights from DEVICE tensors of the shapes the block was created with (ebc_mlp2_update)."""
-        from . import _capi
-        (w1, b1), (w2, b2) = layers
-        t = [x.detach().to(torch.float32).contiguous() for x in (w1, b1, w2, b2)]
-        assert tuple(t[0].shape) == (self.H, self.K0) and tuple(t[2].shape) == (self.O, self.H) and t[0].is_cuda
-        f = None
-        if final is not None:
-            f = [final[0].detach().to(torch.float32).reshape(-1).contiguous(), final[1].detach().to(torch.float32).reshape(-1).contiguous()]
-        _capi.check(self._L.ebc_mlp2_update(self._h, torch.cuda.current_stream(t[0].device).cuda_stream, t[0].data_ptr(),
-                                            t[1].data_ptr(), t[2].data_ptr(), t[3].data_ptr(),
-                                            None if f is None else f[0].data_ptr(), None if f is None else f[1].data_ptr()))
 
-    def f32(self, x, relu_out, row_bias=None, group_rows=0, out=None):
-        """The same block in plain float32 on the vector ALUs (ebc_mlp2_forward_f32): float32-GEMM-grade values for the
-        few rows that decide an argmax."""
-        from . import _capi
-        x = x.contiguous()
-        shape = (x.shape[0],) if self.has_final else (x.shape[0], self.O)
-        y = _out(out, shape, torch.float32, x.device)
-        if row_bias is not None:
-            row_bias = row_bias.contiguous()
-        _capi.check(self._L.ebc_mlp2_forward_f32(self._h, torch.cuda.current_stream(x.device).cuda_stream,
-                                                 x.data_ptr(), int(x.shape[0]), int(bool(relu_out)),
-                                                 None if row_bias is None else row_bias.data_ptr(), int(group_rows),
-                                                 y.data_ptr()))
-        return y
-
-    def reduce(self, x, relu_out, seg_rows, row_weight=None, store=True):
-        """The block with the row-group sums folded into its epilogue (ebc_mlp2_forward_reduce): -> (y or None,
-        partial [ceil(M / 32)][3][O]) — ebc_pair_combine turns the partials into per-pair means / weighted sums."""
-        from . import _capi
-        x = x.contiguous()
-        M = int(x.shape[0])
-        y = torch.empty((M, self.O), dtype=torch.float32, device=x.device) if store else None
-        partial = torch.empty(((M + 31) // 32, 3, self.O), dtype=torch.float64, device=x.device)
-        if row_weight is not None:
-            row_weight = row_weight.contiguous()
-        _capi.check(self._L.ebc_mlp2_forward_reduce(self._h, torch.cuda.current_stream(x.device).cuda_stream,
-                                                    x.data_ptr(), M, int(bool(relu_out)), None, 0,
-                                                    None if y is None else y.data_ptr(), int(seg_rows),
-                                                    None if row_weight is None else row_weight.data_ptr(),
-                                                    partial.data_ptr()))
-        return y, partial
-
-    def __del__(self):
-        try:
-            self._L.ebc_mlp2_destroy(self._h)
-        except Exception:
-            pass
+def chunk_values(forward, rows, n_valid, chunk_pairs, side_streams=None):
+    """forward(pairs [n, R, T], n_valid [n] or None) -> [n] over rows [E, A, R, T] in chunks of whole envs, at most
+    chunk_pairs pairs each (None: one chunk) -> (v [E, A] float32, envs per chunk).  side_streams: asked, when there is
+    more than one chunk, for the streams the chunks alternate between (none: the caller's stream)."""
+    E, A, R, T = rows.shape
+    step = E if not chunk_pairs else max(1, int(chunk_pairs) // A)
+    v = torch.empty((E, A), dtype=torch.float32, device=rows.device)
+    n_chunks = -(-E // step)
+    side = side_streams() if n_chunks > 1 and side_streams is not None else ()
+    if side:
+        # Chunks are independent, and a third of a chunk's kernels are small (the per-pair blocks: ~110 workgroups on
+        # 256 CUs, each as long as its own critical path): chunks alternate between two streams, so one chunk's
+        # small kernels run beside the other's wide ones.  An even number of equal chunks, no larger than asked for.
+        n_chunks += n_chunks & 1
+        step = -(-E // n_chunks)
+        main = torch.cuda.current_stream(rows.device)
+        ready = torch.cuda.Event()
+        ready.record(main)
+    for i, e0 in enumerate(range(0, E, step)):
+        e1 = min(E, e0 + step)
+        if side:
+            side[i % len(side)].wait_event(ready)
+        with torch.cuda.stream(side[i % len(side)]) if side else contextlib.nullcontext():
+            nv = None if n_valid is None else n_valid[e0:e1].repeat_interleave(A)
+            v[e0:e1] = forward(rows[e0:e1].reshape(-1, R, T), nv).view(e1 - e0, A)
+    for s_ in side:
+        main.wait_stream(s_)
+    return v, step
 
 
 class SarlValueNet(object):
     """rl/policy/sarl.py:9-82 (ValueNetwork), weights from its state_dict."""
 
-    def __init__(self, state_dict, device="cpu", with_global_state=True, self_state_dim=6,
-                 dtype=torch.float32):
+    def __init__(self, state_dict, device="cpu", with_global_state=True, self_state_dim=6, dtype=torch.float32):
         """dtype: torch.float32 reproduces the reference's values (2e-4); torch.bfloat16 runs the
         GEMMs on the bf16 matrix cores: measured on MI355X 2.3x faster per decision, but values move by
         up to 0.2 and only 63 % of the envs keep the fp32 action (positions lose their digits in bf16
         inputs) -- an experiment, not a parity path."""
-        self.dtype = dtype
-
         def stack(prefix):
             idx = sorted({int(k.split(".")[1]) for k in state_dict if k.startswith(prefix + ".")})
             return [(state_dict["%s.%d.weight" % (prefix, i)].to(device=device, dtype=dtype),
                      state_dict["%s.%d.bias" % (prefix, i)].to(device=device, dtype=dtype))
                     for i in idx]
-        self.mlp1, self.mlp2 = stack("mlp1"), stack("mlp2")
-        self.attention, self.mlp3 = stack("attention"), stack("mlp3")
-        self.with_global_state = with_global_state
-        self.self_state_dim = self_state_dim
-        self.input_dim = self.mlp1[0][0].shape[1]
-        self.device = torch.device(device)
-        self._native = None  # built on first use: (mlp1, mlp2, attention[1:]) as fused two-layer blocks
+        # the blocks are built on first use: (mlp1, mlp2, attention[1:], mlp3 halves) as fused two-layer blocks
+        self._init(stack("mlp1"), stack("mlp2"), stack("attention"), stack("mlp3"), with_global_state, self_state_dim,
+                   torch.device(device), dtype, build_on_first_use=True)
+
+    @classmethod
+    def from_stacks(cls, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, native=False):
+        """A float32 network on the caller's tensors ([(weight, bias), ...] per stack: a training module's parameters,
+        which change under it).  Packed copies only on request: native builds the blocks from the current weights on a
+        HIP device (enable_native), refresh_native() re-packs them after the weights have changed."""
+        net = cls.__new__(cls)
+        net._init(mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, torch.device(device), torch.float32,
+                  build_on_first_use=False)
+        if native and net.device.type == "cuda":
+            net.enable_native()
+        return net
+
+    def _init(self, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, dtype, build_on_first_use):
+        self.mlp1, self.mlp2, self.attention, self.mlp3 = mlp1, mlp2, attention, mlp3
+        self.with_global_state, self.self_state_dim = with_global_state, self_state_dim
+        self.input_dim = mlp1[0][0].shape[1]
+        self.device, self.dtype = device, dtype
+        # the libebcsim blocks: none until _native_blocks() has built them, which it does once while _build_pending
+        self._build_pending = bool(build_on_first_use)
+        self._native, self._native_frag, self._gterm_block = None, (), None
+        self._facts = PathFacts(with_global_state, 0, 0, 0, False, False, False, False)
+        self.frag_handoff = True  # h1 goes from mlp1 to its consumers as fragments (False: as float32 rows)
+        self.native_exact = True  # exact=True runs the library's float32 blocks (False: torch's float32 GEMMs)
+        self.coarse_eps = None  # the refinement's bound: measured at the first bound-driven decision
+        self.values_decidable = False
+        self.native_forwards = self.folded_forwards = self.native_exact_forwards = self.native_exact_mlp1_forwards = 0
+        self.native_refreshes = 0
+        self._refine_host, self._side_streams = None, {}  # refine_stats' counters, from the first bound-driven decision on
 
     def _block_specs(self):
         """(layers, final) of every libebcsim block of this network, from its CURRENT tensors, or None when the blocks
@@ -255,97 +208,49 @@ class SarlValueNet(object):
     def _native_blocks(self):
         """The two-layer stacks of the network as libebcsim blocks (inference on a HIP device,
         float32 weights, the reference's layer counts); None when that does not apply."""
-        if getattr(self, "_native", ()) is None:  # nets assembled by hand for training opt in with enable_native()
+        if self._build_pending:
             spec = self._block_specs()
             if spec is not None:
                 idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-                # the shapes were checked above: a failure from here on is a HIP error and is raised, never
-                # turned into a silent torch path
+                # the shapes were checked above: a failure from here on is a HIP error and is raised, never a silent torch path
                 specs, gterm = spec
-                self._gterm_block = None if gterm is None else _NativeMlp2(gterm[0], idx)
-                self._native = tuple(_NativeMlp2(layers, idx, final=final) for layers, final in specs)
+                self._gterm_block = None if gterm is None else Mlp2Block(gterm[0], idx)
+                self._native = nat = tuple(Mlp2Block(layers, idx, final=final) for layers, final in specs)
                 # the two consumers of h1 once more, taking it as the fragments mlp1 leaves (no transposition, no splitting
                 # in their input phase): mlp2 and the attention stack
-                self._native_frag = tuple(_NativeMlp2(layers, idx, final=final, in_fragments=True) for layers, final in specs[1:3])
-            else:
-                self._native = ()
-        return getattr(self, "_native", ()) or None
+                self._native_frag = tuple(Mlp2Block(layers, idx, final=final, in_fragments=True) for layers, final in specs[1:3])
+                self._facts = PathFacts(self.with_global_state, len(nat), nat[0].O, nat[1].O, nat[0].tile_epilogue,
+                                        nat[1].tile_epilogue, self._gterm_block is not None, len(self._native_frag) == 2)
+            self._build_pending = False
+        return self._native
 
     def enable_native(self):
         """For a network whose tensors are a training module's parameters (SarlModule.as_value_net): build the blocks
         from the current weights; refresh_native() re-packs them after the weights have changed."""
-        self._native = None
+        self._build_pending = True
         return self._native_blocks() is not None
 
     def refresh_native(self):
         """Re-pack every block from the network's current tensors, on the device (ebc_mlp2_update: no host copy): the
         training loop calls this once per round after its optimizer steps (rl/train.py:239-259), so its rollouts decide
         on the matrix-core blocks like every other decision.  Returns False when the network has no blocks."""
-        nat = getattr(self, "_native", ()) or None
-        if nat is None:
+        if self._native is None:
             return False
         specs, gterm = self._block_specs()
-        for blk, (layers, final) in zip(nat, specs):
-            blk.update(layers, final)
-        for blk, (layers, final) in zip(getattr(self, "_native_frag", ()), specs[1:3]):
+        for blk, (layers, final) in zip(self._native + self._native_frag, specs + specs[1:3]):
             blk.update(layers, final)
         if self._gterm_block is not None:
             self._gterm_block.update(gterm[0], None)
-        self.native_refreshes = getattr(self, "native_refreshes", 0) + 1
+        self.native_refreshes += 1
         self.coarse_eps = None  # other weights: the refinement measures its bound again at the next decision
         return True
 
-    @staticmethod
-    def _pair_mean(h1, nv64, B, R, out=None):
-        """sarl.py:56-58 in one pass over h1 (libebcsim ebc_pair_mean)."""
-        from . import _capi
-        h1 = h1.contiguous()
-        g = _out(out, (B, h1.shape[1]), torch.float32, h1.device)
-        _capi.check(_capi.lib().ebc_pair_mean(torch.cuda.current_stream(h1.device).cuda_stream, h1.data_ptr(),
-                                              None if nv64 is None else nv64.data_ptr(), B, R, int(h1.shape[1]),
-                                              g.data_ptr()))
-        return g
-
-    @staticmethod
-    def _pair_attend(scores, feat, nv64, B, R, out=None):
-        """sarl.py:69-76 in one pass over the features (libebcsim ebc_pair_attend)."""
-        from . import _capi
-        scores, feat = scores.contiguous(), feat.contiguous()
-        out = _out(out, (B, feat.shape[2]), torch.float32, feat.device)
-        _capi.check(_capi.lib().ebc_pair_attend(torch.cuda.current_stream(feat.device).cuda_stream, scores.data_ptr(),
-                                                feat.data_ptr(), None if nv64 is None else nv64.data_ptr(), B, R,
-                                                int(feat.shape[2]), out.data_ptr()))
-        return out
-
-    @staticmethod
-    def _pair_combine(partial, nv64, B, R, mean, out=None):
-        """Per-pair sums of a block's tile partials (libebcsim ebc_pair_combine): the pair mean (sarl.py:56-58) or,
-        with the attention weights as row weights, the weighted feature sum (sarl.py:73-76)."""
-        from . import _capi
-        O = int(partial.shape[2])
-        out = _out(out, (B, O), torch.float32, partial.device)
-        _capi.check(_capi.lib().ebc_pair_combine(torch.cuda.current_stream(partial.device).cuda_stream, partial.data_ptr(),
-                                                 None if nv64 is None else nv64.data_ptr(), B, R, O, int(bool(mean)),
-                                                 out.data_ptr()))
-        return out
-
-    @staticmethod
-    def _pair_weights(scores, nv64, B, R):
-        """softmax' of the pair's scores (sarl.py:69-71) as row weights [B * R] (libebcsim ebc_pair_weights)."""
-        from . import _capi
-        scores = scores.contiguous()
-        w = torch.empty((B * R,), dtype=torch.float32, device=scores.device)
-        _capi.check(_capi.lib().ebc_pair_weights(torch.cuda.current_stream(scores.device).cuda_stream, scores.data_ptr(),
-                                                 None if nv64 is None else nv64.data_ptr(), B, R, w.data_ptr()))
-        return w
-
-    @staticmethod
-    def _pair_mask(nv64, B, R):
-        from . import _capi
-        w = torch.empty((B * R,), dtype=torch.float32, device=nv64.device)
-        _capi.check(_capi.lib().ebc_pair_mask(torch.cuda.current_stream(nv64.device).cuda_stream, nv64.data_ptr(), B, R,
-                                              w.data_ptr()))
-        return w
+    # the pair kernels under the names they had as methods of this class
+    _pair_mean = staticmethod(pair_mean)
+    _pair_attend = staticmethod(pair_attend)
+    _pair_combine = staticmethod(pair_combine)
+    _pair_weights = staticmethod(pair_weights)
+    _pair_mask = staticmethod(pair_mask)
 
     @classmethod
     def load(cls, path, device="cpu", **kw):
@@ -382,7 +287,6 @@ class SarlValueNet(object):
         if not err <= self.COARSE_EPS_MAX:
             raise RuntimeError("SarlValueNet: the matrix-core blocks are off by %.2e on this network: not fit to rank its values" % err)
         self.coarse_eps = max(self.EPS_MARGIN * err, self.EPS_FLOOR)
-        self.measured_coarse_err = err
         return self.coarse_eps
 
     CHUNK_STREAMS = 2  # streams the chunks of a decision batch alternate between (1: the caller's stream only)
@@ -390,11 +294,10 @@ class SarlValueNet(object):
     def _chunk_streams(self, device):
         if self.CHUNK_STREAMS < 2:
             return ()
-        pool = self.__dict__.setdefault("_side_streams", {})
         key = (str(device), self.CHUNK_STREAMS)
-        if key not in pool:
-            pool[key] = tuple(torch.cuda.Stream(device=device) for _ in range(self.CHUNK_STREAMS))
-        return pool[key]
+        if key not in self._side_streams:
+            self._side_streams[key] = tuple(torch.cuda.Stream(device=device) for _ in range(self.CHUNK_STREAMS))
+        return self._side_streams[key]
 
     def action_values(self, rows, reward, discount, n_valid=None, refine=None, chunk_pairs=None, eps=None):
         """reward + discount * V(rows) for every candidate action (multi_human_rl.py:72-76): rows
@@ -411,66 +314,52 @@ class SarlValueNet(object):
         refine: None = this bound-driven set; an int k = the best k candidates of every env (0 = the
         matrix-core values as they are).  refine_stats counts decisions, re-evaluated candidates, envs with more than two
         of them, the largest set, bound violations and fallbacks to the whole batch."""
-        E, A, R, T = rows.shape
         self.values_decidable = False  # set where the float32 selection leaves no NaN and a value above -inf in every env
-        step = E if not chunk_pairs else max(1, int(chunk_pairs) // A)
-        v = torch.empty((E, A), dtype=torch.float32, device=rows.device)
-        n_chunks = -(-E // step)
-        side = self._chunk_streams(rows.device) if (n_chunks > 1 and rows.is_cuda and self._native_blocks() is not None) else ()
-        if side:
-            # Chunks are independent, and a third of a chunk's kernels are small (the per-pair blocks: ~110 workgroups on
-            # 256 CUs, each as long as its own critical path): chunks alternate between two streams, so one chunk's
-            # small kernels run beside the other's wide ones.  An even number of equal chunks, no larger than asked for.
-            n_chunks += n_chunks & 1
-            step = -(-E // n_chunks)
-            main = torch.cuda.current_stream(rows.device)
-            ready = torch.cuda.Event()
-            ready.record(main)
-        for i, e0 in enumerate(range(0, E, step)):
-            e1 = min(E, e0 + step)
-            if side:
-                side[i % len(side)].wait_event(ready)
-            with torch.cuda.stream(side[i % len(side)]) if side else contextlib.nullcontext():
-                nv = None if n_valid is None else n_valid[e0:e1].repeat_interleave(A)
-                v[e0:e1] = self.forward(rows[e0:e1].reshape(-1, R, T), nv).view(e1 - e0, A)
-        for s_ in side:
-            main.wait_stream(s_)
-        native_select = rows.is_cuda and self._native_blocks() is not None and refine is None
-        if native_select:
-            if eps is not None:
-                self.coarse_eps = float(eps)
-            elif getattr(self, "coarse_eps", None) is None:
-                self.calibrate_eps(rows.reshape(E * A, R, T), None if n_valid is None else n_valid.repeat_interleave(A))
-            # values, every env's actions by value and the size of its near-best set in ONE launch (ebc_decision_rank)
-            from . import _capi
-            values = torch.empty((E, A), dtype=torch.float64, device=rows.device)
-            order = torch.empty((E, A), dtype=torch.int32, device=rows.device)
-            count_dev = torch.empty((E,), dtype=torch.int32, device=rows.device)
-            reward = reward.to(torch.float64).contiguous()
-            _capi.check(_capi.lib().ebc_decision_rank(torch.cuda.current_stream(rows.device).cuda_stream, v.data_ptr(), reward.data_ptr(),
-                                                      float(discount), 2.0 * float(discount) * self.coarse_eps, E, A,
-                                                      values.data_ptr(), order.data_ptr(), count_dev.data_ptr()))
-        else:
-            values = reward + discount * v.to(torch.float64)
-        if not (rows.is_cuda and self._native_blocks() is not None) or refine == 0:
-            return values
-        if refine is not None:
-            k = min(int(refine), A)
-            top = torch.topk(values, k, dim=1).indices
-            env_i = torch.arange(E, device=rows.device)[:, None].expand(E, k).reshape(-1)
-            act_i = top.reshape(-1)
-            nv = None if n_valid is None else n_valid[env_i]
-            values[env_i, act_i] = reward[env_i, act_i] + discount * self.forward(rows[env_i, act_i], nv, exact=True).to(torch.float64)
-            return values
+        native = rows.is_cuda and self._native_blocks() is not None
+        v, step = chunk_values(self.forward, rows, n_valid, chunk_pairs, (lambda: self._chunk_streams(rows.device)) if native else None)
+        if native and refine is None:
+            return self._refine_within_bound(rows, reward, discount, n_valid, v, step, eps)
+        values = reward + discount * v.to(torch.float64)
+        if native and refine != 0:
+            self._refine_top_k(rows, reward, discount, n_valid, values, int(refine))
+        return values
+
+    def _refine_top_k(self, rows, reward, discount, n_valid, values, k):
+        """The best k candidates of every env by coarse value, re-evaluated in float32 into `values`."""
+        E, A = values.shape
+        k = min(k, A)
+        act_i = torch.topk(values, k, dim=1).indices.reshape(-1)
+        env_i = torch.arange(E, device=rows.device)[:, None].expand(E, k).reshape(-1)
+        nv = None if n_valid is None else n_valid[env_i]
+        values[env_i, act_i] = reward[env_i, act_i] + discount * self.forward(rows[env_i, act_i], nv, exact=True).to(torch.float64)
+
+    def _rank(self, rows, n_valid, reward, discount, v, eps):
+        """The bound (given, kept or measured now), then values, every env's actions by value and the size of its
+        near-best set in ONE launch (ebc_decision_rank) -> (reward float64, values [E, A], order [E, A], counts [E])."""
+        E, A, R, T = rows.shape
         if eps is not None:
             self.coarse_eps = float(eps)
-        elif getattr(self, "coarse_eps", None) is None:
+        elif self.coarse_eps is None:
             self.calibrate_eps(rows.reshape(E * A, R, T), None if n_valid is None else n_valid.repeat_interleave(A))
-        st = self.__dict__.setdefault("_refine_host", {"decisions": 0, "candidates": 0, "over2": 0, "capped": 0, "max_set": 0,
-                                                       "bound_violations": 0, "contested": 0, "fallbacks": 0})
-        st.setdefault("fallbacks", 0)
+        values = torch.empty((E, A), dtype=torch.float64, device=rows.device)
+        order = torch.empty((E, A), dtype=torch.int32, device=rows.device)
+        count_dev = torch.empty((E,), dtype=torch.int32, device=rows.device)
+        reward = reward.to(torch.float64).contiguous()
+        _capi.check(_capi.lib().ebc_decision_rank(torch.cuda.current_stream(rows.device).cuda_stream, v.data_ptr(), reward.data_ptr(),
+                                                  float(discount), 2.0 * float(discount) * self.coarse_eps, E, A,
+                                                  values.data_ptr(), order.data_ptr(), count_dev.data_ptr()))
+        return reward, values, order, count_dev
+
+    def _refine_within_bound(self, rows, reward, discount, n_valid, v, step, eps):
+        """The bound-driven refinement of action_values: the candidates that could be the float32 best of their env,
+        re-evaluated in float32, with the bound checked on them (a violation widens it and selects again)."""
+        E, A = v.shape
+        reward, values, order, count_dev = self._rank(rows, n_valid, reward, discount, v, eps)
+        if self._refine_host is None:
+            self._refine_host = {"decisions": 0, "candidates": 0, "over2": 0, "capped": 0, "max_set": 0,
+                                 "bound_violations": 0, "contested": 0, "fallbacks": 0}
+        st = self._refine_host
         k = min(self.REFINE_CAP, A)
-        ar = np.arange(E)
         discount = float(discount)
         # the candidates that could be the float32 best: a PREFIX of every env's sorted row, so the set is its length.
         # The lengths go to the host in one 8 KB copy — the one host round trip of the selection — and the index lists
@@ -489,45 +378,15 @@ class SarlValueNet(object):
             fe_dev = torch.from_numpy(fe).to(rows.device)
             if not bool((values[fe_dev] > float("-inf")).any(1).all()):
                 raise ValueError("Value network is not well trained. ")
-        ranked = None
-        for attempt in range(4):
-            if attempt:  # the bound was widened: the sizes again, from the COARSE values by rank (a longer prefix)
-                bound = 2.0 * discount * self.coarse_eps
-                if ranked is None:
-                    ranked = (reward + discount * v.to(torch.float64)).gather(1, order.to(torch.int64))
-                count = (ranked >= (ranked[:, :1] - bound)).sum(1).cpu().numpy()
-            count = np.where(full, A, np.minimum(count, k))
-            # an env with ONE candidate is decided: every other action's float32 value lies below that one's
-            sizes = np.where((count > 1) & ~full, count, 0)
-            n_cand = int(sizes.sum())
-            if n_cand == 0:
-                break
-            env_h = np.repeat(ar, sizes)
-            slot_h = np.arange(n_cand) - np.repeat(np.cumsum(sizes) - sizes, sizes)
-            idx = torch.from_numpy(np.stack([env_h, slot_h])).to(rows.device, non_blocking=True)
-            act_i = order[idx[0], idx[1]].to(torch.int64)
-            # the candidates' float32 values into `values`, and the bound checked where it matters: one launch, one read
-            # (a widened bound below selects a longer prefix and applies again)
-            worst_dev = torch.zeros(1, dtype=torch.float32, device=rows.device)
-            self._apply_exact(rows, n_valid, idx[0], act_i, reward, v, discount, values, worst_dev, E)
-            worst = float(worst_dev)
-            if worst <= self.coarse_eps:
-                break
-            st["bound_violations"] += 1
-            if not worst <= self.COARSE_EPS_MAX:
-                raise RuntimeError("SarlValueNet: matrix-core values off by %.2e: not fit to rank this network's values" % worst)
-            self.coarse_eps = self.EPS_MARGIN * worst
-        else:
+        count, n_cand = self._settle_bound(rows, n_valid, reward, discount, v, values, order, count, full, k)
+        if count is None:
             # every widening pulled in a larger error: the bound has not settled, so every action of the batch is
             # re-evaluated in float32 and the decision is the float32 network's; the errors seen widen the bound
             live = np.nonzero(~full)[0]
             worst_dev = torch.zeros(1, dtype=torch.float32, device=rows.device)
             self._apply_exact(rows, n_valid, np.repeat(live, A), np.tile(np.arange(A), len(live)), reward, v, discount, values,
                               worst_dev, step)
-            worst = float(worst_dev)
-            if not worst <= self.COARSE_EPS_MAX:
-                raise RuntimeError("SarlValueNet: matrix-core values off by %.2e: not fit to rank this network's values" % worst)
-            self.coarse_eps = max(self.coarse_eps, self.EPS_MARGIN * worst)
+            self.coarse_eps = max(self.coarse_eps, self.EPS_MARGIN * self._fit_to_rank(float(worst_dev)))
             st["fallbacks"] += 1
             count = np.full(E, A, dtype=np.int64)
             n_cand = len(live) * A
@@ -542,11 +401,49 @@ class SarlValueNet(object):
         self.values_decidable = n_full == 0
         return values
 
+    def _fit_to_rank(self, worst):
+        if not worst <= self.COARSE_EPS_MAX:
+            raise RuntimeError("SarlValueNet: matrix-core values off by %.2e: not fit to rank this network's values" % worst)
+        return worst
+
+    def _settle_bound(self, rows, n_valid, reward, discount, v, values, order, count, full, k):
+        """Up to four selections: the candidates of every env (a prefix of `order`, `count` long, at most k) re-evaluated
+        in float32 into `values`; the largest error among them within the bound ends it, else the bound is widened and
+        the prefixes are taken again.  -> (the sizes used, candidates re-evaluated), or (None, 0) when four were not enough."""
+        E, A = values.shape
+        ar = np.arange(E)
+        ranked = None
+        for attempt in range(4):
+            if attempt:  # the bound was widened: the sizes again, from the COARSE values by rank (a longer prefix)
+                bound = 2.0 * discount * self.coarse_eps
+                if ranked is None:
+                    ranked = (reward + discount * v.to(torch.float64)).gather(1, order.to(torch.int64))
+                count = (ranked >= (ranked[:, :1] - bound)).sum(1).cpu().numpy()
+            count = np.where(full, A, np.minimum(count, k))
+            # an env with ONE candidate is decided: every other action's float32 value lies below that one's
+            sizes = np.where((count > 1) & ~full, count, 0)
+            n_cand = int(sizes.sum())
+            if n_cand == 0:
+                return count, n_cand
+            env_h = np.repeat(ar, sizes)
+            slot_h = np.arange(n_cand) - np.repeat(np.cumsum(sizes) - sizes, sizes)
+            idx = torch.from_numpy(np.stack([env_h, slot_h])).to(rows.device, non_blocking=True)
+            act_i = order[idx[0], idx[1]].to(torch.int64)
+            # the candidates' float32 values into `values`, and the bound checked where it matters: one launch, one read
+            # (a widened bound above selects a longer prefix and applies again)
+            worst_dev = torch.zeros(1, dtype=torch.float32, device=rows.device)
+            self._apply_exact(rows, n_valid, idx[0], act_i, reward, v, discount, values, worst_dev, E)
+            worst = float(worst_dev)
+            if worst <= self.coarse_eps:
+                return count, n_cand
+            self._refine_host["bound_violations"] += 1
+            self.coarse_eps = self.EPS_MARGIN * self._fit_to_rank(worst)
+        return None, 0
+
     def _apply_exact(self, rows, n_valid, env_i, act_i, reward, v, discount, values, worst_dev, chunk_envs):
         """The float32 form of the network on the pairs (env_i, act_i) (host arrays or device tensors), written into
         `values` as reward + discount * value with the largest |float32 - coarse| among them into worst_dev
         (ebc_decision_apply; worst_dev is not read here).  At most chunk_envs * A pairs per forward."""
-        from . import _capi
         A = values.shape[1]
         if not torch.is_tensor(env_i):
             env_i, act_i = (torch.from_numpy(np.ascontiguousarray(t, dtype=np.int64)).to(rows.device) for t in (env_i, act_i))
@@ -564,142 +461,143 @@ class SarlValueNet(object):
         """Counters of the bound-driven re-evaluation since the network was made: decisions, re-evaluated candidates, envs
         with more than one / more than two candidates, sets cut at REFINE_CAP, the largest set, bound violations, and
         decisions whose bound did not settle in four attempts (every action re-evaluated)."""
-        st = self.__dict__.get("_refine_host")
-        return None if st is None else dict(st)
+        return None if self._refine_host is None else dict(self._refine_host)
+
+    def path_for(self, rows, want_weights=False, exact=False):
+        """The path of select_path that _forward takes on rows [B, R, T] under the current autograd mode."""
+        grad = torch.is_grad_enabled()
+        if rows.is_cuda and not grad:
+            self._native_blocks()  # built on first use; select_path reads what they are from _facts
+        return select_path(self._facts, rows.device.type, self.frag_handoff, self.native_exact, rows.shape[1], rows.shape[2],
+                           exact, want_weights, grad)
 
     def _forward(self, rows, n_valid=None, want_weights=False, exact=False):
-        B, R, T = rows.shape
-        rows = rows.to(getattr(self, "dtype", torch.float32))
-        self_state = rows[:, 0, :self.self_state_dim]
-        nat = None if torch.is_grad_enabled() or not rows.is_cuda or exact else self._native_blocks()
+        rows = rows.to(self.dtype)
         nv64 = None if n_valid is None else n_valid.to(torch.int64).contiguous()
-        # The pair reductions folded into the blocks that produce the rows (16 <= R <= 32: a 32-row tile touches at
-        # most three pairs): mlp1 leaves the pair sums of h1 beside h1, the attention stack runs BEFORE mlp2, and
-        # mlp2 multiplies its rows by the attention weights and leaves only their pair sums — the [B * R][F]
-        # features are never written, nothing reads h1 a second time for the mean.
-        folded = (nat is not None and self.with_global_state and 16 <= R <= 32 and not want_weights
-                  and getattr(self, "fold_pairs", True) and nat[0].tile_epilogue and nat[1].tile_epilogue)
-        if folded:
-            self.native_forwards = getattr(self, "native_forwards", 0) + 1
-            self.folded_forwards = getattr(self, "folded_forwards", 0) + 1
-            mask = None if nv64 is None else self._pair_mask(nv64, B, R)
-            natf = getattr(self, "_native_frag", ()) if getattr(self, "frag_handoff", True) else ()
-            H1 = nat[0].O
-            if len(natf) == 2:
-                # h1 never exists as float32 rows: mlp1 leaves it split and in fragment order, its consumers load that
-                M = B * R
-                h1f = _NativeMlp2.frag_buffer(M, H1, rows.device)
-                _, part = nat[0].forward_ex(M, True, x=rows.reshape(M, T), want_y=False, seg_rows=R, row_weight=mask,
-                                            want_partial=True, frag_out=h1f)
-            else:
-                h1, part = nat[0].reduce(rows.reshape(B * R, T), True, R, mask)
-            g = self._pair_combine(part, nv64, B, R, True)
-            if self._gterm_block is not None:
-                gterm = self._gterm_block(g, False)
-            else:
-                w0, b0 = self.attention[0]
-                gterm = torch.nn.functional.linear(g, w0[:, H1:], b0)
-            if len(natf) == 2:
-                scores, _ = natf[1].forward_ex(M, False, frag_in=h1f, row_bias=gterm, group_rows=R,
-                                               general=getattr(self, "general_kernels", False))
-                w = self._pair_weights(scores, nv64, B, R)
-                _, part = natf[0].forward_ex(M, False, frag_in=h1f, want_y=False, seg_rows=R, row_weight=w, want_partial=True)
-            else:
-                scores = nat[2](h1, False, row_bias=gterm, group_rows=R)
-                w = self._pair_weights(scores, nv64, B, R)
-                _, part = nat[1].reduce(h1, False, R, w, store=False)
-            attended = self._pair_combine(part, None, B, R, False)
-            joint = torch.cat([self_state, attended], dim=1)
-            if len(nat) > 4:
-                return nat[4](nat[3](joint, True), False).squeeze(1)
-            if len(nat) > 3:
-                return _mlp(nat[3](joint, True), self.mlp3[2:], False).squeeze(1).to(torch.float32)
-            return _mlp(joint, self.mlp3, False).squeeze(1).to(torch.float32)
-        # exact on a HIP device: the float32 form of the same blocks (vector ALUs, fmaf into float32 sums) with the pair
-        # kernels in between — the whole refinement stays inside the library (no hipBLASLt GEMMs, no element-wise launches)
-        natx = None
-        if (exact and rows.is_cuda and not torch.is_grad_enabled() and not want_weights and self.with_global_state
-                and getattr(self, "native_exact", True)):
-            natx = self._native_blocks()
-            if natx is not None and (len(natx) < 5 or self._gterm_block is None or natx[0].O % 4 or natx[1].O % 4
-                                     or natx[1].O > 256):  # what the pair kernels take (else: torch's float32 GEMMs)
-                natx = None
-        if natx is not None:
-            self.native_exact_forwards = getattr(self, "native_exact_forwards", 0) + 1
-            h1 = natx[0].f32(rows.reshape(B * R, T), True)
-            feat = natx[1].f32(h1, False).view(B, R, -1)
-            g = self._pair_mean(h1, nv64, B, R)
-            gterm = self._gterm_block.f32(g, False)
-            scores = natx[2].f32(h1, False, row_bias=gterm, group_rows=R).view(B, R)
-            attended = self._pair_attend(scores, feat, nv64, B, R)
-            joint = torch.cat([self_state, attended], dim=1)
-            return natx[4].f32(natx[3].f32(joint, True), False).squeeze(1)
-        if nat is not None:
-            self.native_forwards = getattr(self, "native_forwards", 0) + 1  # tests assert the HIP path ran
-            h1 = nat[0](rows.reshape(B * R, T), True)
-            feat = nat[1](h1, False).view(B, R, -1)
-        elif (exact and T > 32 and rows.is_cuda and not torch.is_grad_enabled() and getattr(self, "native_exact", True)
-              and self._native_blocks() is not None):
-            # rows wider than one input tile (occupancy maps appended) on a network the pair kernels do not take (mlp2
-            # with 50 outputs): mlp1, the one stack that sees the wide rows, still runs as the library's float32 form
-            self.native_exact_mlp1_forwards = getattr(self, "native_exact_mlp1_forwards", 0) + 1
-            h1 = self._native_blocks()[0].f32(rows.reshape(B * R, T), True)
-            feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
-        else:
-            h1 = _mlp(rows.reshape(B * R, T), self.mlp1, True)
-            feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
+        return self._BODIES[self.path_for(rows, want_weights, exact)](self, rows, n_valid, nv64, want_weights, exact)
+
+    def _gterm(self, g, entry=None):
+        """The mean state's half of attention layer 0, once per pair [B, A1]: through `entry` (the gterm block or its
+        float32 form), else torch.  Layer 0 acts on cat([h1, g]) without the concatenation being built."""
+        if entry is not None:
+            return entry(g, False)
+        w0, b0 = self.attention[0]
+        return torch.nn.functional.linear(g, w0[:, g.shape[1]:], b0)
+
+    def _value(self, rows, attended, nat, f32=False):
+        """mlp3 on cat([self state, attended]) -> values [B]: on the blocks `nat` has for it (f32: their float32 form),
+        torch for the layers it has none for."""
+        joint = torch.cat([rows[:, 0, :self.self_state_dim], attended], dim=1)
+        if nat is not None and len(nat) > 4:
+            first, second = (nat[3].f32, nat[4].f32) if f32 else (nat[3], nat[4])
+            return second(first(joint, True), False).squeeze(1)
+        if nat is not None and len(nat) > 3:
+            return _mlp(nat[3](joint, True), self.mlp3[2:], False).squeeze(1).to(torch.float32)
+        return _mlp(joint, self.mlp3, False).squeeze(1).to(torch.float32)
+
+    def _glue(self, rows, n_valid, nv64, want_weights, h1, feat, nat, on_library):
+        """From h1 [B * R, H] and the features [B, R, F] to the values: the pair mean, the attention scores, the
+        weighted feature sum and mlp3.  nat: the blocks for the attention stack and mlp3, or None = torch;
+        on_library: the forward is the library's (blocks, or exact on the device without autograd)."""
+        B, R, _ = rows.shape
         # the pair glue as two HIP kernels (plain float32 arithmetic: also behind the float32 GEMMs of the exact pass,
         # where they replace a dozen element-wise launches)
-        fused = ((nat is not None or (exact and rows.is_cuda and not torch.is_grad_enabled()))
-                 and h1.shape[1] % 4 == 0 and feat.shape[2] % 4 == 0 and feat.shape[2] <= 256)
-        if fused or n_valid is None:
-            valid = None
-            denom = float(R)
+        fused = on_library and h1.shape[1] % 4 == 0 and feat.shape[2] % 4 == 0 and feat.shape[2] <= 256
+        if not self.with_global_state:
+            scores = _mlp(h1, self.attention, False).view(B, R)
         else:
-            valid = (torch.arange(R, device=rows.device)[None, :] < n_valid[:, None])
-            denom = n_valid.to(rows.dtype).clamp(min=1)[:, None, None]
-        if self.with_global_state:
             if fused:
-                g = self._pair_mean(h1, nv64, B, R)
-            else:
-                h1v = h1.view(B, R, -1)
-                if valid is not None:
-                    h1v = h1v * valid[:, :, None]
-                g = h1v.sum(1) / (denom if isinstance(denom, float) else denom[:, 0, :])  # [B, H]: mean of the pair's rows
-            # attention layer 1 on cat([h1, g]) without building the concatenation: the g half of the
-            # weight acts once per pair, its result is added to every row of the pair
-            H = h1.shape[1]
-            w0, b0 = self.attention[0]
-            gterm = torch.nn.functional.linear(g, w0[:, H:], b0)  # [B, A1]
+                g = pair_mean(h1, nv64, B, R)
+            elif n_valid is None:
+                g = h1.view(B, R, -1).sum(1) / float(R)
+            else:  # [B, H]: the mean of the pair's rows that exist
+                valid = (torch.arange(R, device=rows.device)[None, :] < n_valid[:, None])
+                g = (h1.view(B, R, -1) * valid[:, :, None]).sum(1) / n_valid.to(rows.dtype).clamp(min=1)[:, None]
+            gterm = self._gterm(g)  # added to every row of the pair
             if nat is not None:
                 scores = nat[2](h1, False, row_bias=gterm, group_rows=R).view(B, R)
             else:
-                a1 = torch.nn.functional.linear(h1, w0[:, :H]).view(B, R, -1)
+                H = h1.shape[1]
+                a1 = torch.nn.functional.linear(h1, self.attention[0][0][:, :H]).view(B, R, -1)
                 a1 = torch.relu(a1 + gterm[:, None, :]).view(B * R, -1)
                 scores = _mlp(a1, self.attention[1:], False).view(B, R)
-        else:
-            scores = _mlp(h1, self.attention, False).view(B, R)
         if fused:
-            attended = self._pair_attend(scores, feat, nv64, B, R)
+            attended = pair_attend(scores, feat, nv64, B, R)
         else:
-            e = torch.exp(scores) * (scores != 0).to(scores.dtype)  # the reference's masked softmax (sarl.py:69-70)
-            if valid is not None:
-                e = e * valid
-            w = (e / e.sum(dim=1, keepdim=True)).unsqueeze(2)
-            attended = (w * feat).sum(dim=1)
-        joint = torch.cat([self_state, attended], dim=1)
-        if nat is not None and len(nat) > 4:
-            value = nat[4](nat[3](joint, True), False).squeeze(1)
-        elif nat is not None and len(nat) > 3:
-            value = _mlp(nat[3](joint, True), self.mlp3[2:], False).squeeze(1).to(torch.float32)
-        else:
-            value = _mlp(joint, self.mlp3, False).squeeze(1).to(torch.float32)
-        if not want_weights:
-            return value
-        e = torch.exp(scores) * (scores != 0).to(scores.dtype)
-        if n_valid is not None:
-            e = e * (torch.arange(R, device=rows.device)[None, :] < n_valid[:, None])
-        return value, e / e.sum(dim=1, keepdim=True)
+            attended = (_attention_weights(scores, n_valid).unsqueeze(2) * feat).sum(dim=1)
+        value = self._value(rows, attended, nat)
+        return (value, _attention_weights(scores, n_valid)) if want_weights else value
+
+    # one body per path of select_path
+    def _folded_frag(self, rows, n_valid, nv64, want_weights, exact):
+        """mlp1 leaves the pair sums of h1 beside h1, the attention stack runs BEFORE mlp2, and mlp2 multiplies its rows
+        by the attention weights and leaves only their pair sums — the [B * R][F] features are never written, nothing
+        reads h1 a second time for the mean.  h1 never exists as float32 rows: mlp1 leaves it split and in fragment
+        order, its consumers load that."""
+        (B, R, T), M = rows.shape, rows.shape[0] * rows.shape[1]
+        self.native_forwards, self.folded_forwards = self.native_forwards + 1, self.folded_forwards + 1
+        nat, natf = self._native, self._native_frag
+        mask = None if nv64 is None else pair_mask(nv64, B, R)
+        h1f = Mlp2Block.frag_buffer(M, nat[0].O, rows.device)
+        _, part = nat[0].forward_ex(M, True, x=rows.reshape(M, T), want_y=False, seg_rows=R, row_weight=mask,
+                                    want_partial=True, frag_out=h1f)
+        gterm = self._gterm(pair_combine(part, nv64, B, R, True), self._gterm_block)
+        scores, _ = natf[1].forward_ex(M, False, frag_in=h1f, row_bias=gterm, group_rows=R)
+        w = pair_weights(scores, nv64, B, R)
+        _, part = natf[0].forward_ex(M, False, frag_in=h1f, want_y=False, seg_rows=R, row_weight=w, want_partial=True)
+        return self._value(rows, pair_combine(part, None, B, R, False), nat)
+
+    def _folded_rows(self, rows, n_valid, nv64, want_weights, exact):
+        """The folded path with h1 handed on as float32 rows (ebc_mlp2_forward_reduce)."""
+        B, R, T = rows.shape
+        self.native_forwards, self.folded_forwards = self.native_forwards + 1, self.folded_forwards + 1
+        nat = self._native
+        mask = None if nv64 is None else pair_mask(nv64, B, R)
+        h1, part = nat[0].reduce(rows.reshape(B * R, T), True, R, mask)
+        gterm = self._gterm(pair_combine(part, nv64, B, R, True), self._gterm_block)
+        scores = nat[2](h1, False, row_bias=gterm, group_rows=R)
+        w = pair_weights(scores, nv64, B, R)
+        _, part = nat[1].reduce(h1, False, R, w, store=False)
+        return self._value(rows, pair_combine(part, None, B, R, False), nat)
+
+    def _exact_native(self, rows, n_valid, nv64, want_weights, exact):
+        """exact on a HIP device: the float32 form of the same blocks (vector ALUs, fmaf into float32 sums) with the pair
+        kernels in between — the whole refinement stays inside the library (no hipBLASLt GEMMs, no element-wise launches)."""
+        B, R, T = rows.shape
+        self.native_exact_forwards += 1
+        nat = self._native
+        h1 = nat[0].f32(rows.reshape(B * R, T), True)
+        feat = nat[1].f32(h1, False).view(B, R, -1)
+        gterm = self._gterm(pair_mean(h1, nv64, B, R), self._gterm_block.f32)
+        scores = nat[2].f32(h1, False, row_bias=gterm, group_rows=R).view(B, R)
+        return self._value(rows, pair_attend(scores, feat, nv64, B, R), nat, f32=True)
+
+    def _blocks(self, rows, n_valid, nv64, want_weights, exact):
+        """The general native path: every stack a block, the pair glue as kernels where their widths allow."""
+        B, R, T = rows.shape
+        self.native_forwards += 1  # tests assert the HIP path ran
+        h1 = self._native[0](rows.reshape(B * R, T), True)
+        feat = self._native[1](h1, False).view(B, R, -1)
+        return self._glue(rows, n_valid, nv64, want_weights, h1, feat, self._native, True)
+
+    def _exact_mlp1(self, rows, n_valid, nv64, want_weights, exact):
+        """Rows wider than one input tile (occupancy maps appended) on a network the pair kernels do not take (mlp2 with
+        50 outputs): mlp1, the one stack that sees the wide rows, as the library's float32 block, torch for the rest."""
+        B, R, T = rows.shape
+        self.native_exact_mlp1_forwards += 1
+        h1 = self._native[0].f32(rows.reshape(B * R, T), True)
+        feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
+        return self._glue(rows, n_valid, nv64, want_weights, h1, feat, None, True)
+
+    def _torch(self, rows, n_valid, nv64, want_weights, exact):
+        """torch's GEMMs: the CPU, training (autograd), networks without blocks, exact=True where no float32 block applies."""
+        B, R, T = rows.shape
+        h1 = _mlp(rows.reshape(B * R, T), self.mlp1, True)
+        feat = _mlp(h1, self.mlp2, False).view(B, R, -1)
+        return self._glue(rows, n_valid, nv64, want_weights, h1, feat, None, exact and rows.is_cuda and not torch.is_grad_enabled())
+
+    _BODIES = {"folded_frag": _folded_frag, "folded_rows": _folded_rows, "exact_native": _exact_native, "blocks": _blocks,
+               "exact_mlp1": _exact_mlp1, "torch": _torch}
 
 
 class DeviceSarlPolicy(object):
@@ -717,7 +615,7 @@ class DeviceSarlPolicy(object):
         self.actions_np = np.ascontiguousarray(actions, dtype=np.float64)
         self.gamma = float(gamma)
         self.chunk_rows = int(chunk_rows)
-        self._bufs = None
+        self._bufs = self._env_key = None
 
     def values_from(self, rows, reward, n_valid, dt, v_pref):
         """rows [E, A, R, T] float32, reward [E, A] float64 -> values [E, A] float64
@@ -736,7 +634,7 @@ class DeviceSarlPolicy(object):
         dev = self.net.device
         A = len(self.actions_np)
         key = (id(env), env.E, env.R, env.T)
-        if self._bufs is None or getattr(self, "_env_key", None) != key:  # buffers are sized for ONE env batch
+        if self._bufs is None or self._env_key != key:  # buffers are sized for ONE env batch
             self._env_key = key
             self._acts = torch.tensor(self.actions_np, dtype=torch.float64, device=dev)
             self._bufs = env.alloc_lookahead_outputs(A, ("reward", "rows_rotated") + (("next_ob",) if self.om is not None else ()))
@@ -744,7 +642,7 @@ class DeviceSarlPolicy(object):
             self._v_pref = uniform_v_pref(env)
             if self.om is not None:
                 wide = env.T + self.om.width
-                if getattr(self.net, "input_dim", wide) != wide:
+                if self.net.input_dim != wide:
                     raise ValueError("the value network takes rows %d wide, occupancy maps make them %d + %d" % (
                         self.net.input_dim, env.T, self.om.width))
                 self._wide = torch.empty((env.E, A, env.R, wide), dtype=torch.float32, device=dev)
@@ -765,6 +663,6 @@ class DeviceSarlPolicy(object):
         """The reference's choice over values [E, A] (reference_choice).  Values that action_values' float32 selection
         left without a NaN and with a value above -inf in every env (values_decidable) need neither the NaN mask nor
         the host round trip of the check: the first maximum is the reference's choice."""
-        if getattr(self.net, "values_decidable", False):
+        if self.net.values_decidable:
             return torch.argmax(values, dim=1)
         return reference_choice(values)

@@ -74,17 +74,8 @@ class SarlModule(torch.nn.Module):
         """A SarlValueNet whose tensors ARE this module's parameters (it follows every optimizer step).  native: also
         build the matrix-core blocks for inference from the current weights — the caller re-packs them with
         net.refresh_native() after the weights have changed (run_training: once per round)."""
-        net = SarlValueNet.__new__(SarlValueNet)
-        net.mlp1, net.mlp2 = self._stack("mlp1"), self._stack("mlp2")
-        net.attention, net.mlp3 = self._stack("attention"), self._stack("mlp3")
-        net.with_global_state, net.self_state_dim = self.with_global_state, self.self_state_dim
-        net.input_dim = self._layout["mlp1"][0]
-        net.device = next(self.parameters()).device
-        net.dtype = torch.float32
-        net._native = ()  # the weights change under training: packed copies only on request (native=True)
-        if native and net.device.type == "cuda":
-            net.enable_native()
-        return net
+        return SarlValueNet.from_stacks(self._stack("mlp1"), self._stack("mlp2"), self._stack("attention"), self._stack("mlp3"),
+                                        self.with_global_state, self.self_state_dim, next(self.parameters()).device, native)
 
     def forward(self, rows, n_valid=None):
         net = self.as_value_net()
@@ -539,8 +530,8 @@ def run_training(env, model, actions, gamma, il_steps=0, il_epochs=0, il_learnin
     if train_iterations:
         save(os.path.join(output_dir or ".", "rl_model_%d.pth" % train_iterations))
     # how the rollouts decided: matrix-core forwards and on-device re-packs of the blocks (0 / 0 on a CPU device)
-    hist["native_forwards"] = int(getattr(policy.net, "native_forwards", 0))
-    hist["native_refreshes"] = int(getattr(policy.net, "native_refreshes", 0))
+    hist["native_forwards"] = int(policy.net.native_forwards)
+    hist["native_refreshes"] = int(policy.net.native_refreshes)
     return hist
 
 

@@ -399,3 +399,40 @@ def test_whole_network_against_float64(name, dims, T, native, native_exact):
         print("%s R %d: coarse error %.3g, exact error %.3g, float32 CPU %.3g, scale %.3g" % (name, R, ec, ee, e32, scale))
         assert ec <= 5e-5, (name, R, ec)
         assert ee <= max(3.0 * e32, 2e-6 * max(1.0, scale)), (name, R, ee, e32)
+
+
+# what each path of ebcsim.sarl.select_path adds to (native_forwards, folded_forwards, native_exact_forwards,
+# native_exact_mlp1_forwards)
+PATH_COUNTERS = {"folded_frag": (1, 1, 0, 0), "folded_rows": (1, 1, 0, 0), "blocks": (1, 0, 0, 0),
+                 "exact_native": (0, 0, 1, 0), "exact_mlp1": (0, 0, 0, 1), "torch": (0, 0, 0, 0)}
+
+
+@pytest.mark.parametrize("which", ("golden", "small_T13"))
+def test_the_counters_follow_the_selector(which):
+    """One forward moves exactly the counters of the path the selector names, by 1: the shipped weights (folded between
+    16 and 32 rows, the library's float32 form when exact) and the network whose blocks have no tile epilogue."""
+    import os
+    from ebcsim.sarl import SarlValueNet
+    from helpers import GOLDEN
+    if which == "golden":
+        net = SarlValueNet.load(os.path.join(GOLDEN, "weights", "sarl_n10_ebcadrl.pth"), device="cuda:0")
+    else:
+        name, dims, T, _, _ = next(n for n in vc.NETWORKS if n[0] == which)
+        net = SarlValueNet(vc.network_state_dict(dims, T, seed=T * 13 + len(name)), device="cuda:0")
+    g = torch.Generator().manual_seed(5)
+    B, T = 5, net.input_dim
+    counters = lambda: (net.native_forwards, net.folded_forwards, net.native_exact_forwards, net.native_exact_mlp1_forwards)  # noqa: E731
+    seen = set()
+    for R in vc.NETWORK_ROWS:
+        rows = torch.randn(B, R, T, generator=g).cuda()
+        nv = torch.randint(1, R + 1, (B,), generator=g).cuda()
+        for exact in (False, True):
+            with torch.no_grad():
+                path = net.path_for(rows, exact=exact)
+            before = counters()
+            out = net.forward(rows, nv, exact=exact)
+            moved = tuple(a - b for a, b in zip(counters(), before))
+            assert moved == PATH_COUNTERS[path], (which, R, exact, path, moved)
+            assert tuple(out.shape) == (B,) and bool(torch.isfinite(out).all())
+            seen.add(path)
+    assert seen == ({"folded_frag", "blocks", "exact_native"} if which == "golden" else {"blocks", "exact_native"}), seen

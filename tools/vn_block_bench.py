@@ -13,7 +13,7 @@ for p in (ROOT, os.path.join(ROOT, "eb-cadrl_amd")):
 
 def main():
     import torch
-    from ebcsim.sarl import _NativeMlp2
+    from ebcsim.mlp2 import Mlp2Block
     M = int(sys.argv[1]) if len(sys.argv) > 1 else 359 * 81 * 18
     dev = torch.device("cuda", 0)
     g = torch.Generator().manual_seed(3)
@@ -21,11 +21,11 @@ def main():
 
     def lin(o, i):
         return torch.randn(o, i, generator=g) / i ** 0.5, torch.randn(o, generator=g)
-    src = _NativeMlp2([lin(300, 17), lin(K0, 300)], 0)
-    att = _NativeMlp2([lin(H, K0), lin(O, H)], 0, final=(torch.randn(1, O, generator=g) / O ** 0.5, torch.randn(1, generator=g)),
+    src = Mlp2Block([lin(300, 17), lin(K0, 300)], 0)
+    att = Mlp2Block([lin(H, K0), lin(O, H)], 0, final=(torch.randn(1, O, generator=g) / O ** 0.5, torch.randn(1, generator=g)),
                       in_fragments=True)
     x = torch.randn(M, 17, generator=g).to(dev)
-    frag = _NativeMlp2.frag_buffer(M, K0, dev)
+    frag = Mlp2Block.frag_buffer(M, K0, dev)
     src.forward_ex(M, True, x=x, want_y=False, seg_rows=18, want_partial=True, frag_out=frag)
     rb = torch.randn((M + 17) // 18, H, generator=g).to(dev)
     out = {}
