@@ -29,14 +29,13 @@ __global__ __launch_bounds__(EBC_WAVE) void dagger_label_kernel(EbcParams p, Dev
   __shared__ __align__(16) unsigned char scratch[OrcaLds<GS>::BYTES];
   const RobotLane l = robot_lane<GS>(s);
   const int R = s.N + s.S;
-  bool valid;
-  const RobotRow row = robot_row_load(s, l, valid);
+  const ObsRow row = obs_row(env_rows(s, l.ee), l.j, l.n, l.ns);
   double rb[9];
   const double *src = s.robot + l.ee * 9;
 #pragma unroll
   for (int c = 0; c < 9; ++c) rb[c] = src[c];
   float ox, oy;
-  orca_robot_solve<GS>(p, s, safety_space, sim, scratch, l, rb, row, valid, ox, oy, [&]() {
+  orca_robot_solve<GS>(p, s, safety_space, sim, scratch, l, rb, row, ox, oy, [&]() {
     if (l.e_ok && l.j < R) {
       double *o = ob_out + (l.ee * R + l.j) * 5;
       o[0] = row.px; o[1] = row.py; o[2] = row.vx; o[3] = row.vy; o[4] = row.radius;

@@ -30,29 +30,12 @@
 #endif
 #include "ebc_orca_group.h"
 #include "ebc_scene_gen.h"
+#include "ebc_step_rules.h"
 
 namespace ebc {
 
-
-// Scenes an env restarts from under EBC_FLAG_AUTO_RESET, in the same SoA layout as the state.
-// Slots [0, E) are the envs' own ebc_reset scenes; slots [E, E + P) a host-generated pool installed
-// by ebc_set_scene_pool.  cursor[e] is the slot env e restarts from next: e itself without a pool
-// (stride 0), else it walks E + (e mod P), + stride, ... (mod P) from episode to episode without
-// leaving the device.  Occupancy grids are never copied: an env points at the grid of the slot it
-// is running (grid_scene[e]).
-struct ScenePool {
-  int P, stride;  // custom scenes (0 = none) and the cursor step
-  int *cursor;  // [E]
-  int *n_humans;
-  double *px, *py, *vx, *vy, *gx, *gy, *radius, *v_pref;
-  uint8_t *type;
-  int *n_static;
-  double *spx, *spy, *sradius;
-  uint64_t *grid;  // nullptr: free maps
-  double *robot;
-  float2 *pref;    // [slots][N] ORCA preferred velocity of the scene's humans (float tile, orca.py:136-140)
-};
-
+// The device state of a batch, a kernel argument.  Its member `pool` is a ScenePool, the scenes an env restarts from:
+// that struct is defined in ebc_step_rules.h, beside the restart rules that read it (restart_human, pool_next_cursor).
 struct DevState {
   int E, N, S, G;
   int *n_humans;
@@ -180,6 +163,16 @@ struct OrcaLds {
   static constexpr int DIST = GROUPS * Sh::DIST * 4;
   static constexpr int BYTES = DIST + 3 * GROUPS * Sh::LINES * 16;
 };
+// The four arrays of a wave's scratch area; orca_group takes group g's part of each (+ g * Sh::DIST, + g * Sh::LINES)
+template <int GS>
+__device__ __forceinline__ void orca_scratch_carve(unsigned char *scratch, float *&dist_lds, float4 *&lines_lds,
+                                                   float4 *&segs_lds, float4 *&proj_lds) {
+  using L = OrcaLds<GS>;
+  dist_lds = reinterpret_cast<float *>(scratch);
+  lines_lds = reinterpret_cast<float4 *>(scratch + L::DIST);
+  segs_lds = lines_lds + L::GROUPS * L::Sh::LINES;
+  proj_lds = segs_lds + L::GROUPS * L::Sh::LINES;
+}
 
 // What an ORCA wave needs before it can issue its first load.  In the step launch these are the
 // leading kernel arguments, preloaded into scalar registers when the wave starts
@@ -225,16 +218,18 @@ __device__ __forceinline__ OrcaTile orca_tile_load(const OrcaHot &hot, bool h_ok
   return t;
 }
 
-template <int GS, typename Hook = NoHook>
-__device__ __forceinline__ void orca_wave_compute(const EbcParams &p, const DevState &s, const OrcaHot &hot, const OrcaTile &t,
-                                                  bool h_ok, int e, int i, unsigned char *scratch, float &ox, float &oy,
-                                                  bool &human_ok, Hook after_rank = Hook()) {
+// A human's ORCA solve from t = orca_tile_load's record.  robot_of() = the FullState of the env's robot, asked for only
+// where the robot is one of the "others" (with a pointer worked out by the caller the compiler emits other code for the
+// ORCA role of orca_step_kernel at the power-of-two group sizes: profiles/step_rules_refactor.txt); record and robot may
+// live in global memory or in LDS.
+template <int GS, typename RobotOf, typename Hook = NoHook>
+__device__ __forceinline__ void orca_wave_compute(const EbcParams &p, const DevState &s, int N, const OrcaTile &t,
+                                                  RobotOf robot_of, bool h_ok, int i, unsigned char *scratch, float &ox,
+                                                  float &oy, bool &human_ok, Hook after_rank = Hook()) {
   using L = OrcaLds<GS>;
-  float *dist_lds = reinterpret_cast<float *>(scratch);
-  float4 *lines_lds = reinterpret_cast<float4 *>(scratch + L::DIST);
-  float4 *segs_lds = lines_lds + L::GROUPS * L::Sh::LINES;
-  float4 *proj_lds = segs_lds + L::GROUPS * L::Sh::LINES;
-  const int N = hot.N;
+  float *dist_lds;
+  float4 *lines_lds, *segs_lds, *proj_lds;
+  orca_scratch_carve<GS>(scratch, dist_lds, lines_lds, segs_lds, proj_lds);
   const int lane = threadIdx.x & (EBC_WAVE - 1);
   const int group = lane / GS;
   const int j = lane - group * GS;
@@ -246,7 +241,7 @@ __device__ __forceinline__ void orca_wave_compute(const EbcParams &p, const DevS
   const int n_others = human_ok ? (n - 1 + (p.robot_visible ? 1 : 0)) : 0;
   const bool valid = j < n_others;
   if (p.robot_visible && valid && j == n - 1) {  // the robot, last in ob (env.py:401-402)
-    const double *rb = s.robot + (size_t)e * 9;
+    const double *rb = robot_of();
     opx = (float)rb[0];
     opy = (float)rb[1];
     ovx = (float)rb[2];
@@ -263,7 +258,7 @@ template <int GS>
 __device__ __forceinline__ void orca_wave(const EbcParams &p, const DevState &s, const OrcaHot &hot, bool h_ok, int e, int i,
                                           unsigned char *scratch, float &ox, float &oy, bool &human_ok) {
   const OrcaTile t = orca_tile_load<GS>(hot, h_ok, e, i);
-  orca_wave_compute<GS>(p, s, hot, t, h_ok, e, i, scratch, ox, oy, human_ok);
+  orca_wave_compute<GS>(p, s, hot.N, t, [&] { return s.robot + (size_t)e * 9; }, h_ok, i, scratch, ox, oy, human_ok);
 }
 
 // (env, slot) of flat human index h < E * N without the ~20-instruction integer divide
@@ -334,45 +329,27 @@ __device__ __forceinline__ RobotLane robot_lane(const DevState &s) {
   return l;
 }
 
-// Row j of the env's observation in the world frame (env.py:381-382, :457-458): px, py, vx, vy, radius as the state
-// holds them (float64); a row that does not exist is zeros, which is also what ebc_observe writes for it.
-struct RobotRow {
-  double px, py, vx, vy, radius;
-};
-__device__ __forceinline__ RobotRow robot_row_load(const DevState &s, const RobotLane &l, bool &valid) {
-  RobotRow r = {0, 0, 0, 0, 0};
-  valid = l.e_ok && l.j < l.n + l.ns;
-  if (valid && l.j < l.n) {
-    const size_t k = l.ee * s.N + l.j;
-    r.px = s.px[k];
-    r.py = s.py[k];
-    r.vx = s.vx[k];
-    r.vy = s.vy[k];
-    r.radius = s.radius[k];
-  } else if (valid) {
-    const size_t q = l.ee * s.S + (l.j - l.n);
-    r.px = s.spx[q];
-    r.py = s.spy[q];
-    r.radius = s.sradius[q];
-  }
-  return r;
+// The arrays of env e in the device state, as obs_row (ebc_step_rules.h) reads an observation row from them
+__device__ __forceinline__ EnvRows<uint8_t> env_rows(const DevState &s, size_t e) {
+  return EnvRows<uint8_t>{s.px, s.py, s.vx, s.vy, s.radius, s.type, s.spx, s.spy, s.sradius}.at(e * s.N, e * s.S);
 }
 
 // The robot's ORCA solve of one GS-lane group, from the values the caller loaded: rb = the robot's FullState (entries
-// 0 .. 7 are read), row = this lane's observation row.  The ONE definition of that arithmetic for orca_robot_kernel and
-// dagger_label_kernel (ebc_dagger.h), the persistent simulator's read-before-replace included.  before_solve() runs once
-// every global load of the function has been consumed and before the LDS-bound solve: where a caller issues stores
-// that nothing here waits for.
+// 0 .. 7 are read), row = row l.j of the env's observation (not valid on an idle lane: l.n = l.ns = 0 there).  The ONE
+// definition of that arithmetic for orca_robot_kernel, dagger_label_kernel (ebc_dagger.h) and rollout_kernel
+// (ebc_rollout.h, where rb, row and sim live in LDS), the persistent simulator's read-before-replace included.
+// before_solve() runs once every global load of the function has been consumed and before the LDS-bound solve: where a
+// caller issues stores that nothing here waits for.
 template <int GS, typename Hook = NoHook>
 __device__ __forceinline__ void orca_robot_solve(const EbcParams &p, const DevState &s, double safety_space, const RobotSim &sim,
-                                                 unsigned char *scratch, const RobotLane &l, const double *rb, const RobotRow &row,
-                                                 bool valid, float &ox, float &oy, Hook before_solve = Hook()) {
+                                                 unsigned char *scratch, const RobotLane &l, const double *rb, const ObsRow &row,
+                                                 float &ox, float &oy, Hook before_solve = Hook()) {
   using L = OrcaLds<GS>;
-  float *dist_lds = reinterpret_cast<float *>(scratch);
-  float4 *lines_lds = reinterpret_cast<float4 *>(scratch + L::DIST);
-  float4 *segs_lds = lines_lds + L::GROUPS * L::Sh::LINES;
-  float4 *proj_lds = segs_lds + L::GROUPS * L::Sh::LINES;
+  float *dist_lds;
+  float4 *lines_lds, *segs_lds, *proj_lds;
+  orca_scratch_carve<GS>(scratch, dist_lds, lines_lds, segs_lds, proj_lds);
   const int group = l.group, j = l.j, n = l.n, ns = l.ns;
+  const bool valid = row.valid;
   const size_t ee = l.ee;
   const int N = s.N, S = s.S;
   const float posx = (float)rb[0], posy = (float)rb[1], velx = (float)rb[2], vely = (float)rb[3];
@@ -380,7 +357,7 @@ __device__ __forceinline__ void orca_robot_solve(const EbcParams &p, const DevSt
   float prefx, prefy;
   orca_pref_velocity(rb[0], rb[1], rb[5], rb[6], prefx, prefy);
   float opx = 0, opy = 0, ovx = 0, ovy = 0, orad = 0;
-  if (valid) {  // a static row's velocity is the 0 robot_row_load left
+  if (valid) {  // a static row's velocity is the 0 obs_row gave it
     opx = (float)row.px;
     opy = (float)row.py;
     ovx = (float)row.vx;
@@ -415,10 +392,9 @@ template <int GS>
 __global__ __launch_bounds__(EBC_WAVE) void orca_robot_kernel(EbcParams p, DevState s, double safety_space, double *act, RobotSim sim) {
   __shared__ __align__(16) unsigned char scratch[OrcaLds<GS>::BYTES];
   const RobotLane l = robot_lane<GS>(s);
-  bool valid;
-  const RobotRow row = robot_row_load(s, l, valid);
+  const ObsRow row = obs_row(env_rows(s, l.ee), l.j, l.n, l.ns);
   float ox, oy;
-  orca_robot_solve<GS>(p, s, safety_space, sim, scratch, l, s.robot + l.ee * 9, row, valid, ox, oy);
+  orca_robot_solve<GS>(p, s, safety_space, sim, scratch, l, s.robot + l.ee * 9, row, ox, oy);
   if (l.e_ok && l.j == 0) {
     act[2 * l.ee] = (double)ox;  // getAgentVelocity -> Python float
     act[2 * l.ee + 1] = (double)oy;
@@ -676,13 +652,14 @@ __device__ __forceinline__ void unpack_velocity(u32x4 v, double &ax, double &ay)
   ay = (double)__uint_as_float(v.z);
 }
 
-// The robot's action for this step (its policy, or the caller's) — env.py:388-392.
-__device__ __forceinline__ void robot_action(const StepIO &io, size_t ee, const double *rb, double &a0, double &a1) {
-  if (io.robot_policy == EBC_ROBOT_LINEAR) {
+// The robot's action for this step (its policy, or entry ee of the caller's actions) — env.py:388-392.
+__device__ __forceinline__ void robot_action(int policy, const double *actions, size_t ee, const double *rb, double &a0,
+                                             double &a1) {
+  if (policy == EBC_ROBOT_LINEAR) {
     linear_policy(rb[0], rb[1], rb[5], rb[6], rb[7], a0, a1);
   } else {
-    a0 = io.robot_action[2 * ee];
-    a1 = io.robot_action[2 * ee + 1];
+    a0 = actions[2 * ee];
+    a1 = actions[2 * ee + 1];
   }
 }
 // Agent.step for the robot (agent.py:202-228): rb becomes the next state.  It depends on the action
@@ -748,6 +725,7 @@ __device__ __forceinline__ int service_env(const EbcParams &p_early, const DevSt
   }
   wave_sync();
   const double a0 = sh_ract[m.env_ok ? m.el : 0][0], a1 = sh_ract[m.env_ok ? m.el : 0][1];
+  // swept_robot_velocity (ebc_step_rules.h), restated
   double rvx, rvy;
   if (p.robot_kinematics == EBC_HOLONOMIC) {
     rvx = a0;
@@ -813,6 +791,7 @@ __device__ __forceinline__ int service_env(const EbcParams &p_early, const DevSt
     rb[3] = a0 * sin(rb[8]);
   }
   s.done[m.ee] = (uint8_t)ro.done;
+  // store_outcome (ebc_step_rules.h), restated
   if (io.reward) io.reward[m.ee] = ro.reward;
   if (io.done) io.done[m.ee] = (uint8_t)ro.done;
   if (io.info) io.info[m.ee] = (uint8_t)ro.info;
@@ -853,6 +832,7 @@ __device__ __forceinline__ void commit_state_tail(const EbcParams &p, const DevS
   if (restore) {
     const ScenePool &P = s.pool;
     const int n_new = pre.n_humans;
+    // restart_human (ebc_step_rules.h), restated over the preloaded scene
     const bool live = m.i < n_new;
     const double npx = live ? pre.px : 0.0, npy = live ? pre.py : 0.0;
     const double nvx = live ? pre.vx : 0.0, nvy = live ? pre.vy : 0.0;
@@ -885,6 +865,7 @@ __device__ __forceinline__ void commit_state_tail(const EbcParams &p, const DevS
 #pragma unroll
       for (int q = 0; q < 9; ++q) A.robot[q] = pre.robot[q];
       *A.time = 0.0;
+      // pool_next_cursor (ebc_step_rules.h), restated
       if (P.P > 0) {  // walk the custom pool; without one the env keeps restarting from its own slot
         int nxt = pre.cursor - s.E + P.stride;
         P.cursor[m.ee] = s.E + (nxt >= P.P ? nxt % P.P : nxt);
@@ -923,6 +904,7 @@ __device__ __forceinline__ void service_commit(const EbcParams &p, const DevStat
     A.human_action[1] = ay;
   }
   // returned observation: humans then static rows, raw and in the robot frame
+  // obs_row + rotated_row_or_zeros (ebc_step_rules.h), restated over the preloaded rows
   if (io.ob || io.obs_rotated) {
     int t = 0;
     for (int r = m.i; r < R; r += N, ++t) {
@@ -1089,7 +1071,7 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
 #pragma unroll
   for (int c = 0; c < 9; ++c) pin(rb[c]);
   double a0 = 0, a1 = 0;
-  if (ok) robot_action(io, ee, rb, a0, a1);
+  if (ok) robot_action(io.robot_policy, io.robot_action, ee, rb, a0, a1);
   EBC_MARK(1);
   {
     // The robot's next state, published as soon as the action is known: the ROWS role builds this step's observation
@@ -1136,6 +1118,7 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
       ht[q] = have ? (int)sl.type[k] : 0;
     }
   }
+  // swept_robot_velocity (ebc_step_rules.h), restated
   double rvx, rvy;
   if (p.robot_kinematics == EBC_HOLONOMIC) {
     rvx = a0;
@@ -1144,7 +1127,8 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
     rvx = a0 * cos(a1 + rb[8]);
     rvy = a0 * sin(a1 + rb[8]);
   }
-  // compute_collisions (env.py:303-338) over this lane's humans: per type in index order, break at the first hit
+  // compute_collisions (env.py:303-338) over this lane's humans: per type in index order, break at the first hit:
+  // TypeWalk::visit (ebc_step_rules.h), restated
   double dmin[3] = {INFINITY, INFINITY, INFINITY};
   int coll[4] = {0, 0, 0, 0};
   auto visit = [&](double px, double py, double vx, double vy, double r, int t) {
@@ -1198,6 +1182,7 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
     EBC_MARK(3);
     const RewardOut ro = reward_compute(p, nx, ny, XL.goal[el][0], XL.goal[el][1], rb[4], a1, XL.gtime[el], fm, c4);
     s.done[ee] = (uint8_t)ro.done;
+    // store_outcome (ebc_step_rules.h), restated
     if (io.reward) io.reward[ee] = ro.reward;
     if (io.done) io.done[ee] = (uint8_t)ro.done;
     if (io.info) io.info[ee] = (uint8_t)ro.info;
@@ -1301,6 +1286,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     if (env_ok && slot + stride >= R && first == 0) mailbox_put(s.rows_loaded + ee, epoch);
     const bool valid = human ? slot < n : slot - N < ns;
     const int row = human ? (valid ? slot : ns + slot) : (valid ? n + slot - N : slot);
+    // obs_row + rotated_row_or_zeros (ebc_step_rules.h), restated: a slot emits its row as soon as it has it
     auto emit = [&]() {
       if (!valid) opx = opy = ovx = ovy = orad = 0.0;
       if (io.ob) {
@@ -1454,6 +1440,7 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
     // a terminal env under auto-reset takes its next scene: every per-scene field (ragged human
     // count, goals, radii, static rows, map), time 0
     const ScenePool &P = s.pool;
+    // restart_human (ebc_step_rules.h), restated over the preloaded scene
     const bool live = m.i < pre.n_humans;
     s.px[m.k] = live ? pre.px : 0.0;
     s.py[m.k] = live ? pre.py : 0.0;
@@ -1496,6 +1483,7 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
         for (int q = 0; q < 9; ++q) rdst[q] = src[q];
       }
       s.time[m.ee] = 0.0;
+      // pool_next_cursor (ebc_step_rules.h), restated
       if (P.P > 0) {  // walk the custom pool; without one the env keeps restarting from its own slot
         int nxt = pre.cursor - s.E + P.stride;
         P.cursor[m.ee] = s.E + (nxt >= P.P ? nxt % P.P : nxt);
@@ -1613,31 +1601,16 @@ __global__ __launch_bounds__(256) void observe_kernel(EbcParams p, DevState s, d
   const int r = (int)(g - e * R);
   const int n = s.n_humans[e];
   const int ns = s.S ? s.n_static[e] : 0;
-  double opx = 0, opy = 0, ovx = 0, ovy = 0, orad = 0;
-  int otype = 0;
-  bool valid = false;
-  if (r < n) {
-    const size_t k = e * s.N + r;
-    opx = s.px[k]; opy = s.py[k]; ovx = s.vx[k]; ovy = s.vy[k]; orad = s.radius[k]; otype = s.type[k];
-    valid = true;
-  } else if (r - n < ns) {
-    const size_t q = e * s.S + (r - n);
-    opx = s.spx[q]; opy = s.spy[q]; orad = s.sradius[q]; otype = EBC_ADULT_STATIC;
-    valid = true;
-  }
+  const ObsRow row = obs_row(env_rows(s, e), r, n, ns);
   if (ob) {
     double *o = ob + g * 5;
-    o[0] = opx; o[1] = opy; o[2] = ovx; o[3] = ovy; o[4] = orad;
+    o[0] = row.px; o[1] = row.py; o[2] = row.vx; o[3] = row.vy; o[4] = row.radius;
   }
   if (obs) {
     float out[T];
-    if (valid) {
-      const RotFrame f = rot_frame(s.robot + e * 9, p.rotate_unicycle);
-      rotate_row<T>(f, opx, opy, ovx, ovy, orad, otype, out);
-    } else {
-#pragma unroll
-      for (int c = 0; c < T; ++c) out[c] = 0.0f;
-    }
+    RotFrame f = {};  // a row that does not exist needs no frame
+    if (row.valid) f = rot_frame(s.robot + e * 9, p.rotate_unicycle);
+    rotated_row_or_zeros<T>(f, row, out);
     float *o = obs + g * T;
 #pragma unroll
     for (int c = 0; c < T; ++c) o[c] = out[c];
@@ -1683,36 +1656,29 @@ __global__ __launch_bounds__(EBC_LA_THREADS) void lookahead_kernel(EbcParams p, 
   float *tile = reinterpret_cast<float *>(la_lds + (size_t)A * N * 8);  // [256][T]
 
   for (int r = tid; r < R; r += EBC_LA_THREADS) {
-    double o[5] = {0, 0, 0, 0, 0};
-    int t = 0;
-    if (r < n) {
+    ObsRow cur = obs_row(env_rows(s, (size_t)e), r, n, ns);
+    if (r < n) {  // a human: the current state stays for phase B1, the row moves on (Agent.step)
       const size_t k = (size_t)e * N + r;
-      const double px = s.px[k], py = s.py[k];
       double ax, ay;
       if (POLICY == EBC_HUMAN_LINEAR) {
-        linear_policy(px, py, s.gx[k], s.gy[k], s.v_pref[k], ax, ay);
+        linear_policy(cur.px, cur.py, s.gx[k], s.gy[k], s.v_pref[k], ax, ay);
         s.hact[k * 2] = ax;  // cache for a following EBC_HUMAN_CACHED step
         s.hact[k * 2 + 1] = ay;
       } else {
         ax = s.hact[k * 2];
         ay = s.hact[k * 2 + 1];
       }
-      hpx[r] = px; hpy[r] = py; hvx[r] = s.vx[k]; hvy[r] = s.vy[k];
-      hrad[r] = s.radius[k]; htype[r] = s.type[k];
-      o[0] = px + ax * dt;
-      o[1] = py + ay * dt;
-      o[2] = ax;
-      o[3] = ay;
-      o[4] = hrad[r];
-      t = htype[r];
-    } else if (r - n < ns) {
-      const size_t q = (size_t)e * S + (r - n);
-      o[0] = s.spx[q]; o[1] = s.spy[q]; o[4] = s.sradius[q];
-      t = EBC_ADULT_STATIC;
+      hpx[r] = cur.px; hpy[r] = cur.py; hvx[r] = cur.vx; hvy[r] = cur.vy;
+      hrad[r] = cur.radius; htype[r] = (uint8_t)cur.type;
+      cur.px = cur.px + ax * dt;
+      cur.py = cur.py + ay * dt;
+      cur.vx = ax;
+      cur.vy = ay;
     }
+    const double o[5] = {cur.px, cur.py, cur.vx, cur.vy, cur.radius};
 #pragma unroll
     for (int c = 0; c < 5; ++c) row[r][c] = o[c];
-    row_type[r] = (uint8_t)t;
+    row_type[r] = (uint8_t)cur.type;
     if (io.next_ob) {
       double *dst = io.next_ob + ((size_t)e * R + r) * 5;
 #pragma unroll
@@ -1726,13 +1692,7 @@ __global__ __launch_bounds__(EBC_LA_THREADS) void lookahead_kernel(EbcParams p, 
     const int a = q / n, j = q - a * n;
     const double a0 = io.actions[2 * a], a1 = io.actions[2 * a + 1];
     double rvx, rvy;
-    if (p.robot_kinematics == EBC_HOLONOMIC) {
-      rvx = a0;
-      rvy = a1;
-    } else {
-      rvx = a0 * cos(a1 + rb[8]);
-      rvy = a0 * sin(a1 + rb[8]);
-    }
+    swept_robot_velocity(p.robot_kinematics, a0, a1, rb[8], rvx, rvy);
     dist[a * N + j] = closest_dist(hpx[j], hpy[j], hvx[j], hvy[j], hrad[j], rb[0], rb[1], rb[4], rvx, rvy, dt);
   }
   __syncthreads();
@@ -1742,31 +1702,22 @@ __global__ __launch_bounds__(EBC_LA_THREADS) void lookahead_kernel(EbcParams p, 
   const int grid_slot = s.pool.grid ? s.grid_scene[e] : 0;
   for (int a = tid; a < A; a += EBC_LA_THREADS) {
     const double a0 = io.actions[2 * a], a1 = io.actions[2 * a + 1];
-    double dm0 = INFINITY, dm1 = INFINITY, dm2 = INFINITY;
-    int c0 = 0, c1 = 0, c2 = 0;
-    for (int j = 0; j < n; ++j) {  // index order, break at the first hit per type (env.py:303-313)
-      const int t = htype[j];
-      const double d = dist[a * N + j];
-      const bool hit = d < 0;
-      if (t == 0 && !c0) { c0 = hit; dm0 = (!hit && d < dm0) ? d : dm0; }
-      if (t == 1 && !c1) { c1 = hit; dm1 = (!hit && d < dm1) ? d : dm1; }
-      if (t == 2 && !c2) { c2 = hit; dm2 = (!hit && d < dm2) ? d : dm2; }
-    }
-    const double dmin[3] = {dm0, dm1, dm2};
+    TypeWalk w;
+    for (int j = 0; j < n; ++j) w.visit(dist[a * N + j], htype[j]);  // index order (env.py:303-313)
     double nx, ny;
     robot_next_position(rb, p.robot_kinematics, a0, a1, dt, nx, ny);
-    int coll[4] = {c0, c1, c2, 0};
+    int coll[4] = {w.coll[0], w.coll[1], w.coll[2], 0};
     coll[3] = grid_collision(s.pool.grid ? s.pool.grid + (size_t)grid_slot * s.G * 2 : nullptr, s.G, p.map_size_m,
                              p.map_resolution, nx, ny, rb[4], io.has_border ? io.border : nullptr);
-    const RewardOut ro = reward_compute(p, nx, ny, rb[5], rb[6], rb[4], a1, gtime, dmin, coll);
+    const RewardOut ro = reward_compute(p, nx, ny, rb[5], rb[6], rb[4], a1, gtime, w.dmin, coll);
     const size_t o = (size_t)e * A + a;
     if (io.reward) io.reward[o] = ro.reward;
     if (io.done) io.done[o] = (uint8_t)ro.done;
     if (io.info) io.info[o] = (uint8_t)ro.info;
     if (io.dmin) {
-      io.dmin[3 * o] = dm0;
-      io.dmin[3 * o + 1] = dm1;
-      io.dmin[3 * o + 2] = dm2;
+      io.dmin[3 * o] = w.dmin[0];
+      io.dmin[3 * o + 1] = w.dmin[1];
+      io.dmin[3 * o + 2] = w.dmin[2];
     }
     if (io.rows) {
       // CADRL.propagate for the robot (cadrl.py:118-165)
@@ -1793,7 +1744,9 @@ __global__ __launch_bounds__(EBC_LA_THREADS) void lookahead_kernel(EbcParams p, 
   if (!io.rows) return;
   __syncthreads();
 
-  // phase C
+  // phase C: rotated_row_or_zeros and flush_rows (ebc_step_rules.h), restated.  This loop writes the 400 MB that bound
+  // the sweep, and with the two calls in place of the copies the sweep measured 1.5 - 5 % slower
+  // (profiles/step_rules_refactor.txt).  The head is taken from the float index: io.rows is 16-byte aligned.
   const int total_rows = A * R;
   const size_t env_base = (size_t)e * total_rows * T;  // in floats
   for (int c0 = 0; c0 < total_rows; c0 += EBC_LA_THREADS) {

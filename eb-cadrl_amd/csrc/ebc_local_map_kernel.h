@@ -53,11 +53,8 @@ __global__ __launch_bounds__(EBC_WAVE) void local_map_kernel(EbcParams p, DevSta
 #pragma unroll
   for (int q = 0; q < 9; ++q) rb[q] = s.robot[(size_t)e * 9 + q];
   if (io.next) {  // the robot's next state, as every role of the step works it out (robot_action / robot_advance)
-    StepIO sio = {};
-    sio.robot_policy = io.robot_policy;
-    sio.robot_action = io.robot_action;
     double a0, a1;
-    robot_action(sio, (size_t)e, rb, a0, a1);
+    robot_action(io.robot_policy, io.robot_action, (size_t)e, rb, a0, a1);
     robot_advance(p, rb, a0, a1);
   }
   const double px = rb[0], py = rb[1], radius = rb[4], theta = rb[8];

@@ -21,13 +21,17 @@
 //   P3a  a thread per human: move, first arrival, next tile record, its obs_rotated[k] row; static and padding rows
 //   P3b  (only in a workgroup where an env ended under auto-reset, behind a third barrier) the restart scene
 //
-// What is shared and what is restated.  The leaf arithmetic is called, not copied: orca_group, orca_pref_velocity /
-// orca_pref_from, closest_dist, grid_collision, reward_compute, linear_policy, robot_advance, rot_frame, rotate_row.
-// Restated here, because the per-step bodies read DevState arrays in global memory and their instruction sequence is
-// the measured headline (ebc_kernels.h is not touched by this form): the row set-up and persistent-simulator rule of
-// orca_robot_kernel, orca_tile_load + orca_wave_compute, the ordered per-type reduce of env_lane_role, and the
-// commit / restart of state_role with the pool-cursor walk.  Each block below names the function it restates; a
-// change to one of those has to be made here too, and the raw-byte tests fail on the GPU when it is not.
+// What is shared.  The leaf arithmetic (orca_group, closest_dist, grid_collision, reward_compute, rot_frame, ...) and
+// the step rules around it are called, not copied; the rules take values and plain pointers, and here they get the LDS
+// state.  From ebc_step_rules.h: swept_robot_velocity, TypeWalk (the ordered per-type walk), store_outcome, obs_row +
+// rotated_row_or_zeros (every row of state_rotated and obs_rotated, and the rows the SAIL network reads), flush_rows,
+// restart_human and pool_next_cursor.  From ebc_kernels.h: robot_action, orca_robot_solve (the robot's ORCA with the
+// persistent-simulator rule, as orca_robot_kernel and dagger_label_kernel call it) and orca_tile_load +
+// orca_wave_compute (a human's ORCA, as the ORCA role of the per-step launch calls it).  What stays written out here
+// is what only this form does: the moved human's commit on LDS arrays (P3a) and the copies between global memory and
+// LDS.  The per-step kernels keep copies of some rules (the comments there name them): their emitted code is the
+// measured headline and a call moves it.  So a change to one of those rules is made in ebc_step_rules.h and at the
+// copies that name it, and tests/test_step_k_one_launch_gpu.py compares the two forms byte for byte.
 //
 // The arithmetic is that of the per-step form, operation for operation (ebc_device.h, ebc_orca_group.h; the unit is
 // built with -ffp-contract=off): what the per-step kernels compute across several waves and launches is computed
@@ -129,25 +133,10 @@ struct RolloutScratch {
   static constexpr unsigned BYTES = A > B ? A : B;
 };
 
-// `cnt` floats of an LDS row buffer -> dst, in flat order: 16-byte stores between the first and the last 16-byte
-// boundary of the destination (a row's 4 T bytes are not a multiple of 16: see lookahead_kernel, phase C).
-__device__ __forceinline__ void rollout_flush_rows(const float *buf, float *dst, int cnt, int tid) {
-  int head = (int)(((16 - ((size_t)dst & 15)) & 15) >> 2);
-  head = head < cnt ? head : cnt;
-  if (tid < head) dst[tid] = buf[tid];
-  const int body4 = (cnt - head) / 4;
-  typedef float f32x4 __attribute__((ext_vector_type(4)));
-  for (int v = tid; v < body4; v += EBC_RO_THREADS) {
-    const int f = head + 4 * v;
-    const f32x4 w = {buf[f], buf[f + 1], buf[f + 2], buf[f + 3]};
-    __builtin_nontemporal_store(w, reinterpret_cast<f32x4 *>(dst + f));  // nothing on the device reads the rows again
-  }
-  const int tail0 = head + 4 * body4;
-  if (tid < cnt - tail0) dst[tail0 + tid] = buf[tail0 + tid];
-}
-
-// the first T floats of a rotated row into an LDS row buffer
-__device__ __forceinline__ void rollout_put_row(float *dst, const float (&out)[EBC_RO_TMAX], int T) {
+// A row in frame f (or zeros) into an LDS row buffer: the first T floats of it
+__device__ __forceinline__ void rollout_put_row(float *dst, const RotFrame &f, const ObsRow &row, int T) {
+  float out[EBC_RO_TMAX];
+  rotated_row_or_zeros<EBC_RO_TMAX>(f, row, out);
 #pragma unroll
   for (int c = 0; c < EBC_RO_TMAX; ++c)
     if (c < T) dst[c] = out[c];
@@ -161,23 +150,17 @@ struct RolloutSail {
 };
 
 // Inputs of sail_group (ebc_sail.h) from the rollout kernel's LDS state: the rows ebc_observe's `ob` would hold
-// (observe_kernel: the humans, then the static obstacles with zero velocity, then zeros), cast once.
+// (obs_row), cast once.
 struct RolloutSailSrc {
-  const double *robot_base, *h_px, *h_py, *h_vx, *h_vy, *st_x, *st_y;
+  const double *robot_base;
+  EnvRows<int> rows;  // of the workgroup
   const int *n_h, *n_s;
   int N, S, el0;
   __device__ __forceinline__ const double *robot(int g) const { return robot_base + (el0 + g) * 9; }
   __device__ __forceinline__ float frame(int g, int i, int c) const {
-    const int el = el0 + g, n = n_h[el], ns = n_s[el];
-    double v = 0.0;
-    if (i < n) {
-      const int h = el * N + i;
-      v = c == 0 ? h_px[h] : c == 1 ? h_py[h] : c == 2 ? h_vx[h] : h_vy[h];
-    } else if (i - n < ns) {
-      const int q = el * S + (i - n);
-      v = c == 0 ? st_x[q] : c == 1 ? st_y[q] : 0.0;
-    }
-    return (float)v;
+    const int el = el0 + g;
+    const ObsRow o = obs_row(rows.at(el * N, el * S), i, n_h[el], n_s[el]);
+    return (float)(c == 0 ? o.px : c == 1 ? o.py : c == 2 ? o.vx : o.vy);
   }
 };
 
@@ -228,6 +211,10 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
   const ScenePool &P = s.pool;
   const double dt = p.time_step;
   const bool robot_orca = io.robot_policy == EBC_ROBOT_ORCA;
+  // the LDS state as the shared rules take it (el in place of the env index)
+  const EnvRows<int> lds_rows = {h_px, h_py, h_vx, h_vy, h_rad, h_type, st_x, st_y, st_r};
+  const RobotSim lds_sim = {io.sim.rows ? sim_rows : nullptr, sim_radius, sim_self};
+  const OrcaHot lds_hot = {E, N, s.n_magic, s.n_shift, tile, n_h};
 
   // ---- the envs' state: global memory -> LDS, once
   for (int q = tid; q < HN; q += EBC_RO_THREADS) {
@@ -276,20 +263,11 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
   for (int k = 0; k < io.K; ++k) {
     const size_t ke = (size_t)k * E + e0;  // first env of this workgroup in a [K][E] output
     // ================================================================ P1
-    if (k > 0 && io.obs_rotated) rollout_flush_rows(rows_obs, io.obs_rotated + (ke - E) * R * T, RN * T, tid);
-    if (io.state_rotated) {  // observe_kernel: rows of the current state in the robot's frame
+    if (k > 0 && io.obs_rotated) flush_rows<EBC_RO_THREADS>(rows_obs, io.obs_rotated + (ke - E) * R * T, RN * T, tid);
+    if (io.state_rotated) {  // rows of the current state in the robot's frame
       for (int q = tid; q < RN; q += EBC_RO_THREADS) {
         const int el = q / R, r = q - el * R;
-        const int n = n_h[el], ns = n_s[el];
-        float out[EBC_RO_TMAX] = {};  // a padding row is zeros
-        if (r < n) {
-          const int h = el * N + r;
-          rotate_row<EBC_RO_TMAX>(frame_cur[el], h_px[h], h_py[h], h_vx[h], h_vy[h], h_rad[h], h_type[h], out);
-        } else if (r - n < ns) {
-          const int g = el * S + (r - n);
-          rotate_row<EBC_RO_TMAX>(frame_cur[el], st_x[g], st_y[g], 0.0, 0.0, st_r[g], EBC_ADULT_STATIC, out);
-        }
-        rollout_put_row(rows_state + (size_t)q * T, out, T);
+        rollout_put_row(rows_state + (size_t)q * T, frame_cur[el], obs_row(lds_rows.at(el * N, el * S), r, n_h[el], n_s[el]), T);
       }
     }
     if constexpr (SAIL) {
@@ -298,7 +276,7 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
       const SailLds SL = sail_lds(reinterpret_cast<float *>(ro_lds + L.bytes), io.sail.chunk, io.sail.N);
       for (int c0 = 0; c0 < envs; c0 += io.sail.chunk) {
         const int ne = min(io.sail.chunk, envs - c0);
-        const RolloutSailSrc src = {robot, h_px, h_py, h_vx, h_vy, st_x, st_y, n_h, n_s, N, S, c0};
+        const RolloutSailSrc src = {robot, lds_rows, n_h, n_s, N, S, c0};
         sail_group<EBC_RO_WAVES>(io.sail.P, io.sail.N, SL, ne, src);
         const float *planned = SL.planned();
         for (int q = tid; q < ne * 2; q += EBC_RO_THREADS) {
@@ -313,74 +291,26 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
     if (wave == EBC_RO_WAVES - 1) {
       if (lane < envs && io.n_rows) io.n_rows[ke + lane] = (long long)n_h[lane] + n_s[lane];
       if (robot_orca) {
-        for (int pass = 0; pass < robot_passes; ++pass) {  // orca_robot_kernel, rows from LDS
-          using OL = OrcaLds<EBC_RO_RW>;
-          constexpr int EPW = EBC_WAVE / EBC_RO_RW;
-          float *dist_lds = reinterpret_cast<float *>(scratch);
-          float4 *lines_lds = reinterpret_cast<float4 *>(scratch + OL::DIST);
-          float4 *segs_lds = lines_lds + OL::GROUPS * OL::Sh::LINES;
-          float4 *proj_lds = segs_lds + OL::GROUPS * OL::Sh::LINES;
-          const int group = lane / EBC_RO_RW, j = lane - group * EBC_RO_RW;
-          const int el_raw = pass * EPW + group;
-          const bool e_ok = el_raw < envs;
-          const int el = e_ok ? el_raw : 0;
-          const int n = e_ok ? n_h[el] : 0, ns = e_ok ? n_s[el] : 0;
-          const double *rb = robot + el * 9;
-          const float posx = (float)rb[0], posy = (float)rb[1], velx = (float)rb[2], vely = (float)rb[3];
-          float radius = (float)(rb[4] + 0.01 + io.safety_space), maxSpeed = (float)rb[7];
-          float prefx, prefy;
-          orca_pref_velocity(rb[0], rb[1], rb[5], rb[6], prefx, prefy);
-          const bool valid = e_ok && j < n + ns;
-          float opx = 0, opy = 0, ovx = 0, ovy = 0, orad = 0;
-          if (valid && j < n) {
-            const int h = el * N + j;
-            opx = (float)h_px[h];
-            opy = (float)h_py[h];
-            ovx = (float)h_vx[h];
-            ovy = (float)h_vy[h];
-            orad = (float)(h_rad[h] + 0.01 + io.safety_space);
-          } else if (valid) {
-            const int g = el * S + (j - n);
-            opx = (float)st_x[g];
-            opy = (float)st_y[g];
-            orad = (float)(st_r[g] + 0.01 + io.safety_space);
-          }
-          if (io.sim.rows && e_ok) {
-            // every lane of the group reads the simulator's row count before lane 0 of the group replaces it (one wave)
-            const bool rebuild = sim_rows[el] != n + ns;
-            const int g = el * R + j;
-            if (rebuild) {
-              if (valid) sim_radius[g] = orad;
-              if (j == 0) {
-                sim_self[el] = make_float2(radius, maxSpeed);
-                sim_rows[el] = n + ns;
-              }
-            } else {
-              if (valid) orad = sim_radius[g];
-              const float2 me = sim_self[el];
-              radius = me.x;
-              maxSpeed = me.y;
-            }
-          }
+        for (int pass = 0; pass < robot_passes; ++pass) {  // orca_robot_kernel's solve: lane, robot, row and simulator from LDS
+          RobotLane l;
+          l.group = lane / EBC_RO_RW;
+          l.j = lane - l.group * EBC_RO_RW;
+          const int el = pass * (EBC_WAVE / EBC_RO_RW) + l.group;
+          l.e_ok = el < envs;
+          l.ee = l.e_ok ? (size_t)el : 0;
+          l.n = l.e_ok ? n_h[l.ee] : 0;
+          l.ns = l.e_ok ? n_s[l.ee] : 0;
+          const ObsRow row = obs_row(lds_rows.at(l.ee * N, l.ee * S), l.j, l.n, l.ns);
           float ox, oy;
-          orca_group<EBC_RO_RW>(p, j, group, valid, posx, posy, velx, vely, radius, maxSpeed, prefx, prefy, opx, opy, ovx, ovy,
-                                orad, dist_lds + group * OL::Sh::DIST, lines_lds + group * OL::Sh::LINES,
-                                segs_lds + group * OL::Sh::LINES, proj_lds + group * OL::Sh::LINES, N + S, s.range_sq,
-                                s.inv_time_horizon, s.inv_time_step, ox, oy);
-          if (e_ok && j == 0) {
-            act[2 * el] = (double)ox;  // getAgentVelocity -> Python float
-            act[2 * el + 1] = (double)oy;
+          orca_robot_solve<EBC_RO_RW>(p, s, io.safety_space, lds_sim, scratch, l, robot + l.ee * 9, row, ox, oy);
+          if (l.e_ok && l.j == 0) {
+            act[2 * l.ee] = (double)ox;  // getAgentVelocity -> Python float
+            act[2 * l.ee + 1] = (double)oy;
           }
         }
-      } else if (!SAIL && lane < envs) {  // robot_action(): env.py:388-392
-        const double *rb = robot + lane * 9;
+      } else if (!SAIL && lane < envs) {
         double a0, a1;
-        if (io.robot_policy == EBC_ROBOT_LINEAR) {
-          linear_policy(rb[0], rb[1], rb[5], rb[6], rb[7], a0, a1);
-        } else {
-          a0 = io.robot_action[2 * (ke + lane)];
-          a1 = io.robot_action[2 * (ke + lane) + 1];
-        }
+        robot_action(io.robot_policy, io.robot_action, ke + lane, robot + lane * 9, a0, a1);
         act[2 * lane] = a0;
         act[2 * lane + 1] = a1;
       }
@@ -390,13 +320,7 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
         const double *rb = robot + el * 9;
         const double a0 = act[2 * el], a1 = act[2 * el + 1];
         double rvx, rvy;
-        if (p.robot_kinematics == EBC_HOLONOMIC) {
-          rvx = a0;
-          rvy = a1;
-        } else {
-          rvx = a0 * cos(a1 + rb[8]);
-          rvy = a0 * sin(a1 + rb[8]);
-        }
+        swept_robot_velocity(p.robot_kinematics, a0, a1, rb[8], rvx, rvy);
         dist[q] = i < n_h[el] ? closest_dist(h_px[q], h_py[q], h_vx[q], h_vy[q], h_rad[q], rb[0], rb[1], rb[4], rvx, rvy, dt) : 0.0;
       }
       wave_sync();  // dist
@@ -407,41 +331,14 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
         for (int c = 0; c < 9; ++c) rn[c] = rb[c] = robot[el * 9 + c];
         const double a0 = act[2 * el], a1 = act[2 * el + 1];
         robot_advance(p, rn, a0, a1);
-        // compute_collisions (env.py:303-338): per type in index order, break at the first hit (env_lane_role's
-        // walk and ordered combination of its quarters, as one walk)
-        double fm[3] = {INFINITY, INFINITY, INFINITY};
-        int fc[3] = {0, 0, 0};
-        const int n = n_h[el];
-        for (int i = 0; i < n; ++i) {
-          const double d = dist[el * N + i];
-          const int t = h_type[el * N + i];
-#pragma unroll
-          for (int q = 0; q < 3; ++q) {
-            if (t == q && !fc[q]) {
-              if (d < 0) fc[q] = 1;
-              else if (d < fm[q]) fm[q] = d;
-            }
-          }
-        }
-        int c4[4] = {fc[0], fc[1], fc[2], 0};
+        TypeWalk w;  // env_lane_role's walk and ordered combination of its quarters, as one walk
+        for (int i = 0, n = n_h[el]; i < n; ++i) w.visit(dist[el * N + i], h_type[el * N + i]);
+        int c4[4] = {w.coll[0], w.coll[1], w.coll[2], 0};
         c4[3] = grid_collision(P.grid ? P.grid + (size_t)slot[el] * s.G * 2 : nullptr, s.G, p.map_size_m, p.map_resolution,
                                rn[0], rn[1], rb[4], nullptr);
         const double g_now = gtime[el];
-        const RewardOut ro = reward_compute(p, rn[0], rn[1], rb[5], rb[6], rb[4], a1, g_now, fm, c4);
-        const size_t o = ke + el;
-        if (io.reward) io.reward[o] = ro.reward;
-        if (io.done) io.done[o] = (uint8_t)ro.done;
-        if (io.info) io.info[o] = (uint8_t)ro.info;
-        if (io.dmin) {
-          io.dmin[3 * o] = fm[0];
-          io.dmin[3 * o + 1] = fm[1];
-          io.dmin[3 * o + 2] = fm[2];
-        }
-        if (io.dist_to_goal) io.dist_to_goal[o] = ro.dist_to_goal;
-        if (io.robot_action_out) {
-          io.robot_action_out[2 * o] = a0;
-          io.robot_action_out[2 * o + 1] = a1;
-        }
+        const RewardOut ro = reward_compute(p, rn[0], rn[1], rb[5], rb[6], rb[4], a1, g_now, w.dmin, c4);
+        store_outcome(io, ke + el, ro, w.dmin, a0, a1);
 #pragma unroll
         for (int c = 0; c < 9; ++c) robot_next[el * 9 + c] = rn[c];
         if (io.obs_rotated || io.state_rotated) frame_next[el] = rot_frame(rn, p.rotate_unicycle);
@@ -450,56 +347,23 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
         tnew[el] = g_now + dt;
       }
     }
-    for (int hp = 0; hp < human_passes; ++hp) {  // orca_tile_load + orca_wave_compute, tile and robot from LDS
+    for (int hp = 0; hp < human_passes; ++hp) {  // the humans' ORCA, tile and robot from LDS
       if (hp % orca_waves != wave) continue;
-      using OL = OrcaLds<GS>;
       constexpr int HPW = EBC_WAVE / GS;
-      float *dist_lds = reinterpret_cast<float *>(scratch);
-      float4 *lines_lds = reinterpret_cast<float4 *>(scratch + OL::DIST);
-      float4 *segs_lds = lines_lds + OL::GROUPS * OL::Sh::LINES;
-      float4 *proj_lds = segs_lds + OL::GROUPS * OL::Sh::LINES;
       const int group = lane / GS, j = lane - group * GS;
       const int u = hp * HPW + group;           // human of this workgroup: el * N + i
       const bool h_ok = group < HPW && u < HN;  // lanes past HPW * GS idle
       const int el = h_ok ? u / N : 0;
       const int i = h_ok ? u - el * N : 0;
-      const int n = h_ok ? n_h[el] : 0;
-      const int base = el * N;
-      const int ks = base + i;
-      const int oj = j < i ? j : j + 1;  // humans before / after this one
-      const int ko = base + (oj < N ? oj : N - 1);
-      float4 ta = make_float4(0, 0, 0, 0), tb = ta, tc = ta;
-      float orad = 0;
-      if (h_ok) {
-        ta = tile[2 * ks];
-        tb = tile[2 * ks + 1];
-        tc = tile[2 * ko];
-        orad = tile[2 * ko + 1].x;
-      }
-      const bool human_ok = h_ok && i < n;
-      const float posx = ta.x, posy = ta.y, velx = ta.z, vely = ta.w;
-      const float radius = tb.x, maxSpeed = tb.y, prefx = tb.z, prefy = tb.w;
-      float opx = tc.x, opy = tc.y, ovx = tc.z, ovy = tc.w;
-      const int n_others = human_ok ? (n - 1 + (p.robot_visible ? 1 : 0)) : 0;
-      const bool valid = j < n_others;
-      if (p.robot_visible && valid && j == n - 1) {  // the robot, last in ob (env.py:401-402)
-        const double *rb = robot + el * 9;
-        opx = (float)rb[0];
-        opy = (float)rb[1];
-        ovx = (float)rb[2];
-        ovy = (float)rb[3];
-        orad = (float)(rb[4] + 0.01 + p.orca_safety_space);
-      }
+      const OrcaTile t = orca_tile_load<GS>(lds_hot, h_ok, el, i);
       float ox, oy;
-      orca_group<GS>(p, j, group, valid, posx, posy, velx, vely, radius, maxSpeed, prefx, prefy, opx, opy, ovx, ovy, orad,
-                     dist_lds + group * OL::Sh::DIST, lines_lds + group * OL::Sh::LINES, segs_lds + group * OL::Sh::LINES,
-                     proj_lds + group * OL::Sh::LINES, N - 1 + (p.robot_visible ? 1 : 0), s.range_sq, s.inv_time_horizon,
-                     s.inv_time_step, ox, oy);
+      bool human_ok;
+      orca_wave_compute<GS>(p, s, N, t, [&] { return robot + el * 9; }, h_ok, i, scratch, ox, oy, human_ok);
       if (h_ok && j == 0) vel[u] = make_float2(human_ok ? ox : 0.0f, human_ok ? oy : 0.0f);
     }
     __syncthreads();
     // ================================================================ P3a
-    if (io.state_rotated) rollout_flush_rows(rows_state, io.state_rotated + ke * R * T, RN * T, tid);
+    if (io.state_rotated) flush_rows<EBC_RO_THREADS>(rows_state, io.state_rotated + ke * R * T, RN * T, tid);
     bool any_restore = false;
     for (int el = 0; el < envs; ++el) any_restore = any_restore || restore[el];  // the same answer in every thread
     for (int q = tid; q < HN; q += EBC_RO_THREADS) {
@@ -510,11 +374,8 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
       const double ax = (double)vel[q].x, ay = (double)vel[q].y;  // getAgentVelocity -> Python float
       const double px = h_px[q] + ax * dt, py = h_py[q] + ay * dt;
       const double rad = h_rad[q];
-      if (io.obs_rotated) {
-        float out[EBC_RO_TMAX];
-        rotate_row<EBC_RO_TMAX>(frame_next[el], px, py, ax, ay, rad, h_type[q], out);
-        rollout_put_row(rows_obs + (size_t)(el * R + i) * T, out, T);
-      }
+      if (io.obs_rotated)
+        rollout_put_row(rows_obs + (size_t)(el * R + i) * T, frame_next[el], ObsRow{px, py, ax, ay, rad, h_type[q], true}, T);
       if (!restore[el]) {
         const double dx = h_gx[q] - px, dy = h_gy[q] - py;
         const double dg = norm2(dx, dy);
@@ -529,14 +390,9 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
     if (io.obs_rotated) {  // static obstacles as pedestrians (env.py:457-458) and the padding rows
       for (int q = tid; q < RN; q += EBC_RO_THREADS) {
         const int el = q / R, r = q - el * R;
-        const int n = n_h[el], ns = n_s[el];
-        if (r < n) continue;
-        float out[EBC_RO_TMAX] = {};
-        if (r - n < ns) {
-          const int g = el * S + (r - n);
-          rotate_row<EBC_RO_TMAX>(frame_next[el], st_x[g], st_y[g], 0.0, 0.0, st_r[g], EBC_ADULT_STATIC, out);
-        }
-        rollout_put_row(rows_obs + (size_t)q * T, out, T);
+        const int n = n_h[el];
+        if (r < n) continue;  // a human's row: above, moved
+        rollout_put_row(rows_obs + (size_t)q * T, frame_next[el], obs_row(lds_rows.at(el * N, el * S), r, n, n_s[el]), T);
       }
     }
     if (tid < envs) {
@@ -556,26 +412,13 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
       for (int q = tid; q < HN; q += EBC_RO_THREADS) {
         const int el = q / N, i = q - el * N;
         if (!restore[el]) continue;
-        const int cur = slot[el];
-        const size_t src = (size_t)cur * N + i;
-        const bool live = i < P.n_humans[cur];
-        const double npx = live ? P.px[src] : 0.0, npy = live ? P.py[src] : 0.0;
-        const double nvx = live ? P.vx[src] : 0.0, nvy = live ? P.vy[src] : 0.0;
-        const double nrad = live ? P.radius[src] : 0.0, nvp = live ? P.v_pref[src] : 0.0;
-        h_px[q] = npx; h_py[q] = npy; h_vx[q] = nvx; h_vy[q] = nvy;
-        h_gx[q] = live ? P.gx[src] : 0.0;
-        h_gy[q] = live ? P.gy[src] : 0.0;
-        h_rad[q] = nrad; h_vpref[q] = nvp;
+        const RestartHuman h = restart_human(p, P, N, slot[el], i);
+        h_px[q] = h.px; h_py[q] = h.py; h_vx[q] = h.vx; h_vy[q] = h.vy;
+        h_gx[q] = h.gx; h_gy[q] = h.gy; h_rad[q] = h.radius; h_vpref[q] = h.v_pref;
         h_arr[q] = 0.0;
-        h_type[q] = live ? (int)P.type[src] : 0;
-        if (live) {
-          const float2 rp = P.pref[src];
-          tile[2 * q] = make_float4((float)npx, (float)npy, (float)nvx, (float)nvy);
-          tile[2 * q + 1] = make_float4((float)(nrad + 0.01 + p.orca_safety_space), (float)nvp, rp.x, rp.y);
-        } else {
-          tile[2 * q] = make_float4(0, 0, 0, 0);
-          tile[2 * q + 1] = make_float4(0, 0, 0, 0);
-        }
+        h_type[q] = h.type;
+        tile[2 * q] = h.tile0;
+        tile[2 * q + 1] = h.tile1;
       }
       for (int q = tid; q < SN; q += EBC_RO_THREADS) {
         const int el = q / S, r = q - el * S;
@@ -591,15 +434,12 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
         for (int c = 0; c < 9; ++c) robot[tid * 9 + c] = P.robot[(size_t)cur * 9 + c];
         gtime[tid] = 0.0;
         if (io.state_rotated) frame_cur[tid] = rot_frame(robot + tid * 9, p.rotate_unicycle);
-        if (P.P > 0) {  // walk the custom pool; without one the env keeps restarting from its own slot
-          const int nxt = cur - E + P.stride;
-          cursor[tid] = E + (nxt >= P.P ? nxt % P.P : nxt);
-        }
+        if (P.P > 0) cursor[tid] = pool_next_cursor(P, E, cur);  // without a custom pool the env keeps restarting from its own slot
       }
     }
     __syncthreads();
   }
-  if (io.obs_rotated) rollout_flush_rows(rows_obs, io.obs_rotated + ((size_t)(io.K - 1) * E + e0) * R * T, RN * T, tid);
+  if (io.obs_rotated) flush_rows<EBC_RO_THREADS>(rows_obs, io.obs_rotated + ((size_t)(io.K - 1) * E + e0) * R * T, RN * T, tid);
 
   // ---- LDS -> global memory, once: what K per-step steps would have left
   for (int q = tid; q < HN; q += EBC_RO_THREADS) {

@@ -162,6 +162,86 @@ def test_one_launch_full_size_vs_oracle():
         np.testing.assert_allclose(sg[k], so[k], atol=1e-9, rtol=0, err_msg=k)
 
 
+def _placed_batch(n_humans, n_static, N, S, shift):
+    """Scenes placed by hand, free maps.  Robot e starts at (0.1 e, -3) for (0, 3).  Its humans stand 2 m from it on the
+    side of its goal, walk towards it at 0.3 m/s and want to pass it; its static obstacles stand 2.5 m behind it.  Every
+    radius is its own (and `shift` larger), so a simulator that kept its radii shows which scene built it.  Within the
+    0.5 s before the time-out nothing can touch: the gap is 2 m - 0.3 - radius (at most 0.4 + shift), the closing speed
+    at most 1 + 0.7 m/s."""
+    E = len(n_humans)
+    f = lambda *s: np.zeros(s)  # noqa: E731
+    b = ebc_scene.SceneBatch(E, N, S, np.asarray(n_humans, np.int32), f(E, N), f(E, N), f(E, N), f(E, N), f(E, N), f(E, N),
+                             f(E, N), f(E, N), np.zeros((E, N), np.uint8), np.asarray(n_static, np.int32),
+                             f(E, max(S, 1)), f(E, max(S, 1)), f(E, max(S, 1)), None, f(E, 9))
+    for e in range(E):
+        rx, ry = 0.1 * e, -3.0
+        b.robot[e] = [rx, ry, 0, 0, 0.3, 0.0, 3.0, 0.7, np.pi / 2]
+        for i in range(n_humans[e]):
+            th = 0.5 + 0.9 * i + 0.05 * e
+            c, s = np.cos(th), np.sin(th)
+            b.px[e, i], b.py[e, i] = rx + 2.0 * c, ry + 2.0 * s
+            b.vx[e, i], b.vy[e, i] = -0.3 * c, -0.3 * s
+            b.gx[e, i], b.gy[e, i] = rx - 2.0 * c, ry - 2.0 * s
+            b.radius[e, i] = 0.2 + 0.05 * i + 0.01 * e + shift
+            b.v_pref[e, i] = 1.0
+        for j in range(n_static[e]):
+            ph = np.pi + 0.9 + 1.3 * j
+            b.spx[e, j], b.spy[e, j] = rx + 2.5 * np.cos(ph), ry + 2.5 * np.sin(ph)
+            b.sradius[e, j] = 0.3 + 0.1 * j + shift
+    return b
+
+
+def test_one_launch_robot_orca_persistent_simulator_vs_oracle(monkeypatch):
+    """The robot on ORCA with the persistent simulator, one launch against the oracle and nothing else: the one-launch
+    and the per-step form call the same orca_robot_solve, so their agreement no longer witnesses the simulator rule.
+    Five envs, two per workgroup (the last workgroup holds one), scenes placed by hand (_placed_batch: no seed decides
+    a row count or a collision).  Every env times out at the third step and restarts
+    from its pool scene: one of them onto another row count (the simulator is rebuilt), four onto the same (it keeps
+    the radii of the scene that built it); the fourth step is decided from those simulators.  The robot's action bit
+    for bit, as test_robot_orca_rollouts_vs_oracle holds the per-step kernel; the rest with the tolerances of
+    test_one_launch_equals_k_oracle_steps."""
+    from oracle import oracle
+    params, _ = _walls_params()
+    params.time_limit = 0.5
+    E, N, S, K = 5, 3, 2, 4
+    first = _placed_batch([3, 2, 3, 1, 2], [1, 2, 0, 2, 1], N, S, 0.0)
+    pool = _placed_batch([3, 2, 3, 1, 3], [1, 2, 0, 2, 1], N, S, 0.07)  # env e restarts from pool scene e: the last onto 4 rows, from 3
+    rows_first, rows_pool = first.n_humans + first.n_static, pool.n_humans + pool.n_static
+    assert int((rows_first != rows_pool).sum()) == 1
+    g = _env(params, E, N, S)
+    o = oracle.OracleEnv(params, E, N, S)
+    for x in (g, o):
+        x.reset(first)
+        x.set_scene_pool(pool)
+        x.robot_orca_sim(True)
+    monkeypatch.setenv("EBCSIM_ONE_LAUNCH_EPG", "2")
+    kw = _robot_kw("orca", K, E, 0.7)
+    og = g.step_k(K, KEYS9, flags=AUTO | ONE, **kw)
+    oo = o.step_k(K, KEYS9, flags=AUTO, **kw)
+    assert oo["done"][2].all() and not oo["done"][:2].any()  # the restarts lie inside the launch, a step before its end
+    for k in ("done", "info", "n_rows"):
+        np.testing.assert_array_equal(og[k], oo[k], err_msg=k)
+    _bytes_equal(og["robot_action_out"], oo["robot_action_out"], "robot_action_out")
+    for k in ("reward", "dmin", "dist_to_goal"):
+        both_inf = np.isinf(og[k]) & np.isinf(oo[k])
+        np.testing.assert_allclose(np.where(both_inf, 0, og[k]), np.where(both_inf, 0, oo[k]), atol=1e-9, rtol=0, err_msg=k)
+    for k in ("state_rotated", "obs_rotated"):
+        np.testing.assert_allclose(og[k], oo[k], atol=1e-5, rtol=1e-5, err_msg=k)
+    sg, so = g.get_state(), o.get_state()
+    for k in sg:
+        np.testing.assert_allclose(sg[k], so[k], atol=1e-9, rtol=0, err_msg=k)
+    mg, mo = g.robot_orca_sim_state(), o.robot_orca_sim_state()
+    np.testing.assert_array_equal(mg["rows"], rows_pool)
+    np.testing.assert_array_equal(mg["rows"], mo["rows"])
+    _bytes_equal(mg["self"], mo["self"], "simulator self")
+    for e in range(E):  # the rows the simulator holds; what lies behind them is never read
+        _bytes_equal(mg["radius"][e, :rows_pool[e]], mo["radius"][e, :rows_pool[e]], "simulator radius of env %d" % e)
+    kept = np.flatnonzero(rows_first == rows_pool)
+    built_from = np.float32(first.radius[kept[0], 0] + 0.01 + 0.15)  # the first scene's human, not the pool scene's
+    assert mg["radius"][kept[0], 0] == built_from != np.float32(pool.radius[kept[0], 0] + 0.01 + 0.15)
+    g.synchronize()
+
+
 # ------------------------------------------------------------------ 2. equal to the per-step form, bit for bit
 @pytest.mark.parametrize("robot", ["orca", "linear", "external"])
 def test_bitwise_three_robots(robot):
