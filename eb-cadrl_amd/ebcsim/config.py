@@ -21,11 +21,19 @@ def _opt(cfg, section, key, default=_NAN):
     return default if v is None else v
 
 
-def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="sarl"):
+_HUMAN_ORCA = {"safety_space": "orca_safety_space", "neighbor_dist": "orca_neighbor_dist",
+               "max_neighbors": "orca_max_neighbors", "time_horizon": "orca_time_horizon"}
+
+
+def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="sarl", human_orca=None):
     """env_cfg / policy_cfg: RawConfigParser objects in the reference's schema.  policy: the robot's policy;
     "lstm_rl", "cadrl" and "sail" never read with_agent_type (rl/policy/lstm_rl.py:79-100, rl/policy/cadrl.py:66-82,
-    rl/policy/sail.py:109-112), so their rows are 13 wide whatever [sarl] says."""
+    rl/policy/sail.py:109-112), so their rows are 13 wide whatever [sarl] says.  human_orca: attributes of the humans'
+    ORCA policy objects by the reference's names (safety_space, neighbor_dist, max_neighbors, time_horizon), which no
+    config file sets (simulator/policy/orca.py:63-80): the defaults are that constructor's."""
     p = _abi.default_params()
+    for k, v in (human_orca or {}).items():
+        setattr(p, _HUMAN_ORCA[k], v)
     p.time_step = env_cfg.getfloat("env", "time_step")
     p.time_limit = env_cfg.getint("env", "time_limit")
     # env.configure itself raises without a [map] section (env.py:79); Reward alone does not

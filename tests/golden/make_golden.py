@@ -462,8 +462,10 @@ def ob_rows(ob):
 
 def run_trajectory(ref, name, env_path, overrides, policy_cfg, robot_mode, n_steps, seed_case,
                    kinematics=None, orca=False, lookahead_every=0, scene_json=None,
-                   stop_when_done=False, il_safety_space=0.0):
-    """Drive the reference env and record everything the kernels must reproduce."""
+                   stop_when_done=False, il_safety_space=0.0, human_orca=None):
+    """Drive the reference env and record everything the kernels must reproduce.  human_orca: attributes set on every
+    human's ORCA policy object after the reset that made the humans (the reference keeps time_horizon and safety_space
+    there, simulator/policy/orca.py:63-66, and reads no config for them); recorded in meta and in params."""
     import torch
     from simulator.utils.action import ActionXY, ActionRot
     from simulator.utils.state import JointState
@@ -480,6 +482,12 @@ def run_trajectory(ref, name, env_path, overrides, policy_cfg, robot_mode, n_ste
     if robot_mode == "orca":  # the imitation-learning demonstrator, rl/train.py:124-132
         pol.multiagent_training = True
         pol.safety_space = il_safety_space
+
+    def set_human_orca():  # the scene generator makes new humans, each with a policy object of its own, at every reset
+        for h in humans_of(env):
+            for k, v in (human_orca or {}).items():
+                assert hasattr(h.policy, k), k
+                setattr(h.policy, k, v)
     sarl = make_sarl(ref, policy_cfg, kinematics)   # rotate / transform / action space only
     sarl.time_step = cfg.getfloat("env", "time_step")
     kin = kinematics or "holonomic"
@@ -487,6 +495,7 @@ def run_trajectory(ref, name, env_path, overrides, policy_cfg, robot_mode, n_ste
         ret = env.reset("test", load_scene_path=os.path.join(ref, scene_json), compute_local_map=False)
     else:
         ret = env.reset("test", test_case=seed_case, compute_local_map=False)
+    set_human_orca()
     ob = ret[0]  # (ob, local_map), or (ob, obstacle_vertices, local_map) for an ORCA robot (env.py:201-204)
     assert len(ret) == (3 if robot_mode == "orca" else 2)
     sarl.build_action_space(robot.v_pref)
@@ -538,7 +547,8 @@ def run_trajectory(ref, name, env_path, overrides, policy_cfg, robot_mode, n_ste
         rec["rot"].append(sarl.transform(st).numpy())
         if stop_when_done and done:
             break
-    params = ebc_config.params_from_config(cfg, parsed(open(pol_path).read()), robot_kinematics=kin)
+    params = ebc_config.params_from_config(cfg, parsed(open(pol_path).read()), robot_kinematics=kin,
+                                           human_orca=human_orca)
     out = {("init_" + k): v for k, v in init.items()}
     for k, v in rec.items():
         out[k] = np.array(v)
@@ -565,6 +575,10 @@ def run_trajectory(ref, name, env_path, overrides, policy_cfg, robot_mode, n_ste
                          "human_policy": "orca(oracle-substituted rvo2)" if orca else "linear",
                          "seed_case": seed_case, "scene_json": scene_json, "kinematics": kin,
                          "final_info": int(rec["info"][-1])})
+    if human_orca:  # a key of its own, so that the meta of every other fixture keeps its bytes
+        meta = json.loads(str(out["meta"]))
+        meta["human_orca"] = human_orca
+        out["meta"] = jdump(meta)
     save(name, **out)
     RVO2_MODE["substitute"] = False
     return int(rec["info"][-1])
@@ -602,6 +616,23 @@ def gen_trajectories(ref):
     run_trajectory(ref, "traj_unicycle_rotpen", A5, rot,
                    "configs/policy_configs/policy_non_holonomic.config", "scripted", 40, 4,
                    kinematics="unicycle", lookahead_every=19)
+
+
+def gen_param_trajectories(ref):
+    """time_step, the humans' ORCA horizon and safety space off the values every other fixture has (0.25, 5, 0)."""
+    dt01 = {("env", "time_step"): 0.1}
+    # the reference end to end, no rvo2: the advance, closest_dist, the clock as a sum of inexact 0.1s and the step at
+    # which it passes time_limit, sarl.time_step in propagate and the look-ahead
+    slow = {("adults", "v_pref"): 0.2, ("env", "time_limit"): 3}
+    slow.update(dt01)
+    run_trajectory(ref, "traj_a5_linear_dt01", A5, slow, P1, "linear", 400, 2, lookahead_every=7, stop_when_done=True)
+    rot = {("adults", "v_pref"): 0.35, ("reward", "rotation_penalty_factor"): -0.004, ("env", "time_step"): 0.5}
+    run_trajectory(ref, "traj_unicycle_dt05", A5, rot, "configs/policy_configs/policy_non_holonomic.config", "scripted",
+                   30, 4, kinematics="unicycle", lookahead_every=19)
+    # what the reference hands to PyRVOSimulator / addAgent at its call site (orca.py:110-127); the arithmetic behind it
+    # is the restatement's
+    run_trajectory(ref, "traj_a3b3s2_dt01_orcasub", A3B3S2, dt01, P1, "scripted", 50, 3, orca=True, lookahead_every=23,
+                   human_orca={"time_horizon": 2, "safety_space": 0.1})
 
 
 IL_GAMMA = 0.9  # [rl] gamma of the shipped policy configs
@@ -914,7 +945,7 @@ def gen_local_map(ref):
 
 GENERATORS = {"collisions": gen_collisions, "reward": gen_reward, "grid": gen_grid,
               "rotate": gen_rotate, "action_space": gen_action_space, "scenes": gen_scenes,
-              "trajectories": gen_trajectories, "il": gen_il, "il_persistent": gen_il_persistent, "known": gen_known_answers, "sarl": gen_sarl, "sarl_rl": gen_sarl_rl_memory, "trainer": gen_trainer_steps, "sarl_configs": gen_sarl_configs,
+              "trajectories": gen_trajectories, "param_trajectories": gen_param_trajectories, "il": gen_il, "il_persistent": gen_il_persistent, "known": gen_known_answers, "sarl": gen_sarl, "sarl_rl": gen_sarl_rl_memory, "trainer": gen_trainer_steps, "sarl_configs": gen_sarl_configs,
               "local_map": gen_local_map}
 
 

@@ -50,9 +50,11 @@ def human_policy_of(z):
 
 
 TRAJ_PINNED = ["traj_a5_linear", "traj_a5_scripted", "traj_a3b3s2_scripted", "traj_n10_walls_t17",
-               "traj_unicycle_rotpen"]
+               "traj_unicycle_rotpen",
+               "traj_a5_linear_dt01", "traj_unicycle_dt05"]  # time_step 0.1 (to the time-out at 3 s) and 0.5
 TRAJ_ORCASUB = ["traj_a5_linear_orcasub", "traj_a5_scripted_orcasub",
-                "traj_a3b3s2_scripted_orcasub", "traj_n10_walls_t17_orcasub"]
+                "traj_a3b3s2_scripted_orcasub", "traj_n10_walls_t17_orcasub",
+                "traj_a3b3s2_dt01_orcasub"]  # time_step 0.1, the humans' horizon 2 and safety space 0.1
 # the imitation-learning demonstrator: the robot itself on ORCA (rl/train.py:99-143)
 TRAJ_IL = ["traj_a5_il_orcasub", "traj_n10_walls_il_orcasub"]
 
@@ -527,12 +529,25 @@ def orca_branch_batch(seed, N, lanes, S=0, robot_inside=False):
 
 # (humans, robot_visible): every group size, each both full and with spare lanes
 ORCA_HUMAN_COUNTS = [(n, 0) for n in (1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 17, 18, 22, 23, 33)] + [(10, 1), (32, 1)]
-# name -> (maxNeighbors, neighborDist)
-ORCA_PARAM_SETS = {"default": (10, 10.0), "mn3-nd2": (3, 2.0), "mn1": (1, 10.0), "mn0": (0, 10.0)}
+# name -> (maxNeighbors, neighborDist, time_step, orca_time_horizon, orca_safety_space); the last three default to
+# 0.25, 5 and 0, the values of every golden
+ORCA_PARAM_SETS = {"default": (10, 10.0), "mn3-nd2": (3, 2.0), "mn1": (1, 10.0), "mn0": (0, 10.0),
+                   "dt0.1": (10, 10.0, 0.1), "dt0.5": (10, 10.0, 0.5), "hor2": (10, 10.0, 0.25, 2.0),
+                   "hor0.5": (10, 10.0, 0.25, 0.5), "saf0.1": (10, 10.0, 0.25, 5.0, 0.1),
+                   "all": (3, 2.0, 0.1, 2.0, 0.1)}
+ORCA_PARAM_SETS = {k: v + (0.25, 5.0, 0.0)[len(v) - 2:] for k, v in ORCA_PARAM_SETS.items()}
+# the sets that move time_step, the ORCA horizon or the humans' safety space off the default, and where they run: the
+# smallest group, a 5-lane group, the visible robot twice (the safety space goes onto ITS radius there), a group above ten
+# others, the 32-lane group with 33 agents
+ORCA_MOVED_SETS = ("dt0.1", "dt0.5", "hor2", "hor0.5", "saf0.1", "all")
+ORCA_MOVED_COUNTS = [(2, 0), (6, 0), (10, 1), (14, 0), (32, 1)]
 ORCA_HUMAN_CASES = ([(n, rv, ps) for n, rv in ORCA_HUMAN_COUNTS for ps in ("default", "mn3-nd2")]
-                    + [(n, 0, ps) for n in (6, 13) for ps in ("mn1", "mn0")])
+                    + [(n, 0, ps) for n in (6, 13) for ps in ("mn1", "mn0")]
+                    + [(n, rv, ps) for n, rv in ORCA_MOVED_COUNTS for ps in ORCA_MOVED_SETS])
 # (humans, static rows) of the robot's own ORCA: rows 1..13, 16, 17, 21, 22, 32
 ORCA_ROBOT_CASES = [(r, 0) for r in (1, 2, 3, 4, 5, 6, 7, 8, 9, 11, 12, 13, 16, 17, 22)] + [(6, 4), (10, 11), (20, 12)]
+# the robot's own solve under a handle whose safety space (the humans', 0.1) is not the robot's (0 / 0.15)
+ORCA_ROBOT_MOVED_CASES = [(n, s, ps) for n, s in ((5, 0), (6, 4), (20, 12)) for ps in ("saf0.1", "all")]
 ORCA_STEPS = 3
 
 
@@ -540,10 +555,15 @@ def orca_case_id(case):
     return "N%d%s-%s" % (case[0], "+robot" if case[1] else "", case[2]) if len(case) == 3 else "N%d-S%d" % case
 
 
+def orca_robot_case_id(case):
+    return "N%d-S%d" % case[:2] + "".join("-" + ps for ps in case[2:])
+
+
 def orca_case_params(rv=0, param_set="default"):
-    params = params_of(load("traj_n10_walls_t17_orcasub"))  # time_step 0.25, horizon 5
+    params = params_of(load("traj_n10_walls_t17_orcasub"))
     params.robot_visible = rv
-    params.orca_max_neighbors, params.orca_neighbor_dist = ORCA_PARAM_SETS[param_set]
+    (params.orca_max_neighbors, params.orca_neighbor_dist, params.time_step, params.orca_time_horizon,
+     params.orca_safety_space) = ORCA_PARAM_SETS[param_set]
     return params
 
 
@@ -599,10 +619,11 @@ def orca_reference(case, library=None):
 
 
 def orca_robot_reference(case, safety, library=None):
+    """robot_orca(safety) of a case (N, S), or (N, S, parameter set) of ORCA_ROBOT_MOVED_CASES, from reset."""
     from oracle import oracle
-    N, S = case
+    N, S = case[:2]
     b = orca_robot_batch(N, S)
-    o = oracle.OracleEnv(orca_case_params(), b.n, N, S, library=library)
+    o = oracle.OracleEnv(orca_case_params(0, *case[2:]), b.n, N, S, library=library)
     o.reset(b)
     return o.robot_orca(safety)
 

@@ -158,7 +158,8 @@ def test_known_answer_scenes_cpu_backend():
 
 
 @pytest.mark.parametrize("name", ["traj_a5_scripted", "traj_a3b3s2_scripted_orcasub",
-                                  "traj_unicycle_rotpen", "traj_n10_walls_t17_orcasub"])
+                                  "traj_unicycle_rotpen", "traj_n10_walls_t17_orcasub",
+                                  "traj_a5_linear_dt01", "traj_unicycle_dt05"])
 def test_golden_trajectory_cpu_backend(name):
     _golden_trajectory(name, _oracle_backend)
 
@@ -171,7 +172,7 @@ def test_known_answer_scenes_gpu():
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", ["traj_a5_scripted", "traj_a3b3s2_scripted_orcasub",
                                   "traj_unicycle_rotpen", "traj_n10_walls_t17_orcasub",
-                                  "traj_a5_linear_orcasub"])
+                                  "traj_a5_linear_orcasub", "traj_a5_linear_dt01", "traj_unicycle_dt05"])
 def test_golden_trajectory_gpu(name):
     _golden_trajectory(name, None)
 

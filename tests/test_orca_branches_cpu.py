@@ -8,14 +8,20 @@ Two conditions cannot hold at the smallest counts and are asked from where they 
 ORCA line at all (asserted: every agent there has zero neighbours), and an exact distance tie needs two others (N >= 3,
 or N = 2 with a visible robot).
 
+The sets that move time_step, orca_time_horizon and orca_safety_space off the values of every golden (0.25, 5, 0) are
+asked two more things: that at least a tenth of the humans get another first velocity than under the default set (else a
+kernel that ignored the field would go unnoticed), and that the colliding branch (invTimeStep) and the cut-off circle and
+both legs (invTimeHorizon) are still reached.
+
 The table of counts goes to profiles/orca_branch_coverage.txt between its BEGIN / END markers."""
 import os
 
 import numpy as np
 import pytest
 
-from helpers import (ORCA_HUMAN_CASES, ORCA_HUMAN_COUNTS, ORCA_ROBOT_CASES, ORCA_STEPS, orca_case_id, orca_case_params,
-                     orca_human_batch, orca_reference, orca_robot_batch, orca_robot_reference)
+from helpers import (ORCA_HUMAN_CASES, ORCA_HUMAN_COUNTS, ORCA_MOVED_SETS, ORCA_PARAM_SETS, ORCA_ROBOT_CASES,
+                     ORCA_ROBOT_MOVED_CASES, ORCA_STEPS, orca_case_id, orca_case_params, orca_human_batch, orca_reference,
+                     orca_robot_batch, orca_robot_case_id, orca_robot_reference)
 from oracle import oracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -75,7 +81,7 @@ def coverage(traced):
         c["tie_agents"], c["twin_agents"] = _ties_and_nan_inputs(orca_human_batch(N, rv), rv,
                                                                  orca_case_params(rv, ps).orca_neighbor_dist)
         human[case] = c
-    for case in ORCA_ROBOT_CASES:
+    for case in ORCA_ROBOT_CASES + ORCA_ROBOT_MOVED_CASES:
         pooled = {}
         for safety in SAFETIES:
             plain = orca_robot_reference(case, safety)
@@ -113,17 +119,17 @@ def test_every_human_count_reaches_the_branches(coverage, N, rv):
         assert c["nb_truncated"] >= 1, c
 
 
-@pytest.mark.parametrize("case", [c for c in ORCA_HUMAN_CASES if c[2] != "default"], ids=orca_case_id)
+@pytest.mark.parametrize("case", [c for c in ORCA_HUMAN_CASES if ORCA_PARAM_SETS[c[2]][:2] != (10, 10.0)], ids=orca_case_id)
 def test_parameter_sets_truncate_and_leave_agents_alone(coverage, case):
     N, rv, ps = case
     c = coverage[0][case]
     if ps == "mn0":  # maxNeighbors 0: nobody has a neighbour, every in-range other is dropped
         assert c["nb_none"] == c["agents"] and c["nb_truncated"] >= 1 and c["lp1_dir0"] == 0, c
         return
-    max_neighbors = 3 if ps == "mn3-nd2" else 1
+    max_neighbors, neighbor_dist = ORCA_PARAM_SETS[ps][:2]
     if _others(N, rv) > max_neighbors:
         assert c["nb_truncated"] >= 1, c
-    if ps == "mn3-nd2":  # neighborDist 2.0
+    if neighbor_dist == 2.0:
         if _others(N, rv) >= 1:
             assert c["nb_out_of_range"] >= 1, c
         assert c["nb_none"] >= 1, c
@@ -133,10 +139,49 @@ def test_inner_lp2_failure_inside_lp3_occurs_somewhere(coverage):
     assert sum(c["lp3_inner_fail"] for c in coverage[0].values()) >= 1
 
 
-@pytest.mark.parametrize("case", ORCA_ROBOT_CASES, ids=orca_case_id)
+def _changed_share(a, b, exists):
+    """The share of existing humans whose velocity (either component) differs bitwise between two runs."""
+    differ = (a.view(np.uint64) != b.view(np.uint64)).any(-1)
+    return int((differ & exists).sum()), int(exists.sum())
+
+
+@pytest.mark.parametrize("case", [c for c in ORCA_HUMAN_CASES if c[2] in ORCA_MOVED_SETS], ids=orca_case_id)
+def test_moved_fields_are_seen_and_keep_the_branches(coverage, case):
+    """time_step, the horizon and the humans' safety space off their defaults.  (a) At step 0 at least a tenth of the
+    existing humans get another ORCA velocity than under "default", bit for bit: a kernel that ignored the field would
+    differ from the oracle on as many.  (b) The case still reaches the colliding branch (invTimeStep) and (c) the cut-off
+    circle and both legs (invTimeHorizon)."""
+    N, rv, ps = case
+    b = orca_human_batch(N, rv)
+    exists = np.arange(N)[None, :] < b.n_humans[:, None]
+    changed, total = _changed_share(orca_reference(case)["out"][0]["human_action"],
+                                    orca_reference((N, rv, "default"))["out"][0]["human_action"], exists)
+    assert 10 * changed >= total > 0, (changed, total)
+    c = coverage[0][case]
+    for k in ("line_colliding", "line_circle", "line_left_leg", "line_right_leg"):
+        assert c[k] >= 1, (k, c)
+
+
+@pytest.mark.parametrize("case", ORCA_ROBOT_MOVED_CASES, ids=orca_robot_case_id)
+@pytest.mark.parametrize("safety", SAFETIES)
+def test_robot_solve_takes_its_own_safety_space(case, safety):
+    """The handle's safety space is the humans': under "saf0.1" the robot's solve is the default handle's, bit for bit,
+    at either robot safety space; 0.15 in place of 0 moves it, and so does "all" (time step and horizon)."""
+    plain = orca_robot_reference(case[:2], safety)
+    moved = orca_robot_reference(case, safety)
+    if case[2] == "saf0.1":
+        assert moved.tobytes() == plain.tobytes()
+    else:
+        changed, total = _changed_share(moved, plain, np.ones(len(plain), bool))
+        assert 10 * changed >= total, (changed, total)
+    changed, total = _changed_share(moved, orca_robot_reference(case, SAFETIES[1] - safety), np.ones(len(plain), bool))
+    assert 10 * changed >= total, (changed, total)
+
+
+@pytest.mark.parametrize("case", ORCA_ROBOT_CASES + ORCA_ROBOT_MOVED_CASES, ids=orca_robot_case_id)
 def test_robot_cases_collide_and_enter_lp3(coverage, case):
     c = coverage[1][case]
-    assert c["agents"] == 2 * orca_robot_batch(*case).n  # the robot of every env, once per safety space
+    assert c["agents"] == 2 * orca_robot_batch(*case[:2]).n  # the robot of every env, once per safety space
     assert c["line_colliding"] >= 1 and c["lp3_entered"] >= 1, c
 
 
@@ -171,7 +216,7 @@ def test_write_the_coverage_table(coverage, traced):
     human, robot = coverage
     if not hasattr(test_lp3_parallel_same_direction_by_hand, "count"):
         test_lp3_parallel_same_direction_by_hand(traced)
-    cases = [(orca_case_id(k), v) for k, v in human.items()] + [("robot " + orca_case_id(k), v) for k, v in robot.items()]
+    cases = [(orca_case_id(k), v) for k, v in human.items()] + [("robot " + orca_robot_case_id(k), v) for k, v in robot.items()]
     short = [c.replace("line_", "ln_").replace("_fail_", "_f_").replace("discriminant", "disc").replace("parallel", "par")
              .replace("interval", "intv").replace("_or_more", "+").replace("opposite", "opp").replace("out_of_range", "far")
              .replace("truncated", "trunc").replace("colliding", "coll").replace("entered", "in") for c in COLUMNS]

@@ -9,6 +9,10 @@ linearProgram3, every way linearProgram1 fails, colliding and parallel lines, ma
 and NaN lines.  A difference here is a finding about orca_group, not about the oracle: where a line is NaN (two agents
 with one position and one velocity) the oracle's fminf / fmaxf is RVO2's std::min / std::max.
 
+Parameter sets (helpers.ORCA_PARAM_SETS): maxNeighbors / neighborDist, and time_step, orca_time_horizon and
+orca_safety_space off their defaults one at a time and together; the robot kernel also under a handle whose safety space
+is not the robot's own.
+
 Tie order: both sides rank equal distances in insertion order.  RVO2 proper walks a kd-tree once it holds more than 10
 agents (N >= 11 here), and visits ties in the tree's order; that order is knowingly not modelled, so the lattice cases
 hold the two sides to each other, not to RVO2."""
@@ -16,9 +20,9 @@ import numpy as np
 import pytest
 
 from ebcsim import _abi, actions as ebc_actions
-from helpers import (ORCA_GROUP_SIZES, ORCA_HUMAN_CASES, ORCA_ROBOT_CASES, ORCA_STEPS, Guarded, orca_case_id,
-                     orca_case_params, orca_group_size, orca_human_batch, orca_reference, orca_robot_actions,
-                     orca_robot_batch, orca_robot_reference)
+from helpers import (ORCA_GROUP_SIZES, ORCA_HUMAN_CASES, ORCA_ROBOT_CASES, ORCA_ROBOT_MOVED_CASES, ORCA_STEPS, Guarded,
+                     orca_case_id, orca_case_params, orca_group_size, orca_human_batch, orca_reference,
+                     orca_robot_actions, orca_robot_batch, orca_robot_case_id, orca_robot_reference)
 from test_gpu_parity import _compare_step, _env
 
 pytestmark = pytest.mark.gpu
@@ -92,14 +96,17 @@ def test_one_launch(case):
 
 
 @pytest.mark.parametrize("safety", [0.0, 0.15])
-@pytest.mark.parametrize("case", ORCA_ROBOT_CASES, ids=orca_case_id)
+@pytest.mark.parametrize("case", ORCA_ROBOT_CASES + ORCA_ROBOT_MOVED_CASES, ids=orca_robot_case_id)
 def test_robot_kernel(case, safety):
-    """robot_orca(safety) with the robot inside the crowd; rows N + S = 1 .. 13, 16, 17, 21, 22, 32."""
-    N, S = case
+    """robot_orca(safety) with the robot inside the crowd; rows N + S = 1 .. 13, 16, 17, 21, 22, 32.  The cases with a
+    parameter set run under a handle whose own safety space (the humans': 0.1) is not the robot's, with the time step and
+    the horizon moved too under "all": the robot's solve takes `safety` and the handle's step and horizon."""
+    N, S = case[:2]
     b = orca_robot_batch(N, S)
-    g = _env(orca_case_params(), b.n, N, S)
+    g = _env(orca_case_params(0, *case[2:]), b.n, N, S)
     g.reset(b)
-    _bitwise(g.robot_orca(safety), orca_robot_reference(case, safety), "robot %s safety %g" % (orca_case_id(case), safety))
+    _bitwise(g.robot_orca(safety), orca_robot_reference(case, safety),
+             "robot %s safety %g" % (orca_robot_case_id(case), safety))
 
 
 @pytest.mark.parametrize("N", [4, 10])
