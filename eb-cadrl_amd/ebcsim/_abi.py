@@ -239,3 +239,22 @@ class EbcSailDaggerArgs(C.Structure):
                 ("expert_safety_space", C.c_double)] + [
         (k, C.c_void_p) for k in ("take_expert", "robot", "ob", "n_rows", "learner_action", "expert_action",
                                   "robot_action_out", "reward", "done", "info")]
+
+
+CADRL_NET_LAYERS = 4
+
+
+class EbcCadrlNetWeights(C.Structure):
+    """include/ebcsim.h: the four Linear layers of a CADRL value network, host pointers in torch's layout [out][in]; widths =
+    the row width, then the layers' units."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_layers", C.c_int32), ("widths", C.c_int32 * (CADRL_NET_LAYERS + 1)),
+                ("reserved", C.c_int32), ("weight", C.c_void_p * CADRL_NET_LAYERS), ("bias", C.c_void_p * CADRL_NET_LAYERS)]
+
+
+class EbcCadrlGradArgs(C.Structure):
+    """include/ebcsim.h: one ebc_cadrl_grad (rows [B][R][T] float32, n_valid [B] int64 or NULL, target [B] float32, sample_mask
+    [B] uint8 or NULL -> grad float32 [packed floats], loss_sum float64 [1], count int64 [1], value [B] float32 or NULL,
+    min_row [B] int32 or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
+                ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "min_row")]

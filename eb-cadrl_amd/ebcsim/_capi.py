@@ -84,6 +84,12 @@ SYMBOLS = {
     "ebc_sail_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_dagger_k": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ebc_cadrl_net_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ebc_cadrl_net_destroy": (C.c_int, [C.c_void_p]),
+    "ebc_cadrl_net_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ebc_cadrl_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_cadrl_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_cadrl_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -101,6 +101,7 @@ class CadrlValueNet(object):
             p.requires_grad_(False)
         self.input_dim = self.module.input_dim
         self.native_forwards = 0
+        self.native_refreshes = 0
         self.values_decidable = False
         self.last_choice = None
         self._native = None
@@ -122,6 +123,27 @@ class CadrlValueNet(object):
                                           "output (two two-layer blocks)")
             self._native = tuple(Mlp2Block(layers[i:i + 2], idx) for i in (0, 2))
         return self._native
+
+    def refresh_native(self, state_dict_or_trainer):
+        """New weights for a network that decides: a state_dict of the reference's keys, or a cadrl_train.CadrlTrainer
+        (its master copy, read in place on the device).  The module's parameters take them, and on a HIP device the two
+        two-layer blocks are re-packed from them on the device (ebc_mlp2_update, no host copy): the next decide gives the
+        bytes of a CadrlValueNet freshly built from the same state_dict.  Returns False when the network has no blocks."""
+        sd = state_dict_or_trainer
+        if hasattr(sd, "device_state_dict"):
+            sd = sd.device_state_dict()
+        layers = _stack(self.module.value_network)
+        with torch.no_grad():
+            for i, (w, b) in zip(sorted({int(k.split(".")[1]) for k in sd if k.startswith("value_network.")}), layers):
+                w.copy_(sd["value_network.%d.weight" % i])
+                b.copy_(sd["value_network.%d.bias" % i])
+        if self.device.type != "cuda":
+            return False
+        nat = self._native_blocks()
+        nat[0].update(layers[0:2])
+        nat[1].update(layers[2:4])
+        self.native_refreshes += 1
+        return True
 
     def _check_width(self, T):
         if T != self.input_dim:

@@ -798,6 +798,77 @@ typedef struct EbcSailDaggerArgs {
 } EbcSailDaggerArgs;
 int ebc_sail_dagger_k(void *handle, const EbcSailDaggerArgs *args);
 
+/* ---- training the CADRL value network (rl/policy/cadrl.py:13-31: four Linear layers ending in one output, ReLU after
+ * the first three; rl/utils/trainer.py:74-100: MSE regression on value targets): the gradient of the loss with respect
+ * to every weight, in one launch that runs the forward of every row, takes each state's minimum over its rows and runs
+ * the backward through the minimal row, and a second small launch that adds the partial sums.  The arithmetic is
+ * csrc/ebc_cadrl_grad_rule.h (one definition for the kernel and for the host build tests/native/cadrl_grad_host.cc
+ * compares it with byte for byte): float32, every unit a serial fmaf chain over its inputs ascending from 0, then + bias.
+ * Those are the forward's bytes for THIS entry; ebc_mlp2_forward_f32 (what ebc_cadrl_decide's values come from) agrees
+ * with them to float32 rounding, not bit for bit.
+ *
+ * EbcCadrlNetWeights: n_layers = 4; widths = the row width, then the four layers' units; weight / bias: HOST pointers,
+ * torch's layout [out][in] / [out].  Limits: 1 <= widths[0] <= 64, 1 <= widths[1 .. 3] <= 256, widths[4] = 1, else
+ * EBC_ERR_UNSUPPORTED and ebc_last_error names the limit.
+ * The packed image (weights, and the gradient alike): the four layers in order, layer l as W[k][Op] — unit u of input k
+ * at k * Op + u, Op = the layer's units padded to a multiple of 4 — followed by bias[Op]; pad entries are exactly 0.
+ * 27 732 floats (108 KB) at the reference's 13 -> 150 -> 100 -> 100 -> 1. */
+#define EBC_CADRL_NET_LAYERS 4
+typedef struct EbcCadrlNetWeights {
+  uint32_t struct_size;
+  int32_t n_layers;                            /* 4 */
+  int32_t widths[EBC_CADRL_NET_LAYERS + 1];    /* row width, then the layers' units */
+  int32_t reserved;
+  const float *weight[EBC_CADRL_NET_LAYERS];   /* host float32 [out][in] */
+  const float *bias[EBC_CADRL_NET_LAYERS];     /* host float32 [out] */
+} EbcCadrlNetWeights;
+/* One ebc_cadrl_grad over B states of R row slots each:
+ *   n        = n_valid[b] clamped to [0, R] (NULL: R); rows at or past n are never read
+ *   value[b] = the minimum over rows [0, n) of the network's output, as ebc_cadrl_decide takes it (a NaN among them makes
+ *              it NaN, no row gives NaN); min_row[b] = the first row that holds it, -1 without rows
+ *   live     = (sample_mask == NULL or sample_mask[b] != 0) and n >= 1; a state that is not live enters no sum (a
+ *              selection, never a product with 0: its NaNs reach nothing but its own value); a NaN inside a live state
+ *              reaches loss_sum and grad
+ *   loss_sum = the sum over live states of (value - target)^2, the difference in float32, squared and summed in float64
+ *   grad     = d/dweights of grad_scale / 2 * loss_sum, through each state's min_row alone (the seed is grad_scale *
+ *              (value - target)): grad_scale = 2 / count is torch's MSELoss over count values
+ *   count    = the number of live states
+ * The batch is cut into chunks of 16 consecutive states; a weight's float32 sum runs over a chunk's live states ascending,
+ * the chunks are added ascending in float64 and rounded once: the result depends on the inputs alone, never on the grid or
+ * on timing.  Every NaN written is the quiet NaN 0x7fc00000 (float64: 0x7ff8000000000000).  grad has the packed layout.
+ * Scratch for the partial sums belongs to the network and grows on demand (growing waits for the WHOLE device and frees
+ * the old scratch).  So at most ONE ebc_cadrl_grad may be in flight per network: calls on one network go to one stream, or
+ * are ordered by the caller, and never come from two threads at once; nothing locks the scratch.  A call that has to grow
+ * the scratch must not be made while another stream of the process is being captured (the wait would break that capture):
+ * make the first call at the largest B before capturing elsewhere.  Two networks are independent.  Device
+ * pointers.  1 <= R <= 128, else EBC_ERR_UNSUPPORTED; T other than the network's row width is EBC_ERR_INVALID; a stream
+ * under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcCadrlGradArgs {
+  uint32_t struct_size;
+  int32_t B, R, T;
+  float grad_scale;
+  int32_t reserved;
+  const float *rows;            /* device float32 [B][R][T] */
+  const int64_t *n_valid;       /* device int64 [B]; NULL = all R rows */
+  const float *target;          /* device float32 [B] */
+  const uint8_t *sample_mask;   /* device uint8 [B]; NULL = every state counts */
+  float *grad;                  /* device float32 [ebc_cadrl_net_packed_floats] */
+  double *loss_sum;             /* device float64 [1] */
+  int64_t *count;               /* device int64 [1] */
+  float *value;                 /* device float32 [B], or NULL */
+  int32_t *min_row;             /* device int32 [B], or NULL */
+} EbcCadrlGradArgs;
+int ebc_cadrl_net_create(const EbcCadrlNetWeights *weights, int device_id, void **net_out);
+int ebc_cadrl_net_destroy(void *net);
+/* floats of the network's packed image */
+int ebc_cadrl_net_packed_floats(void *net, int64_t *floats_out);
+/* the packed image into dst_dev (device float32 [ebc_cadrl_net_packed_floats]): a copy enqueued on `stream` */
+int ebc_cadrl_net_get_packed(void *net, void *stream, float *dst_dev);
+/* src_dev (device float32, the packed layout, pad entries 0) becomes the network's weights: a stream-ordered copy,
+ * enqueued on `stream`; an ebc_cadrl_grad enqueued after it on that stream computes with the new weights. */
+int ebc_cadrl_net_set_packed(void *net, void *stream, const float *src_dev);
+int ebc_cadrl_grad(void *net, void *stream, const EbcCadrlGradArgs *args);
+
 #ifdef __cplusplus
 }
 #endif
