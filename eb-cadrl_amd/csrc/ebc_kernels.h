@@ -30,6 +30,7 @@
 #endif
 #include "ebc_orca_group.h"
 #include "ebc_scene_gen.h"
+#include "ebc_step_grid.h"
 #include "ebc_step_rules.h"
 
 namespace ebc {
@@ -461,13 +462,14 @@ struct HumanRegs {
   int type;
 };
 
-__device__ __forceinline__ LaneMap lane_map(const DevState &s, int e0, int epb, int lane) {
+// envs [e0, e_end) of at most epb
+__device__ __forceinline__ LaneMap lane_map(const DevState &s, int e0, int e_end, int epb, int lane) {
   LaneMap m;
   const int N = s.N;
   m.el = lane / N;
   m.i = lane - m.el * N;
   const int e = e0 + m.el;
-  m.env_ok = m.el < epb && e < s.E;
+  m.env_ok = m.el < epb && e < e_end;
   m.ee = m.env_ok ? (size_t)e : 0;
   m.k = m.ee * N + m.i;
   m.n = m.env_ok ? s.n_humans[m.ee] : 0;
@@ -970,7 +972,7 @@ __global__ __launch_bounds__(EBC_WAVE) void step_kernel(EbcParams p_in, DevState
   const DevState &s = args.s;
   const StepIO &io = args.io;
   const int epb = EBC_WAVE / s.N;
-  const LaneMap m = lane_map(s, blockIdx.x * epb, epb, lane);
+  const LaneMap m = lane_map(s, blockIdx.x * epb, s.E, epb, lane);
   double rb[9];
   load_robot(s, m, rb);
   double gtime = m.env_ok ? s.time[m.ee] : 0.0;
@@ -1016,16 +1018,27 @@ __global__ __launch_bounds__(EBC_WAVE) void step_kernel(EbcParams p_in, DevState
 // Everything in a step is local to an env, so the roles meet through per-env / per-human mailbox
 // words in HBM instead of a second launch: an env's rows and state are written as soon as ITS
 // humans and ITS robot-side work are done, while the slowest ORCA waves of the launch (the
-// humans deep in linearProgram3) are still running.  Consumers (ROWS, STATE) only wait for
-// workgroups of LOWER index; the dispatcher starts workgroups in index order and producers wait
+// humans deep in linearProgram3) are still running.
+//
+// WHICH envs / humans a block owns is ebc_step_grid.h's: the envs are cut into eight classes of `ec`
+// consecutive envs, block r of a role works for class r % 8 (rank r / 8 within it), and every role
+// takes a multiple of 8 block indices, in the order ENV, ORCA, ROWS, STATE — every wave that touches
+// an env has the same index mod 8 and, as the dispatcher deals workgroups round-robin over the XCDs,
+// the same L2.  That is placement only: the mailbox words, their scopes and epochs are what they
+// would be under any block-to-XCD map, and a block whose span is empty touches none of them.
+//
+// Liveness: consumers (ROWS, STATE) wait only for ENV / ORCA blocks, ALL of which have lower indices
+// than any ROWS / STATE block; the dispatcher starts workgroups in index order and producers wait
 // for nothing, so every wait ends.  A poll that exceeds EBC_SPIN_LIMIT gives up and raises
 // DevState::fault rather than hang the device.
 struct StepGrid {
-  unsigned env_blocks, orca_blocks, rows_blocks;  // then the STATE blocks (64 / N envs each)
+  unsigned env_blocks, orca_blocks, rows_blocks;  // 8 Q each (ebc_step_grid.h); then the STATE blocks (64 / N envs each)
   unsigned rows_epw;                               // envs per ROWS wave (1 when N + S > 64)
   unsigned epoch;                                  // launch counter, never 0
   unsigned total;                                  // one-wave "blocks" in all (EBC_STEP_WPB of them per workgroup)
+  unsigned ec;                                     // envs per class
 };
+static_assert(EBC_GRID_WAVE == EBC_WAVE, "ebc_step_grid.h: lanes of a wave");
 
 #define EBC_RBN_ENVS 16  // envs per STATE wave whose restart robot is parked in LDS (more: late loads)
 struct RoleLds {  // after the arguments, what the role of the wave needs
@@ -1043,8 +1056,9 @@ struct RoleLds {  // after the arguments, what the role of the wave needs
 // (A lane per human slot and a lane per env were both measured slower: DESIGN.md, profiles/r03_step_forms_ab.txt,
 // profiles/r03_env_lane_timeline.txt.)
 #define EBC_ENV_LANES 4
+static_assert(EBC_GRID_ENV_EPW == EBC_WAVE / EBC_ENV_LANES, "ebc_step_grid.h: envs per ENV wave");
 __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in, RoleLds &L,
-                                              unsigned block, unsigned epoch, int lane) {
+                                              unsigned block, unsigned ec, unsigned epoch, int lane) {
   stage_args(&L.args.p, p_in, lane);
   stage_args(&L.args.s, s_in, lane);
   stage_args(&L.args.io, io_in, lane);
@@ -1054,9 +1068,10 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
   const StepIO &io = L.args.io;
   constexpr int Q = EBC_ENV_LANES, EPW = EBC_WAVE / Q;
   const int el = lane / Q, part = lane - el * Q;
-  const int e0 = (int)block * EPW;
+  const StepSpan span = step_span(block, ec, (unsigned)s.E, EPW);
+  const int e0 = (int)span.first, e_end = (int)span.end;
   const int e = e0 + el;
-  const bool ok = e < s.E;
+  const bool ok = e < e_end;
   const size_t ee = ok ? (size_t)e : 0;
   const int N = s.N;
   double rb[9];
@@ -1097,7 +1112,7 @@ __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevSt
       L.env.ract[el][1] = rn[1];
     }
     wave_sync();
-    const int here = min(EPW, s.E - e0);
+    const int here = e_end - e0;  // <= 0: nothing
     for (int q = lane; q < 9 * here; q += EBC_WAVE)
       __hip_atomic_store(s.robot_n + (size_t)e0 * 9 + q, stage[q], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
@@ -1212,15 +1227,16 @@ __device__ __forceinline__ void sreg(const Tp &x) {
 // ---- ORCA
 template <int GS>
 __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s, const OrcaHot &hot, uint4 *vel, unsigned epoch,
-                                          unsigned char *scratch, unsigned block, int lane) {
-  // `hot`, vel, epoch: preloaded kernel arguments; the rest is asked for now, all at once
+                                          unsigned char *scratch, unsigned block, unsigned class_humans, int lane) {
+  // `hot`, vel, epoch, class_humans (ec N): preloaded kernel arguments; the rest is asked for now, all at once
   sreg(s.robot); sreg(s.range_sq); sreg(s.inv_time_horizon); sreg(s.inv_time_step);
   sreg(p.robot_visible); sreg(p.orca_max_neighbors); sreg(p.orca_safety_space);
   constexpr int HPW = EBC_WAVE / GS;
   const int group = lane / GS, j = lane - group * GS;
   // 32-bit index math (E * N < 2^31 is checked at create)
-  const unsigned hh = block * HPW + group;
-  const bool h_ok = group < HPW && hh < (unsigned)hot.E * (unsigned)hot.N;  // lanes past HPW * GS idle
+  const StepSpan span = step_span(block, class_humans, (unsigned)hot.E * (unsigned)hot.N, HPW);
+  const unsigned hh = span.first + group;
+  const bool h_ok = hh < span.end;  // lanes past HPW * GS idle (a span holds at most HPW humans)
   int e, i;
   split_human(hot, hh, h_ok, e, i);
   float ox, oy;
@@ -1241,7 +1257,7 @@ __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s,
 // ns + i, static slot j >= ns -> N + j.
 template <int T>
 __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
-                                          RoleLds &L, unsigned block, unsigned epw, unsigned epoch, int lane) {
+                                          RoleLds &L, unsigned block, unsigned ec, unsigned epw, unsigned epoch, int lane) {
   stage_args(&L.args.p, p_in, lane);
   stage_args(&L.args.s, s_in, lane);
   stage_args(&L.args.io, io_in, lane);
@@ -1252,8 +1268,9 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
   const int N = s.N, S = s.S, R = N + S;
   const int el = R <= EBC_WAVE ? lane / R : 0;
   const int first = lane - el * R;
-  const int e = (int)(block * epw) + el;
-  const bool env_ok = el < (int)epw && e < s.E;
+  const StepSpan span = step_span(block, ec, (unsigned)s.E, epw);
+  const int e = (int)span.first + el;
+  const bool env_ok = e < (int)span.end;  // at most epw envs
   const size_t ee = env_ok ? (size_t)e : 0;
   const int stride = R <= EBC_WAVE ? R : EBC_WAVE;  // one pass unless an env has more rows than lanes
   RotFrame f = {};
@@ -1329,7 +1346,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
 
 // ---- STATE
 __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
-                                           RoleLds &L, int block, bool wait_rows, unsigned epoch, int lane) {
+                                           RoleLds &L, unsigned block, unsigned ec, bool wait_rows, unsigned epoch, int lane) {
   stage_args(&L.args.p, p_in, lane);
   stage_args(&L.args.s, s_in, lane);
   stage_args(&L.args.io, io_in, lane);
@@ -1338,7 +1355,8 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
   const DevState &s = L.args.s;
   const StepIO &io = L.args.io;
   const int epb = EBC_WAVE / s.N;
-  const LaneMap m = lane_map(s, block * epb, epb, lane);
+  const StepSpan span = step_span(block, ec, (unsigned)s.E, (unsigned)epb);
+  const LaneMap m = lane_map(s, (int)span.first, (int)span.end, epb, lane);
   double gtime = m.env_ok ? s.time[m.ee] : 0.0;
   HumanRegs h = load_human(s, m);
   StepIO io_state = io;  // no observation rows here: CommitPre's static-row preloads stay empty
@@ -1501,16 +1519,19 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
 #endif
 // Waves per workgroup of the step launch.  Every wave is a "block" of its own (roles by index, no
 // workgroup barrier, a private LDS slice); packing several into one workgroup only changes how fast
-// the dispatcher starts them.
+// the dispatcher starts them — and what is placed: XCDs are dealt WORKGROUPS, so with more waves per
+// workgroup a wave runs where its workgroup's index mod 8 says, not its own, and the classes of
+// ebc_step_grid.h no longer land on one XCD each (results do not depend on that).
 #ifndef EBC_STEP_WPB
 #define EBC_STEP_WPB 1
 #endif
 template <int GS, int T>
 __global__ __launch_bounds__(EBC_WAVE * EBC_STEP_WPB, EBC_STEP_WAVES(GS)) void orca_step_kernel(
     // 14 dwords the wave finds in scalar registers when it starts (kernarg preload): its role and, for
-    // an ORCA wave, everything up to its first vector load (13 in use; the last pads p_in to 8 bytes)
+    // an ORCA wave, everything up to its first vector load (the last, the humans of a class = ec N, also pads
+    // p_in to 8 bytes)
     unsigned env_blocks, unsigned orca_blocks, int hot_E, int hot_N, unsigned hot_magic, unsigned hot_shift,
-    const float4 *hot_tile, const int *hot_n_humans, uint4 *hot_vel, unsigned hot_epoch, unsigned pad,
+    const float4 *hot_tile, const int *hot_n_humans, uint4 *hot_vel, unsigned hot_epoch, unsigned hot_class_humans,
     EbcParams p_in, DevState s_in, StepIO io_in, StepGrid g) {
   const WaveTrace wt(2);
   constexpr size_t LDS = ((sizeof(RoleLds) > (size_t)OrcaLds<GS>::BYTES ? sizeof(RoleLds) : (size_t)OrcaLds<GS>::BYTES) + 15) / 16 * 16;
@@ -1522,7 +1543,7 @@ __global__ __launch_bounds__(EBC_WAVE * EBC_STEP_WPB, EBC_STEP_WAVES(GS)) void o
   if (EBC_STEP_WPB > 1 && b >= g.total) return;
   if (b < env_blocks) {
     __builtin_amdgcn_s_setprio(EBC_ENV_PRIO);  // the long dependent chain of the launch
-    env_lane_role(p_in, s_in, io_in, L, b, g.epoch, lane);
+    env_lane_role(p_in, s_in, io_in, L, b, g.ec, g.epoch, lane);
     return;
   }
   b -= env_blocks;
@@ -1531,16 +1552,16 @@ __global__ __launch_bounds__(EBC_WAVE * EBC_STEP_WPB, EBC_STEP_WAVES(GS)) void o
     // -0.08 us per step (profiles/r02_early_rows_ab.txt)
     __builtin_amdgcn_s_setprio(EBC_ORCA_PRIO);
     const OrcaHot hot{hot_E, hot_N, hot_magic, hot_shift, hot_tile, hot_n_humans};
-    orca_role<GS>(p_in, s_in, hot, hot_vel, hot_epoch, lds, b, lane);
+    orca_role<GS>(p_in, s_in, hot, hot_vel, hot_epoch, lds, b, hot_class_humans, lane);
     return;
   }
   b -= orca_blocks;
   if (b < g.rows_blocks) {
-    rows_role<T>(p_in, s_in, io_in, L, b, g.rows_epw, g.epoch, lane);
+    rows_role<T>(p_in, s_in, io_in, L, b, g.ec, g.rows_epw, g.epoch, lane);
     return;
   }
   b -= g.rows_blocks;
-  state_role(p_in, s_in, io_in, L, (int)b, g.rows_blocks != 0, g.epoch, lane);
+  state_role(p_in, s_in, io_in, L, b, g.ec, g.rows_blocks != 0, g.epoch, lane);
 }
 
 // SceneGenerator.generate_random_scene for n seeds, one lane per scene (ebc_scene_gen.h): `d` holds the base of

@@ -10,7 +10,7 @@
 
 namespace ebc {
 
-#define EBC_TRACE_ROW 16  // u64 per wave: r0 r1 c0 c1 hw_id | marks 5..10 | counts 11..15
+#define EBC_TRACE_ROW 16  // u64 per wave: r0 r1 c0 c1 hw_id (xcc_id << 32) | marks 5..10 | counts 11..15
 
 #ifdef EBC_WAVE_TRACE
 __device__ unsigned long long *g_wave_trace;
@@ -58,7 +58,9 @@ struct WaveTrace {
       o[1] = r1;
       o[3] = c1;
 #if EBC_WAVE_TRACE > 1
-      o[4] = __builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11));  // HW_ID
+      // HW_ID, and above it the XCD the wave ran on (HW_REG_XCC_ID = 20, XCC_ID in bits 3:0)
+      o[4] = (unsigned long long)__builtin_amdgcn_s_getreg((4 << 0) | (0 << 6) | (31 << 11)) |
+             (unsigned long long)__builtin_amdgcn_s_getreg((20 << 0) | (0 << 6) | (3 << 11)) << 32;
       const unsigned *box = wave_trace_lds();
       const unsigned c0 = (unsigned)o[2];
       for (int k = 0; k < 6; ++k) o[5 + k] = box[k] ? o[2] + (unsigned)(box[k] - c0) : 0;  // marks, shader cycles

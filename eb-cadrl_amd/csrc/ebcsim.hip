@@ -224,27 +224,26 @@ int launch_orca_step_gs(Handle *h, const StepIO &io, unsigned blocks, const ebc:
   if (h->T == 17)
     hipLaunchKernelGGL((ebc::orca_step_kernel<GS, 17>), dim3((blocks + EBC_STEP_WPB - 1) / EBC_STEP_WPB), dim3(EBC_WAVE * EBC_STEP_WPB), 0, h->stream,
                        g.env_blocks, g.orca_blocks, h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile,
-                       (const int *)h->s.n_humans, h->s.vel, g.epoch, 0u, h->p, h->s, io, g);
+                       (const int *)h->s.n_humans, h->s.vel, g.epoch, g.ec * (unsigned)h->s.N, h->p, h->s, io, g);
   else
     hipLaunchKernelGGL((ebc::orca_step_kernel<GS, 13>), dim3((blocks + EBC_STEP_WPB - 1) / EBC_STEP_WPB), dim3(EBC_WAVE * EBC_STEP_WPB), 0, h->stream,
                        g.env_blocks, g.orca_blocks, h->s.E, h->s.N, h->s.n_magic, h->s.n_shift, (const float4 *)h->s.tile,
-                       (const int *)h->s.n_humans, h->s.vel, g.epoch, 0u, h->p, h->s, io, g);
+                       (const int *)h->s.n_humans, h->s.vel, g.epoch, g.ec * (unsigned)h->s.N, h->p, h->s, io, g);
   HIP_TRY(hipGetLastError());
   return EBC_OK;
 }
 
 int launch_orca_step(Handle *h, const StepIO &io) {
-  const int epb = EBC_WAVE / h->s.N;
-  const int R = h->s.N + h->s.S;
+  // who does what: ebc_step_grid.h (eight classes of envs, every role a multiple of 8 blocks)
+  const ebc::StepGridShape shape = ebc::step_grid_shape(h->s.E, h->s.N, h->s.S, h->orca_gs, io.ob || io.obs_rotated);
+  if (!shape.fits()) return fail(EBC_ERR_UNSUPPORTED, "ORCA step grid >= 2^31 workgroups");
+  const unsigned long long blocks = shape.total();
   ebc::StepGrid g;
-  const unsigned state_blocks = (unsigned)((h->s.E + epb - 1) / epb);
-  constexpr int envs_per_env_wave = EBC_WAVE / EBC_ENV_LANES;
-  g.env_blocks = (unsigned)((h->s.E + envs_per_env_wave - 1) / envs_per_env_wave);
-  g.orca_blocks = (unsigned)orca_blocks(h);
-  g.rows_epw = R <= EBC_WAVE ? (unsigned)(EBC_WAVE / R) : 1u;
-  g.rows_blocks = (io.ob || io.obs_rotated) ? (unsigned)((h->s.E + g.rows_epw - 1) / g.rows_epw) : 0u;
-  const unsigned long long blocks = (unsigned long long)g.env_blocks + state_blocks + g.orca_blocks + g.rows_blocks;
-  if (blocks >= 2147483648ull) return fail(EBC_ERR_UNSUPPORTED, "ORCA step grid >= 2^31 workgroups");
+  g.env_blocks = (unsigned)shape.env_blocks;
+  g.orca_blocks = (unsigned)shape.orca_blocks;
+  g.rows_blocks = (unsigned)shape.rows_blocks;
+  g.rows_epw = shape.rows_epw;
+  g.ec = shape.ec;
   if (++h->epoch == 0) h->epoch = 1;  // every mailbox word is tagged with the epoch of the launch that wrote it; 0 = never
   g.epoch = h->epoch;
   g.total = (unsigned)blocks;

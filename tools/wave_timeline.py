@@ -60,18 +60,20 @@ def main():
         rows = rows[idx]
         if not len(rows):
             continue
-        if tag == 2:  # orca_step_kernel: blocks in role order ENV, ORCA, ROWS, STATE
-            env_blocks = -(-E // 16)  # the ENV role has four lanes per env
-            state_blocks = -(-E // (64 // batch.N))
+        if tag == 2:  # orca_step_kernel: blocks in role order ENV, ORCA, ROWS, STATE, each dealt to the eight classes
+            # of envs by block index mod 8 (csrc/ebc_step_grid.h, restated)
             others = batch.N - 1 + (1 if params.robot_visible else 0)
             gs = next(g for g in (2, 3, 4, 5, 6, 7, 8, 9, 10, 12, 16, 21, 32) if g >= others)
-            orca_blocks = -(-E * batch.N // (64 // gs))
             R = batch.N + batch.S
-            epw = 64 // R if R <= 64 else 1
-            rows_blocks = -(-E // epw)
-            b1, b2, b3 = env_blocks, env_blocks + orca_blocks, env_blocks + orca_blocks + rows_blocks
-            parts = [("ENV", idx < b1), ("ORCA", (idx >= b1) & (idx < b2)),
-                     ("ROWS", (idx >= b2) & (idx < b3)), ("STATE", idx >= b3)]
+            grid = StepGrid(E, batch.N, 64 // gs, 64 // R if R <= 64 else 1)
+            b1, b2, b3 = grid.base["ORCA"], grid.base["ROWS"], grid.base["STATE"]
+            state_blocks = grid.blocks["STATE"]
+            busy = np.zeros(grid.total, bool)  # blocks that own something: the others start and end at once
+            for role in grid.base:
+                busy[grid.base[role]:grid.base[role] + grid.blocks[role]] = grid.owns(np, role)
+            own = busy[np.minimum(idx, grid.total - 1)]
+            parts = [("ENV", (idx < b1) & own), ("ORCA", (idx >= b1) & (idx < b2) & own),
+                     ("ROWS", (idx >= b2) & (idx < b3) & own), ("STATE", (idx >= b3) & own)]
         else:
             parts = [(TAGS[tag], np.ones(len(idx), bool))]
         base_all = rows[:, 0].astype(np.int64).min()
@@ -80,27 +82,74 @@ def main():
         for name, sel in parts:
             if sel.any():
                 report(np, name, rows[sel], launch0 if tag == 3 and launch0 is not None else base_all)
-        if tag == 2 and len(idx) == b3 + state_blocks:
+        if tag == 2 and len(idx) == grid.total:
             # what each STATE wave waited for: the ORCA waves and the ENV waves of its envs
             end = (rows[:, 1].astype(np.int64) - base_all) / 100.0
             start = (rows[:, 0].astype(np.int64) - base_all) / 100.0
-            hpw, epb = 64 // gs, 64 // batch.N
             lag, info = [], []
             for sb in range(state_blocks):
-                e0, e1 = sb * epb, min((sb + 1) * epb, E) - 1
-                h0, h1 = e0 * batch.N, (e1 + 1) * batch.N - 1
-                o0, o1 = b1 + h0 // hpw, b1 + h1 // hpw
-                ready_orca = end[o0:o1 + 1].max()
-                ready_env = end[e0 // 16:e1 // 16 + 1].max()
+                e0, e1 = grid.span("STATE", sb)
+                if e1 <= e0:
+                    continue
+                envs = np.arange(e0, e1)
+                ready_orca = end[np.unique(grid.block_of(np, "ORCA", np.arange(e0 * batch.N, e1 * batch.N)))].max()
+                ready_env = end[np.unique(grid.block_of(np, "ENV", envs))].max()
                 ready = max(ready_orca, ready_env)
                 lag.append(end[b3 + sb] - ready)
                 info.append((end[b3 + sb], ready_orca, ready_env, start[b3 + sb]))
+            if rows[:, 4].any() and (rows[:, 4] >> np.uint64(32)).any():
+                # where the waves of an env ran: its ENV, ROWS and STATE wave and the ORCA waves of its N humans
+                xcc = (rows[:, 4] >> np.uint64(32)).astype(np.int64) & 15
+                envs = np.arange(E)
+                who = [grid.block_of(np, r, envs) for r in ("ENV", "ROWS", "STATE")]
+                who += [grid.block_of(np, "ORCA", envs * batch.N + i) for i in range(batch.N)]
+                per_env = np.sort(xcc[np.stack(who, axis=1)], axis=1)
+                distinct = 1 + (np.diff(per_env, axis=1) != 0).sum(axis=1)
+                # the deal itself: how many blocks ran on the XCD most blocks of their index mod 8 ran on
+                cls = np.arange(grid.total) % 8
+                home = np.array([np.bincount(xcc[cls == c], minlength=16).argmax() for c in range(8)])
+                print("XCC: %.1f%% of envs had all their waves on one XCD; distinct XCDs per env p50 / max %d / %d; "
+                      "%.1f%% of blocks ran on the XCD of their index mod 8 (%s)" % (
+                          100.0 * (distinct == 1).mean(), np.percentile(distinct, 50), distinct.max(),
+                          100.0 * (xcc == home[cls]).mean(), " ".join(str(h) for h in home)))
             lag = np.array(lag)
             print("STATE end minus (its last ORCA wave's end, its last ENV wave's end): p10/p50/p90/max %.2f %.2f %.2f %.2f us" % (
                 np.percentile(lag, 10), np.percentile(lag, 50), np.percentile(lag, 90), lag.max()))
             last = np.argsort([q[0] for q in info])[-6:]
             print("   the 6 STATE waves that ended last (end, last ORCA end, ENV end, own start): " +
                   " ".join("(%.1f %.1f %.1f %.1f)" % info[q] for q in last))
+
+
+class StepGrid:
+    """csrc/ebc_step_grid.h, restated: eight classes of ec = ceil(E / 8) consecutive envs; block r of a role works for
+    class r % 8, rank r // 8, on `upw` units (envs; ORCA: flat humans) of it; every role takes 8 Q blocks."""
+
+    def __init__(self, E, N, hpw, rows_epw):
+        self.E, self.N = E, N
+        self.ec = -(-E // 8)
+        self.upw = {"ENV": 16, "ORCA": hpw, "ROWS": rows_epw, "STATE": 64 // N}
+        self.per_class = {r: self.ec * (N if r == "ORCA" else 1) for r in self.upw}
+        self.units = {r: E * (N if r == "ORCA" else 1) for r in self.upw}
+        self.blocks = {r: 8 * -(-self.per_class[r] // self.upw[r]) for r in self.upw}
+        self.base, at = {}, 0
+        for r in ("ENV", "ORCA", "ROWS", "STATE"):
+            self.base[r] = at
+            at += self.blocks[r]
+        self.total = at
+
+    def span(self, role, r):
+        c, q = r % 8, r // 8
+        lo = c * self.per_class[role]
+        first = lo + q * self.upw[role]
+        return first, min(first + self.upw[role], lo + self.per_class[role], self.units[role])
+
+    def owns(self, np, role):
+        return np.array([self.span(role, r)[1] > self.span(role, r)[0] for r in range(self.blocks[role])])
+
+    def block_of(self, np, role, units):
+        """the block (index in the launch) that owns these units"""
+        c = units // self.per_class[role]
+        return self.base[role] + (units - c * self.per_class[role]) // self.upw[role] * 8 + c
 
 
 def report(np, name, rows, base):
