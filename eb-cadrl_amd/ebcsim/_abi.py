@@ -258,3 +258,24 @@ class EbcCadrlGradArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
                 ("reserved", C.c_int32)] + [
         (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "min_row")]
+
+
+SARL_NET_MAX_LAYERS = 16
+
+
+class EbcSarlNetWeights(C.Structure):
+    """include/ebcsim.h: the Linear layers of a SARL value network in the order mlp1, mlp2, attention, mlp3 (2 / 2 / 3 / 4 of
+    them), host pointers in torch's layout [out][in]; widths = the layers' units."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_mlp1", C.c_int32), ("n_mlp2", C.c_int32), ("n_attention", C.c_int32),
+                ("n_mlp3", C.c_int32), ("with_global_state", C.c_int32), ("self_state_dim", C.c_int32), ("input_dim", C.c_int32),
+                ("widths", C.c_int32 * SARL_NET_MAX_LAYERS), ("weight", C.c_void_p * SARL_NET_MAX_LAYERS),
+                ("bias", C.c_void_p * SARL_NET_MAX_LAYERS)]
+
+
+class EbcSarlGradArgs(C.Structure):
+    """include/ebcsim.h: one ebc_sarl_grad (rows [B][R][T] float32, n_valid [B] int64 or NULL, target [B] float32, sample_mask
+    [B] uint8 or NULL -> grad float32 [packed floats], loss_sum float64 [1], count int64 [1], value [B] float32 or NULL,
+    attention [B][R] float32 or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
+                ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "attention")]

@@ -245,6 +245,20 @@ class SarlValueNet(object):
         self.coarse_eps = None  # other weights: the refinement measures its bound again at the next decision
         return True
 
+    def refresh_from(self, state_dict_or_trainer):
+        """New weights for a network that decides: a state_dict of the reference's keys, or a sarl_train.SarlTrainer (its
+        master copy, read in place on the device).  They are copied into the tensors this network was built on, then
+        refresh_native() re-packs the blocks from them.  Returns what refresh_native returns."""
+        sd = state_dict_or_trainer
+        if hasattr(sd, "device_state_dict"):
+            sd = sd.device_state_dict()
+        with torch.no_grad():
+            for name in ("mlp1", "mlp2", "attention", "mlp3"):
+                for i, (w, b) in enumerate(getattr(self, name)):
+                    w.copy_(sd["%s.%d.weight" % (name, 2 * i)])
+                    b.copy_(sd["%s.%d.bias" % (name, 2 * i)])
+        return self.refresh_native()
+
     # the pair kernels under the names they had as methods of this class
     _pair_mean = staticmethod(pair_mean)
     _pair_attend = staticmethod(pair_attend)

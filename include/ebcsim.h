@@ -869,6 +869,72 @@ int ebc_cadrl_net_get_packed(void *net, void *stream, float *dst_dev);
 int ebc_cadrl_net_set_packed(void *net, void *stream, const float *src_dev);
 int ebc_cadrl_grad(void *net, void *stream, const EbcCadrlGradArgs *args);
 
+/* ---- training the SARL value network (rl/policy/sarl.py:38-82; rl/utils/trainer.py:74-100: MSE regression on value
+ * targets): the gradient of the loss with respect to every weight, in one launch per run of chunks that runs the forward
+ * of every row of a chunk's states (mlp1, mlp2, the mean, attention, the reference's masked softmax, the weighted sum,
+ * mlp3) with every activation kept in LDS and the backward through all of it, and a second small launch that adds the
+ * partial sums.  The arithmetic is csrc/ebc_sarl_grad_rule.h (one definition for the kernel and for the host build
+ * tests/native/sarl_grad_host.cc compares it with byte for byte).  Those are the forward's bytes for THIS entry; the
+ * deciding blocks (ebc_mlp2_*) agree with them to float32 rounding, not bit for bit.
+ *
+ * EbcSarlNetWeights: n_mlp1 / n_mlp2 / n_attention / n_mlp3 = 2 / 2 / 3 / 4 Linear layers (anything else is
+ * EBC_ERR_UNSUPPORTED); widths = the layers' units in the order mlp1, mlp2, attention, mlp3; weight / bias: HOST pointers
+ * in that order, torch's layout [out][in] / [out].  Limits: 1 <= input_dim <= 64, every width 1 .. 256, the last layers of
+ * attention and mlp3 one unit, 0 <= self_state_dim <= input_dim, else EBC_ERR_UNSUPPORTED and ebc_last_error names the limit.
+ * The packed image (weights, and the gradient alike): the eleven layers in that order, layer l as W[k][Op] — unit u of
+ * input k at k * Op + u, Op = the layer's units padded to a multiple of 4 — followed by bias[Op]; pad entries are exactly
+ * 0.  97 452 floats (381 KB) at the reference's widths with the global state. */
+#define EBC_SARL_NET_MAX_LAYERS 16
+typedef struct EbcSarlNetWeights {
+  uint32_t struct_size;
+  int32_t n_mlp1, n_mlp2, n_attention, n_mlp3;   /* 2, 2, 3, 4 */
+  int32_t with_global_state;
+  int32_t self_state_dim;
+  int32_t input_dim;                             /* the row width T */
+  int32_t widths[EBC_SARL_NET_MAX_LAYERS];       /* the layers' units */
+  const float *weight[EBC_SARL_NET_MAX_LAYERS];  /* host float32 [out][in] */
+  const float *bias[EBC_SARL_NET_MAX_LAYERS];    /* host float32 [out] */
+} EbcSarlNetWeights;
+/* One ebc_sarl_grad over B states of R row slots each:
+ *   n            = n_valid[b] clamped to [0, R] (NULL: R); rows at or past n are never read and receive nothing
+ *   value[b]     = the network's output on the state's rows [0, n); NaN without rows
+ *   attention[b] = the softmax weights of the rows [0, n) (e = exp(s) * (s != 0), no maximum subtracted), 0 at or past n
+ *   live         = (sample_mask == NULL or sample_mask[b] != 0) and n >= 1; a state that is not live enters no sum (a
+ *                  selection: its NaNs reach nothing but its own value and attention); a NaN inside a live state reaches
+ *                  loss_sum and grad
+ *   loss_sum     = the sum over the live states of (value - target)^2, count = their number
+ *   grad         = d/dweights of grad_scale / 2 * loss_sum (grad_scale = 2 / count: torch's MSELoss), packed layout
+ * The batch is cut into chunks of 4 consecutive states; inside a chunk a weight's sum is a float32 fmaf chain over the
+ * live states and their rows ascending, the chunks are added ascending in float64 and rounded once: the result depends on
+ * the inputs alone.  Every NaN written is the quiet NaN 0x7fc00000 (float64: 0x7ff8000000000000).  Scratch belongs to
+ * the network and grows on demand, exactly as ebc_cadrl_grad's: at most ONE ebc_sarl_grad in flight per network.  Device
+ * pointers.  1 <= R <= ebc_sarl_net_grad_max_rows (a chunk's activations must fit a workgroup's 160 KB of LDS: 15 at the
+ * reference widths), else EBC_ERR_UNSUPPORTED with nothing written; T other than the network's row width is
+ * EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcSarlGradArgs {
+  uint32_t struct_size;
+  int32_t B, R, T;
+  float grad_scale;
+  int32_t reserved;
+  const float *rows;            /* device float32 [B][R][T] */
+  const int64_t *n_valid;       /* device int64 [B]; NULL = all R rows */
+  const float *target;          /* device float32 [B] */
+  const uint8_t *sample_mask;   /* device uint8 [B]; NULL = every state counts */
+  float *grad;                  /* device float32 [ebc_sarl_net_packed_floats] */
+  double *loss_sum;             /* device float64 [1] */
+  int64_t *count;               /* device int64 [1] */
+  float *value;                 /* device float32 [B], or NULL */
+  float *attention;             /* device float32 [B][R], or NULL */
+} EbcSarlGradArgs;
+int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_id, void **net_out);
+int ebc_sarl_net_destroy(void *net);
+int ebc_sarl_net_packed_floats(void *net, int64_t *floats_out);
+int ebc_sarl_net_get_packed(void *net, void *stream, float *dst_dev);
+int ebc_sarl_net_set_packed(void *net, void *stream, const float *src_dev);
+/* the largest R ebc_sarl_grad takes for this network */
+int ebc_sarl_net_grad_max_rows(void *net, int *rows_out);
+int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *args);
+
 #ifdef __cplusplus
 }
 #endif
