@@ -279,3 +279,25 @@ class EbcSarlGradArgs(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
                 ("reserved", C.c_int32)] + [
         (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "attention")]
+
+
+LSTM_NET_LAYERS = 8
+
+
+class EbcLstmNetWeights(C.Structure):
+    """include/ebcsim.h: an LSTM-RL value network (rl/policy/lstm_rl.py:9-69): the Linear layers of mlp1 (slots 0 .. 3; n_mlp1
+    = 0 for ValueNetwork1) and mlp (slots 4 .. 7) and nn.LSTM's four tensors, host pointers in torch's layout."""
+    _fields_ = [("struct_size", C.c_uint32), ("n_mlp1", C.c_int32), ("n_mlp", C.c_int32), ("self_state_dim", C.c_int32),
+                ("input_dim", C.c_int32), ("lstm_input_dim", C.c_int32), ("hidden_dim", C.c_int32), ("reserved", C.c_int32),
+                ("widths", C.c_int32 * LSTM_NET_LAYERS), ("weight", C.c_void_p * LSTM_NET_LAYERS),
+                ("bias", C.c_void_p * LSTM_NET_LAYERS), ("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p),
+                ("b_hh", C.c_void_p)]
+
+
+class EbcLstmGradArgs(C.Structure):
+    """include/ebcsim.h: one ebc_lstm_grad (rows [B][R][T] float32, n_valid [B] int64 or NULL, target [B] float32, sample_mask
+    [B] uint8 or NULL -> grad float32 [packed floats], loss_sum float64 [1], count int64 [1], value [B] float32 or NULL,
+    joint [B][S + H] float32 or NULL)."""
+    _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
+                ("reserved", C.c_int32)] + [
+        (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "joint")]

@@ -97,6 +97,13 @@ SYMBOLS = {
     "ebc_sarl_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sarl_net_grad_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
     "ebc_sarl_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_lstm_net_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ebc_lstm_net_destroy": (C.c_int, [C.c_void_p]),
+    "ebc_lstm_net_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
+    "ebc_lstm_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_lstm_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_lstm_net_grad_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "ebc_lstm_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

@@ -163,6 +163,7 @@ class LstmValueNet(object):
         self.input_dim = self.module.input_dim
         self.self_state_dim = self.module.self_state_dim
         self.native_forwards = 0
+        self.native_refreshes = 0
         self.values_decidable = False
         self._native = None
 
@@ -184,6 +185,30 @@ class LstmValueNet(object):
             pre = tuple(Mlp2Block(mlp1[i:i + 2], idx) for i in (0, 2)) if mlp1 else ()
             self._native = (pre, _NativeLstm(m.lstm, idx), tuple(Mlp2Block(mlp[i:i + 2], idx) for i in (0, 2)))
         return self._native
+
+    def refresh_from(self, state_dict_or_trainer):
+        """New weights for a network that decides: a state_dict of the reference's keys, or a lstm_train.LstmTrainer (its
+        master copy, read in place on the device).  They are copied into the module's tensors; on a HIP device the float32
+        two-layer blocks (Mlp2Block.update) and the scan's packed weights (_NativeLstm.update) are then re-packed from
+        them on the device, and native_refreshes counts it.  The decisions afterwards are a freshly built LstmValueNet's.
+        Returns whether there were blocks to re-pack."""
+        sd = state_dict_or_trainer
+        if hasattr(sd, "device_state_dict"):
+            sd = sd.device_state_dict()
+        with torch.no_grad():
+            for k, p in self.module.state_dict().items():
+                p.copy_(sd[k])
+        nat = self._native_blocks()
+        if nat is None:
+            return False
+        m = self.module
+        pre, lstm, post = nat
+        for blocks, layers in ((pre, _stack(m.mlp1) if pre else []), (post, _stack(m.mlp))):
+            for i, blk in enumerate(blocks):
+                blk.update(layers[2 * i:2 * i + 2])
+        lstm.update(m.lstm)
+        self.native_refreshes += 1
+        return True
 
     def forward(self, rows, n_valid=None):
         """rows [B, R, T] float32; n_valid [B] or None = all -> values [B] float32."""

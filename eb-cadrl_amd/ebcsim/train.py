@@ -327,12 +327,14 @@ class DataParallelTrainer(object):
 
 
 def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generator=None,
-            human_policy=_abi.HUMAN_ORCA, store=None):
+            human_policy=_abi.HUMAN_ORCA, store=None, state_transform=None):
     """Roll the rank's env slice `steps` decisions forward with an epsilon-greedy SARL policy
     (multi_human_rl.py:31-33, :84-85) and push (state, value target) pairs.  env: BatchedEnv on
     the policy's device with auto-reset; returns the mean reward.  With an EpisodeStore the pairs
     reach the memory as the reference's do: per finished episode, successes and collisions only;
-    without one every step's pair goes in at once."""
+    without one every step's pair goes in at once.  state_transform(rows, n_valid) -> rows, when given, is applied to the
+    state that is stored and to the next state the target network values, not to what the policy decides on (LSTM-RL:
+    lstm_train.sort_rows_by_distance); None leaves every byte as it was."""
     dev = policy.net.device
     E, R, T = env.E, env.R, env.T
     cur = torch.zeros((E, R, T), dtype=torch.float32, device=dev)
@@ -354,11 +356,13 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
                         flags=_abi.FLAG_AUTO_RESET)
         # the returned observation belongs to the scene that was stepped (a terminal env's target is its
         # reward, its restart scene shows up in `cur` below): its row count is the decision's
-        targets = value_targets(outs["reward"], outs["done"], outs["obs_rotated"], target_net, gamma_bar, nv_cur)
+        nxt = outs["obs_rotated"] if state_transform is None else state_transform(outs["obs_rotated"], nv_cur)
+        targets = value_targets(outs["reward"], outs["done"], nxt, target_net, gamma_bar, nv_cur)
+        kept = cur if state_transform is None else state_transform(cur, nv_cur)
         if store is None:
-            memory.push(cur.clone(), targets, nv_cur)
+            memory.push(kept.clone(), targets, nv_cur)
         else:
-            store.add(cur, targets, nv_cur)
+            store.add(kept, targets, nv_cur)
             store.end(outs["done"], outs["info"], memory)
         total += float(outs["reward"].mean())
         # the next decision's state: the returned observation, or the reset scene after a terminal step

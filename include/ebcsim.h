@@ -935,6 +935,78 @@ int ebc_sarl_net_set_packed(void *net, void *stream, const float *src_dev);
 int ebc_sarl_net_grad_max_rows(void *net, int *rows_out);
 int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *args);
 
+/* ---- training the LSTM-RL value networks (rl/policy/lstm_rl.py:9-69: ValueNetwork1, rows -> LSTM -> mlp on cat(self
+ * state, h_n), lstm_rl.py:9-32; ValueNetwork2, rows -> mlp1 -> LSTM -> mlp, lstm_rl.py:35-69; rl/utils/trainer.py:74-100: MSE
+ * regression on value targets): the gradient of the loss with respect to every weight, in one launch per run of chunks
+ * that runs mlp1 over every row of a chunk's states, the recurrence a step at a time, mlp, and the backward through all of
+ * it, through time included, with every activation and every step's gates kept in LDS, and a second small launch that adds
+ * the partial sums.  The arithmetic is csrc/ebc_lstm_grad_rule.h (one definition for the kernel and for the host build
+ * tests/native/lstm_grad_host.cc compares it with byte for byte); the recurrence's forward is csrc/ebc_lstm_cell.h's, so
+ * ValueNetwork1's h_n is ebc_lstm_forward's, bit for bit.
+ *
+ * EbcLstmNetWeights: n_mlp1 = 0 (ValueNetwork1) or 4, n_mlp = 4 Linear layers (anything else is EBC_ERR_UNSUPPORTED);
+ * widths / weight / bias [0 .. 3]: mlp1's layers (not read when n_mlp1 = 0), [4 .. 7]: mlp's; HOST pointers, torch's layout
+ * [out][in] / [out]; w_ih [4 H][I], w_hh [4 H][H], b_ih [4 H], b_hh [4 H] as nn.LSTM keeps them (gate order i, f, g, o).
+ * Limits: 1 <= input_dim <= 64, the LSTM's input and hidden_dim 1 .. 64, every Linear width 1 .. 256, the last layer of mlp
+ * one unit, 0 <= self_state_dim <= input_dim, else EBC_ERR_UNSUPPORTED and ebc_last_error names the limit; lstm_input_dim
+ * must be mlp1's last width (n_mlp1 = 0: input_dim), else EBC_ERR_INVALID.
+ * The packed image (weights, and the gradient alike): mlp1's layers, then w_ih[k][4 H] (gate row q of input k at
+ * k * 4 H + q), w_hh[k][4 H], b_ih[4 H], b_hh[4 H], then mlp's layers; a Linear layer as W[k][Op] — unit u of input k at
+ * k * Op + u, Op = the layer's units padded to a multiple of 4 — followed by bias[Op]; pad entries are exactly 0.  b_ih and
+ * b_hh are two tensors that receive the same gradient.  87 248 floats at the reference's widths with mlp1, 47 268 without. */
+#define EBC_LSTM_NET_LAYERS 8
+typedef struct EbcLstmNetWeights {
+  uint32_t struct_size;
+  int32_t n_mlp1, n_mlp;                      /* 0 or 4, 4 */
+  int32_t self_state_dim;
+  int32_t input_dim;                          /* the row width T */
+  int32_t lstm_input_dim, hidden_dim;         /* I, H */
+  int32_t reserved;
+  int32_t widths[EBC_LSTM_NET_LAYERS];        /* the Linear layers' units */
+  const float *weight[EBC_LSTM_NET_LAYERS];   /* host float32 [out][in] */
+  const float *bias[EBC_LSTM_NET_LAYERS];     /* host float32 [out] */
+  const float *w_ih, *w_hh, *b_ih, *b_hh;     /* host float32, nn.LSTM's layout */
+} EbcLstmNetWeights;
+/* One ebc_lstm_grad over B states of R row slots each:
+ *   n            = n_valid[b] clamped to [0, R] (NULL: R); rows at or past n are never read and receive nothing
+ *   value[b]     = the network's output on the state's rows [0, n); NaN without rows
+ *   joint[b]     = mlp's input: the first self_state_dim floats of row 0, then h_n; zeros without rows
+ *   live         = (sample_mask == NULL or sample_mask[b] != 0) and n >= 1; a state that is not live enters no sum (a
+ *                  selection: its NaNs reach nothing but its own value and joint); a NaN inside a live state reaches
+ *                  loss_sum and grad
+ *   loss_sum     = the sum over the live states of (value - target)^2, count = their number
+ *   grad         = d/dweights of grad_scale / 2 * loss_sum (grad_scale = 2 / count: torch's MSELoss), packed layout
+ * The batch is cut into chunks of 4 consecutive states; inside a chunk a weight's sum is a float32 fmaf chain over the
+ * live states and their steps ascending, the chunks are added ascending in float64 and rounded once: the result depends on
+ * the inputs alone.  Every NaN written is the quiet NaN 0x7fc00000 (float64: 0x7ff8000000000000).  Scratch belongs to
+ * the network and grows on demand, exactly as ebc_sarl_grad's: at most ONE ebc_lstm_grad in flight per network.  Device
+ * pointers.  1 <= R <= ebc_lstm_net_grad_max_rows (a chunk's activations must fit a workgroup's 160 KB of LDS: 12 at the
+ * reference widths with mlp1, 26 without), else EBC_ERR_UNSUPPORTED with nothing written; T other than the network's row
+ * width is EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+typedef struct EbcLstmGradArgs {
+  uint32_t struct_size;
+  int32_t B, R, T;
+  float grad_scale;
+  int32_t reserved;
+  const float *rows;            /* device float32 [B][R][T] */
+  const int64_t *n_valid;       /* device int64 [B]; NULL = all R rows */
+  const float *target;          /* device float32 [B] */
+  const uint8_t *sample_mask;   /* device uint8 [B]; NULL = every state counts */
+  float *grad;                  /* device float32 [ebc_lstm_net_packed_floats] */
+  double *loss_sum;             /* device float64 [1] */
+  int64_t *count;               /* device int64 [1] */
+  float *value;                 /* device float32 [B], or NULL */
+  float *joint;                 /* device float32 [B][self_state_dim + H], or NULL */
+} EbcLstmGradArgs;
+int ebc_lstm_net_create(const EbcLstmNetWeights *weights, int device_id, void **net_out);
+int ebc_lstm_net_destroy(void *net);
+int ebc_lstm_net_packed_floats(void *net, int64_t *floats_out);
+int ebc_lstm_net_get_packed(void *net, void *stream, float *dst_dev);
+int ebc_lstm_net_set_packed(void *net, void *stream, const float *src_dev);
+/* the largest R ebc_lstm_grad takes for this network */
+int ebc_lstm_net_grad_max_rows(void *net, int *rows_out);
+int ebc_lstm_grad(void *net, void *stream, const EbcLstmGradArgs *args);
+
 #ifdef __cplusplus
 }
 #endif

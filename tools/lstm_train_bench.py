@@ -1,0 +1,114 @@
+#!/usr/bin/env python3
+"""Time of one LSTM-RL gradient, two ways on the same inputs and the same device: the kernel (ebc_lstm_grad: mlp1 over every
+row, the recurrence, mlp, the backward through all of it and through time, the reduction of the chunk partials) and torch
+autograd of LstmModule (forward, MSE loss, backward), at the reference's batch of 100 states and at 4096, with 5 and 10
+rows per state, T = 13, for both value networks; and a full optimizer step through LstmTrainer, native and autograd.
+
+    python3 tools/lstm_train_bench.py [--blocks 7] [--reps 20] [--out profiles/lstm_train.txt]
+
+Warm-up first, then the median over `--blocks` blocks of `--reps` back-to-back calls.  Two clocks per block: a pair of
+events on the stream (what the device sees from the first kernel's start to the last one's end, host gaps between the
+launches included) and the host's clock around the block with a synchronize at its end.  Every shape is printed, the
+ones where the kernel is slower too."""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "eb-cadrl_amd")):
+    sys.path.insert(0, p)
+
+SHAPES = [(100, 5), (100, 10), (4096, 5), (4096, 10)]
+NETWORKS = [("ValueNetwork2 (mlp1 150-100-100-50, H 50, mlp 150-100-100-1)", [150, 100, 100, 50]),
+            ("ValueNetwork1 (H 50, mlp 150-100-100-1)", None)]
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--blocks", type=int, default=7)
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--out", default=None, help="also append the lines to this file")
+    args = ap.parse_args()
+    import torch
+    from ebcsim import _capi
+    from ebcsim.lstm_rl import LstmModule
+    from ebcsim.lstm_train import LstmTrainer
+    lines = []
+
+    def say(text):
+        print(text, flush=True)
+        lines.append(text)
+
+    def timed(fn):
+        for _ in range(args.warmup):
+            fn()
+        torch.cuda.synchronize()
+        dev_ms, host_ms = [], []
+        for _ in range(args.blocks):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0 = time.perf_counter()
+            a.record()
+            for _ in range(args.reps):
+                fn()
+            b.record()
+            b.synchronize()
+            host_ms.append((time.perf_counter() - t0) * 1e3 / args.reps)
+            dev_ms.append(a.elapsed_time(b) / args.reps)
+        return statistics.median(dev_ms), min(dev_ms), max(dev_ms), statistics.median(host_ms)
+
+    dev = torch.device("cuda:0")
+    say("# tools/lstm_train_bench.py --blocks %d --reps %d: ms per call, median (min .. max) of the blocks by stream events, "
+        "and the host clock's median; rows 13 wide, self state 6; %s; library %s"
+        % (args.blocks, args.reps, torch.cuda.get_device_name(0), os.path.basename(_capi.LIB_PATH)))
+    for name, mlp1 in NETWORKS:
+        torch.manual_seed(11)
+        sd = LstmModule(13, 6, [150, 100, 100, 1], 50, mlp1).state_dict()
+        native = LstmTrainer(sd, device=dev, optimizer="sgd", lr=1e-3, native=True)
+        auto = LstmTrainer(sd, device=dev, optimizer="sgd", lr=1e-3, native=False)
+        module = LstmModule.from_state_dict(sd).to(dev)
+        say("# %s: %d packed floats, ebc_lstm_net_grad_max_rows = %d" % (name, native.net.packed_floats(), native.net.grad_max_rows()))
+        for B, R in SHAPES:
+            g = torch.Generator(device=dev).manual_seed(1000 * B + R)
+            rows = torch.randn((B, R, 13), generator=g, device=dev)
+            target = 0.5 * torch.randn((B,), generator=g, device=dev)
+            scale = 2.0 / B
+
+            def bare():
+                """what the reference's optimize_batch does between zero_grad and step"""
+                for p in module.parameters():
+                    p.grad = None
+                torch.nn.functional.mse_loss(module(rows).squeeze(1), target).backward()
+
+            def grad(tr):
+                return tr.loss_and_grad(rows, target, grad_scale=scale)
+
+            def step(tr):
+                grad(tr)
+                tr.step()
+
+            ln, cn = grad(native)
+            la, ca = grad(auto)
+            torch.cuda.synchronize()
+            gn, ga = native.flat.grad, auto.flat.grad
+            say("B %4d R %2d: count %d / %d, loss_sum %.9g / %.9g, largest |kernel - autograd| of the gradient %.3g (largest entry %.3g)"
+                % (B, R, int(cn), int(ca), float(ln), float(la), float((gn - ga).abs().max()), float(ga.abs().max())))
+            k = timed(lambda: grad(native))
+            say("B %4d R %2d  ebc_lstm_grad (forward, backward through time, reduction)        : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + k))
+            a = timed(bare)
+            say("B %4d R %2d  torch autograd of LstmModule (forward, MSE, backward)            : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + a))
+            say("B %4d R %2d  autograd / kernel: %.2f x by events, %.2f x by the host clock" % (B, R, a[0] / k[0], a[3] / k[3]))
+            ks = timed(lambda: step(native))
+            say("B %4d R %2d  full step, LstmTrainer native (loss_and_grad, SGD on the flat image, set_packed) : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + ks))
+            as_ = timed(lambda: step(auto))
+            say("B %4d R %2d  full step, LstmTrainer autograd (unpack, autograd, repack, SGD)                  : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + as_))
+            say("B %4d R %2d  LstmTrainer autograd / native: %.2f x by events, %.2f x by the host clock" % (B, R, as_[0] / ks[0], as_[3] / ks[3]))
+    if args.out:
+        with open(args.out, "a") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
