@@ -38,6 +38,9 @@
 //               dm[k] = (float)((double)dg[k] / (double)n) goes to every row < n.
 //   h1'         dh1[r][k] = relu_back(h1[r][k], (L2's dx + L4's dx at input k) + dm[k]); without global state the sum of the two.
 //
+// A wide row (OM-SARL: the occupancy map behind the rotated columns, up to 224 floats) is a longer ascending chain in layer
+// 0 and a longer dW there, and nothing else: no other step sees the row's width.
+//
 // Summation over samples.  The batch is cut into chunks of EBC_SARL_GRAD_CHUNK consecutive states.  Inside a chunk every
 // weight's chain starts at 0 and runs over the live states ascending and, for the layers that see rows (0 .. 6), over a
 // state's rows ascending.  The chunks' float32 partials are added in ascending chunk order in float64 and rounded to float32
@@ -63,7 +66,10 @@
 
 #define EBC_SARL_GRAD_CHUNK 4        // states per chunk: a float32 chain is at most 4 R terms long before float64 takes over
 #define EBC_SARL_GRAD_LAYERS 11      // 2 + 2 + 3 + 4
-#define EBC_SARL_GRAD_MAX_IN 64      // widest row
+#define EBC_SARL_GRAD_MAX_IN 64      // widest rotated row
+#define EBC_SARL_GRAD_MAX_OM 192     // widest occupancy map appended to a row (EBC_OM_MAX_WIDTH)
+#define EBC_SARL_GRAD_MAX_WIDE 224   // widest row with its map (EBC_OM_MAX_ROW_WIDTH: what the deciding blocks take)
+#define EBC_SARL_GRAD_MAX_ROW 256    // what the host build's buffers hold of a row, wide or not
 #define EBC_SARL_GRAD_MAX_WIDTH 256  // widest hidden layer
 #define EBC_SARL_GRAD_MAX_CHUNKS 256 // chunks one launch of the kernel takes (100 MB of partials at the reference widths)
 
@@ -120,6 +126,16 @@ EBC_CADRL_HD int grad_dims_refused(const int *widths, int self_dim) {
   return self_dim < 0 || self_dim > widths[0] ? 13 : 0;
 }
 
+// The network of OM-SARL: widths[0] = the rotated width T, and the rows the gradient reads are T + om_width wide (the maps
+// follow the rotated columns; the self state stays inside the first T).  grad_dims_refused's codes on the rotated widths,
+// and 14: om_width outside 0 .. 192; 15: T + om_width above 224.  Its dims are grad_dims on widths with [0] = T + om_width.
+EBC_CADRL_HD int grad_dims_refused_wide(const int *widths, int self_dim, int om_width) {
+  const int bad = grad_dims_refused(widths, self_dim);
+  if (bad) return bad;
+  if (om_width < 0 || om_width > EBC_SARL_GRAD_MAX_OM) return 14;
+  return widths[0] + om_width > EBC_SARL_GRAD_MAX_WIDE ? 15 : 0;
+}
+
 // exp(s) of a score
 EBC_CADRL_HD float score_exp(float s) {
   float sc, p;
@@ -173,7 +189,7 @@ struct StateActs {
   std::vector<float> a1, h1, b1, ft, c1, c2, xa, s, w, g, j, m1, m2, m3;
   explicit StateActs(int R)
       : n(0), a1((size_t)R * 256), h1((size_t)R * 256), b1((size_t)R * 256), ft((size_t)R * 256), c1((size_t)R * 256), c2((size_t)R * 256),
-        xa((size_t)R * 512), s(R), w(R), g(256), j(EBC_SARL_GRAD_MAX_IN + 256), m1(256), m2(256), m3(256) {}
+        xa((size_t)R * 512), s(R), w(R), g(256), j(EBC_SARL_GRAD_MAX_ROW + 256), m1(256), m2(256), m3(256) {}
 };
 
 // the forward of ONE state with n >= 1 rows x[r][0 .. T) -> L10's output
@@ -221,7 +237,7 @@ inline float grad_forward_state(const float *P, const GradDims &D, const float *
 // their deltas, as the kernel overwrites them
 inline void grad_backward_state(const float *P, float *G, const GradDims &D, const float *x, StateActs &A, float seed) {
   const int H = D.O[L_M1B], F = D.O[L_M2B], n = A.n;
-  float d[512], dj[EBC_SARL_GRAD_MAX_IN + 256];
+  float d[512], dj[EBC_SARL_GRAD_MAX_ROW + 256];
   grad_linear(P, G, D, L_M3D, A.m3.data(), &seed, d);
   for (int k = 0; k < D.K[L_M3D]; ++k) A.m3[k] = grad_relu_back(A.m3[k], d[k]);
   grad_linear(P, G, D, L_M3C, A.m2.data(), A.m3.data(), d);

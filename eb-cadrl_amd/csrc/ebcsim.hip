@@ -15,6 +15,7 @@
 #include "ebc_dagger.h"
 #include "ebc_kernels.h"
 #include "ebc_local_map_kernel.h"
+#include "ebc_om_state.h"
 #include "ebc_rollout.h"
 #include "ebc_sail_api.h"
 
@@ -925,6 +926,44 @@ int launch_observe(Handle *h, double *d_ob, float *d_obs) {
   return EBC_OK;
 }
 
+size_t om_width(const EbcOmSpec &spec) { return (size_t)spec.cell_num * spec.cell_num * spec.channels; }
+
+// ebc_occupancy_rows' limits on a spec, for this handle's R and T; `what` names the entry in the refusal
+int check_om_spec(const Handle *h, const EbcOmSpec *spec, const char *what) {
+  const std::string who = std::string(what) + ": ";
+  if (spec->channels < 1 || spec->channels > 3)
+    return fail(EBC_ERR_UNSUPPORTED, who + "channels not in {1, 2, 3} (" + std::to_string(spec->channels) + ")");
+  if (spec->cell_num < 1) return fail(EBC_ERR_UNSUPPORTED, who + "cell_num < 1 (" + std::to_string(spec->cell_num) + ")");
+  if (!(std::isfinite(spec->cell_size) && spec->cell_size > 0.0)) return fail(EBC_ERR_UNSUPPORTED, who + "cell_size is not a finite positive number");
+  const long long W = (long long)spec->cell_num * spec->cell_num * spec->channels, R = h->s.N + h->s.S;
+  if (W > EBC_OM_MAX_WIDTH) return fail(EBC_ERR_UNSUPPORTED, who + "W > 192 map columns (" + std::to_string(W) + ")");
+  if (R > EBC_OM_MAX_ROWS) return fail(EBC_ERR_UNSUPPORTED, who + "R > 128 row slots (" + std::to_string(R) + ")");
+  if (h->T + W > EBC_OM_MAX_ROW_WIDTH)
+    return fail(EBC_ERR_UNSUPPORTED, who + "T + W > 224 columns, the blocks' input limit (" + std::to_string(h->T + W) + ")");
+  return EBC_OK;
+}
+
+// observe_wide_kernel for every env (a checked spec) -> d_wide [E][R][T + W], d_rows [E] or nullptr, on the handle's stream
+int launch_observe_wide(Handle *h, const EbcOmSpec &spec, float *d_wide, long long *d_rows) {
+  if (h->s.E == 0) return EBC_OK;
+  const int R = h->s.N + h->s.S;
+  const size_t lds = ebc::om_state_lds_bytes(R, (int)om_width(spec), h->T);  // <= 110.5 KB at R = 128, W = 192, T = 17
+  const void *fn = h->T == 17 ? (const void *)ebc::observe_wide_kernel<17> : (const void *)ebc::observe_wide_kernel<13>;
+  static size_t raised_dev[2][64] = {{0}};  // more than the 64 KB a launch gets by default; a function attribute is per device
+  size_t &raised = raised_dev[h->T == 17][h->device & 63];
+  if (lds > 65536 && lds > raised) {
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    raised = lds;
+  }
+  const ebc::OmStateSpec sp = {spec.cell_size, spec.cell_num, spec.channels};
+  if (h->T == 17)
+    hipLaunchKernelGGL((ebc::observe_wide_kernel<17>), dim3((unsigned)h->s.E), dim3(EBC_OMS_THREADS), lds, h->stream, h->p, h->s, sp, d_wide, d_rows);
+  else
+    hipLaunchKernelGGL((ebc::observe_wide_kernel<13>), dim3((unsigned)h->s.E), dim3(EBC_OMS_THREADS), lds, h->stream, h->p, h->s, sp, d_wide, d_rows);
+  HIP_TRY(hipGetLastError());
+  return EBC_OK;
+}
+
 // EBC_FLAG_ONE_LAUNCH: rollout_kernel (ebc_rollout.h), a workgroup per group of envs for all K steps.
 // EBC_ROBOT_SAIL: the network's LDS area for `chunk` envs, in bytes
 unsigned sail_area(const Handle *h, int chunk) { return (unsigned)(ebc::sail_lds_floats(chunk, h->sail_N) * sizeof(float)); }
@@ -1091,14 +1130,22 @@ static int refuse_capture(Handle *h, const char *what) {
   return EBC_OK;
 }
 
-int ebc_step_k(void *handle, const EbcStepKArgs *a) {
+// ebc_step_k, and with `om` (ebc_step_k_om) the wide state of every state the policy sees, enqueued before step k
+static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om, const char *what) {
   Handle *h;
   int rc = check_handle(handle, &h);
   if (rc) return rc;
+  const std::string who = what;
   if (!a || a->struct_size != sizeof(EbcStepKArgs)) return fail(EBC_ERR_INVALID, "EbcStepKArgs.struct_size");
-  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_step_k before ebc_reset");
-  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_step_k: the handle reported a mailbox fault; ebc_reset re-arms it");
-  if ((rc = refuse_capture(h, "ebc_step_k")) != EBC_OK) return rc;
+  if (!h->has_reset) return fail(EBC_ERR_STATE, who + " before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, who + ": the handle reported a mailbox fault; ebc_reset re-arms it");
+  if ((rc = refuse_capture(h, what)) != EBC_OK) return rc;
+  if (om) {
+    if (!om->state_wide) return fail(EBC_ERR_INVALID, who + ": state_wide is NULL");
+    if ((rc = check_om_spec(h, &om->spec, what)) != EBC_OK) return rc;
+    if (a->flags & EBC_FLAG_ONE_LAUNCH)
+      return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH (the window with maps has the per-step form only)");
+  }
   if (a->K < 1) return fail(EBC_ERR_INVALID, "K");
   if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL)
     return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
@@ -1106,18 +1153,18 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
       a->robot_policy != EBC_ROBOT_SAIL)
     return fail(EBC_ERR_INVALID, "robot_policy");
   const bool sail = a->robot_policy == EBC_ROBOT_SAIL;
-  if (sail && !h->sail_P) return fail(EBC_ERR_STATE, "ebc_step_k: EBC_ROBOT_SAIL with no network attached (ebc_robot_sail)");
+  if (sail && !h->sail_P) return fail(EBC_ERR_STATE, who + ": EBC_ROBOT_SAIL with no network attached (ebc_robot_sail)");
   if (a->robot_policy == EBC_ROBOT_EXTERNAL && !a->robot_action) return fail(EBC_ERR_INVALID, "robot_action is NULL");
   if (a->robot_policy == EBC_ROBOT_LINEAR && h->p.robot_kinematics != EBC_HOLONOMIC)
     return fail(EBC_ERR_UNSUPPORTED, "the linear robot policy is holonomic (simulator/policy/linear.py:11)");
   if (a->robot_policy == EBC_ROBOT_ORCA && (rc = check_robot_orca(h, a->robot_safety_space)) != EBC_OK) return rc;
-  if (a->flags & EBC_FLAG_BORDER) return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: no border");
+  if (a->flags & EBC_FLAG_BORDER) return fail(EBC_ERR_UNSUPPORTED, who + ": no border");
   const bool one_launch = (a->flags & EBC_FLAG_ONE_LAUNCH) != 0;
   // strict: a caller who sets the flag knows which form ran
   if (one_launch && a->human_policy == EBC_HUMAN_LINEAR)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_LINEAR (the one-launch form moves ORCA humans only)");
+    return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_LINEAR (the one-launch form moves ORCA humans only)");
   if (one_launch && a->human_policy == EBC_HUMAN_EXTERNAL)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_step_k: EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_EXTERNAL (the one-launch form moves ORCA humans only)");
+    return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_EXTERNAL (the one-launch form moves ORCA humans only)");
   const DevState &s = h->s;
   const size_t E = s.E, R = s.N + s.S, T = h->T, K = (size_t)a->K;
   const double *d_act_in = a->robot_action;
@@ -1174,6 +1221,7 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
     }
   }
   for (size_t k = 0; k < K; ++k) {
+    if (om && (rc = launch_observe_wide(h, om->spec, om->state_wide + k * E * R * (T + om_width(om->spec)), nullptr)) != EBC_OK) return rc;
     if (d_state && (rc = launch_observe(h, nullptr, d_state + k * E * R * T)) != EBC_OK) return rc;
     if (d_rows) {
       hipLaunchKernelGGL(ebc::row_counts_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, h->stream, h->s, d_rows + k * E);
@@ -1212,6 +1260,15 @@ int ebc_step_k(void *handle, const EbcStepKArgs *a) {
   }
   if (a->location != EBC_DEVICE) return st.finish();
   return EBC_OK;
+}
+
+int ebc_step_k(void *handle, const EbcStepKArgs *a) { return step_k_impl(handle, a, nullptr, "ebc_step_k"); }
+
+int ebc_step_k_om(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om) {
+  if (!om) return fail(EBC_ERR_INVALID, "ebc_step_k_om: om is NULL");
+  if (om->struct_size != sizeof(EbcStepKOm)) return fail(EBC_ERR_INVALID, "EbcStepKOm.struct_size");
+  if (om->spec.struct_size != sizeof(EbcOmSpec)) return fail(EBC_ERR_INVALID, "EbcOmSpec.struct_size");
+  return step_k_impl(handle, a, om, "ebc_step_k_om");
 }
 
 // K closed-loop steps of the attached SAIL network with the ORCA robot labelling every state (csrc/ebc_dagger.h): per
@@ -1527,6 +1584,21 @@ int ebc_row_counts(void *handle, int location, long long *n_rows) {
   HIP_TRY(hipGetLastError());
   if (location != EBC_DEVICE) return st.finish();
   return EBC_OK;
+}
+
+int ebc_observe_wide(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows) {
+  if (!spec || spec->struct_size != sizeof(EbcOmSpec)) return fail(EBC_ERR_INVALID, "EbcOmSpec.struct_size");
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_observe_wide before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_observe_wide: the handle reported a mailbox fault; ebc_reset re-arms it");
+  if (!state_wide) return fail(EBC_ERR_INVALID, "ebc_observe_wide: state_wide is NULL");
+  if ((rc = check_om_spec(h, spec, "ebc_observe_wide")) != EBC_OK) return rc;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(h->stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_observe_wide: the stream is being captured into a HIP graph; the maps must be launched, not replayed");
+  return launch_observe_wide(h, *spec, state_wide, n_rows);
 }
 
 int ebc_il_targets(void *stream, const double *reward, const uint8_t *done, const uint8_t *info, int K, int E,

@@ -31,34 +31,42 @@ bool capturing(void *stream) {
 
 }  // namespace
 
-extern "C" int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_id, void **net_out) {
+// ebc_sarl_net_create (om_width 0) and ebc_sarl_net_create_om; `what` names the entry in a refusal
+static int net_create(const EbcSarlNetWeights *weights, int om_width, int device_id, void **net_out, const char *what) {
+  const std::string who = std::string(what) + ": ";
   if (!weights || weights->struct_size != sizeof(EbcSarlNetWeights)) return fail(EBC_ERR_INVALID, "EbcSarlNetWeights.struct_size");
-  if (!net_out) return fail(EBC_ERR_INVALID, "ebc_sarl_net_create: null net_out");
+  if (!net_out) return fail(EBC_ERR_INVALID, who + "null net_out");
   const EbcSarlNetWeights &w = *weights;
   if (w.n_mlp1 != 2 || w.n_mlp2 != 2 || w.n_attention != 3 || w.n_mlp3 != 4)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_create: mlp1 / mlp2 / attention / mlp3 have " + std::to_string(w.n_mlp1) + " / " +
+    return fail(EBC_ERR_UNSUPPORTED, who + "mlp1 / mlp2 / attention / mlp3 have " + std::to_string(w.n_mlp1) + " / " +
                                          std::to_string(w.n_mlp2) + " / " + std::to_string(w.n_attention) + " / " + std::to_string(w.n_mlp3) +
                                          " Linear layers, the gradient takes exactly 2 / 2 / 3 / 4");
   int widths[EBC_SARL_GRAD_LAYERS + 1];
   widths[0] = w.input_dim;
   for (int l = 0; l < EBC_SARL_GRAD_LAYERS; ++l) widths[l + 1] = w.widths[l];
-  const int bad = ebc_sarl::grad_dims_refused(widths, w.self_state_dim);
+  const int bad = ebc_sarl::grad_dims_refused_wide(widths, w.self_state_dim, om_width);
   if (bad == 1)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_create: rows of " + std::to_string(widths[0]) + " floats, the gradient takes 1 .. " +
+    return fail(EBC_ERR_UNSUPPORTED, who + "rows of " + std::to_string(widths[0]) + " floats, the gradient takes 1 .. " +
                                          std::to_string(EBC_SARL_GRAD_MAX_IN));
+  if (bad == 14)
+    return fail(EBC_ERR_UNSUPPORTED, who + "om_width " + std::to_string(om_width) + " outside 0 .. " + std::to_string(EBC_SARL_GRAD_MAX_OM));
+  if (bad == 15)
+    return fail(EBC_ERR_UNSUPPORTED, who + "T + om_width = " + std::to_string(widths[0] + om_width) + " columns, the gradient takes up to " +
+                                         std::to_string(EBC_SARL_GRAD_MAX_WIDE));
   if (bad == 13)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_create: self_state_dim " + std::to_string(w.self_state_dim) + " outside 0 .. the row width");
+    return fail(EBC_ERR_UNSUPPORTED, who + "self_state_dim " + std::to_string(w.self_state_dim) + " outside 0 .. the row width");
   if (bad == ebc_sarl::L_ATC + 2 || bad == ebc_sarl::L_M3D + 2)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_create: the last layer of " + std::string(bad == ebc_sarl::L_ATC + 2 ? "attention" : "mlp3") + " has " +
+    return fail(EBC_ERR_UNSUPPORTED, who + "the last layer of " + std::string(bad == ebc_sarl::L_ATC + 2 ? "attention" : "mlp3") + " has " +
                                          std::to_string(widths[bad - 1]) + " outputs, the gradient takes exactly 1");
   if (bad)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_create: layer " + std::to_string(bad - 1) + " (counted through mlp1, mlp2, attention, mlp3) has " +
+    return fail(EBC_ERR_UNSUPPORTED, who + "layer " + std::to_string(bad - 1) + " (counted through mlp1, mlp2, attention, mlp3) has " +
                                          std::to_string(widths[bad - 1]) + " units, the gradient takes 1 .. " + std::to_string(EBC_SARL_GRAD_MAX_WIDTH));
   for (int l = 0; l < EBC_SARL_GRAD_LAYERS; ++l)
-    if (!w.weight[l] || !w.bias[l]) return fail(EBC_ERR_INVALID, "ebc_sarl_net_create: null weight or bias of layer " + std::to_string(l + 1));
+    if (!w.weight[l] || !w.bias[l]) return fail(EBC_ERR_INVALID, who + "null weight or bias of layer " + std::to_string(l + 1));
   HIP_TRY(hipSetDevice(device_id));
   SarlNet *n = new SarlNet;
   n->device = device_id;
+  widths[0] += om_width;  // the rows the gradient reads: the rotated columns, then the map
   n->D = ebc_sarl::grad_dims(widths, w.self_state_dim, w.with_global_state);
   n->max_rows = ebc::sarl_grad_max_rows(n->D);
   std::vector<float> image(n->D.floats);
@@ -68,10 +76,18 @@ extern "C" int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_
   if (err != hipSuccess) {
     if (n->P) (void)hipFree(n->P);
     delete n;
-    return fail(EBC_ERR_DEVICE, std::string("ebc_sarl_net_create: ") + hipGetErrorString(err));
+    return fail(EBC_ERR_DEVICE, who + hipGetErrorString(err));
   }
   *net_out = n;
   return EBC_OK;
+}
+
+extern "C" int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_id, void **net_out) {
+  return net_create(weights, 0, device_id, net_out, "ebc_sarl_net_create");
+}
+
+extern "C" int ebc_sarl_net_create_om(const EbcSarlNetWeights *weights, int om_width, int device_id, void **net_out) {
+  return net_create(weights, om_width, device_id, net_out, "ebc_sarl_net_create_om");
 }
 
 extern "C" int ebc_sarl_net_destroy(void *net) {

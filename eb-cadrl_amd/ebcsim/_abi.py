@@ -208,6 +208,25 @@ class EbcOmArgs(C.Structure):
         (k, C.c_void_p) for k in ("next_ob", "n_valid", "rows", "om", "rows_wide")]
 
 
+class EbcOmSpec(C.Structure):
+    """include/ebcsim.h: [om] cell_num / om_channel_size / cell_size, what ebc_observe_wide and ebc_step_k_om build the maps with."""
+    _fields_ = [("struct_size", C.c_uint32), ("cell_num", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32),
+                ("cell_size", C.c_double)]
+
+
+class EbcStepKOm(C.Structure):
+    """include/ebcsim.h: what ebc_step_k_om adds to ebc_step_k: the spec and state_wide, device float32 [K][E][R][T + W]."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("spec", EbcOmSpec), ("state_wide", C.c_void_p)]
+
+
+def om_spec(spec):
+    """An occupancy.OccupancySpec (cell_num, cell_size, channels) as the struct."""
+    s = EbcOmSpec()
+    s.struct_size = C.sizeof(s)
+    s.cell_num, s.channels, s.cell_size = int(spec.cell_num), int(spec.channels), float(spec.cell_size)
+    return s
+
+
 SAIL_LAYERS = 14
 
 

@@ -75,6 +75,8 @@ SYMBOLS = {
     "ebc_lstm_destroy": (C.c_int, [C.c_void_p]),
     "ebc_cadrl_decide": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ebc_occupancy_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p]),
+    "ebc_observe_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_step_k_om": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_sail_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_destroy": (C.c_int, [C.c_void_p]),
@@ -91,6 +93,7 @@ SYMBOLS = {
     "ebc_cadrl_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_cadrl_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sarl_net_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "ebc_sarl_net_create_om": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ebc_sarl_net_destroy": (C.c_int, [C.c_void_p]),
     "ebc_sarl_net_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ebc_sarl_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

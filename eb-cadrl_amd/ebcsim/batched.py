@@ -309,6 +309,17 @@ class BatchedEnv:
             raise ValueError("n_rows must be a contiguous int64 [E] tensor")
         _capi.check(self._L.ebc_row_counts(self._h, _abi.DEVICE, n_rows.data_ptr()))
 
+    def observe_wide_device(self, out, spec, n_rows=None):
+        """The state OM-SARL stores (multi_human_rl.py:128-149 transform): the rotated rows of the current state with its
+        occupancy maps appended, one kernel (ebc_observe_wide), into a torch CUDA float32 [E, R, T + spec.width] tensor;
+        n_rows: an int64 [E] tensor for ebc_row_counts' counts from the same read.  Enqueued on the handle's stream."""
+        if out.dtype.itemsize != 4 or out.numel() != self.E * self.R * (self.T + spec.width) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [E, R, %d] tensor" % (self.T + spec.width))
+        if n_rows is not None and (n_rows.dtype.itemsize != 8 or n_rows.numel() != self.E or not n_rows.is_contiguous()):
+            raise ValueError("n_rows must be a contiguous int64 [E] tensor")
+        s = _abi.om_spec(spec)
+        _capi.check(self._L.ebc_observe_wide(self._h, C.addressof(s), out.data_ptr(), None if n_rows is None else n_rows.data_ptr()))
+
     def robot_orca(self, safety_space=0.0):
         """ORCA.predict with the robot as the agent, every env (ebc_robot_orca) -> actions [E, 2]:
         the imitation-learning demonstrator (rl/train.py:99-143)."""
@@ -462,26 +473,45 @@ class BatchedEnv:
         _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
         return out
 
-    def alloc_step_k_outputs(self, K, keys=("reward", "done", "info", "state_rotated")):
-        """torch CUDA tensors [K, ...] for step_k_device(); the caller owns them."""
+    def alloc_step_k_outputs(self, K, keys=("reward", "done", "info", "state_rotated"), om=None):
+        """torch CUDA tensors [K, ...] for step_k_device(); the caller owns them.  The key "state_wide" (with om, an
+        occupancy.OccupancySpec) is [K, E, R, T + om.width] float32."""
         import torch
         dev = torch.device("cuda", self.device)
         shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
+        if "state_wide" in keys:
+            if om is None:
+                raise ValueError("the output state_wide needs om, the occupancy spec")
+            shapes["state_wide"] = ((self.E, self.R, self.T + om.width), "float32")
         return {k: torch.zeros((K,) + shapes[k][0], dtype=getattr(torch, shapes[k][1]), device=dev) for k in keys}
 
     def step_k_device(self, outputs, K, robot_action=None, human_policy=_abi.HUMAN_ORCA,
-                      robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0):
-        """Enqueue K steps (ebc_step_k) writing into torch CUDA tensors [K, ...] (not copied); flags as step_k."""
+                      robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0, om=None):
+        """Enqueue K steps (ebc_step_k) writing into torch CUDA tensors [K, ...] (not copied); flags as step_k.  om (an
+        occupancy.OccupancySpec) with the output "state_wide" [K, E, R, T + om.width]: ebc_step_k_om, which also writes the
+        wide state of the state the policy sees before every step (per-step form only)."""
+        if (om is None) != ("state_wide" not in outputs):
+            raise ValueError("om and the output state_wide go together")
         for k, t in outputs.items():
             if t.shape[0] != K or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous [K, ...] tensor" % k)
         if robot_action is not None and (robot_action.dtype.itemsize != 8 or robot_action.numel() != K * self.E * 2
                                          or not robot_action.is_contiguous()):
             raise ValueError("robot_action must be a contiguous float64 [K, E, 2] tensor")
-        args = self._step_k_args(K, _abi.DEVICE, {k: t.data_ptr() for k, t in outputs.items()}, human_policy,
+        args = self._step_k_args(K, _abi.DEVICE, {k: t.data_ptr() for k, t in outputs.items() if k != "state_wide"}, human_policy,
                                  robot_policy, flags, robot_safety_space,
                                  None if robot_action is None else robot_action.data_ptr())
-        _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
+        if om is None:
+            _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
+            return
+        wide = outputs["state_wide"]
+        if wide.dtype.itemsize != 4 or wide.numel() != K * self.E * self.R * (self.T + om.width):
+            raise ValueError("state_wide must be a float32 [K, E, R, %d] tensor" % (self.T + om.width))
+        w = _abi.EbcStepKOm()
+        w.struct_size = C.sizeof(w)
+        w.spec = _abi.om_spec(om)
+        w.state_wide = wide.data_ptr()
+        _capi.check(self._L.ebc_step_k_om(self._h, C.addressof(args), C.addressof(w)))
 
     _DAGGER_SHAPES = staticmethod(lambda E, R: dict(
         robot=((E, 9), "float64"), ob=((E, R, 5), "float64"), n_rows=((E,), "int64"), learner_action=((E, 2), "float64"),

@@ -132,6 +132,34 @@ def widen(rows, om):
     return torch.cat([rows, om.to(rows.dtype).unsqueeze(-3).expand(*rows.shape[:-1], om.shape[-1])], dim=-1)
 
 
+def wide_state(rotated, ob, n_valid, spec):
+    """The state OM-SARL stores (multi_human_rl.py:128-149 transform = [rotate(state) | build_occupancy_maps(state)]):
+    rotated [E, R, T] float32 (the rotated rows of the CURRENT state), ob [E, R, >= 4] float64 (its world-frame rows) and
+    n_valid [E] or None -> [E, R, T + W] float32.  Rows at or past n_valid[e] keep their rotated padding and get zero maps.
+    `widen` of one "action" over `occupancy_maps`: the CPU path, and the checker of ebc_observe_wide."""
+    rotated = np.asarray(rotated, dtype=np.float32)
+    return widen(rotated[:, None], occupancy_maps(ob, n_valid, spec))[:, 0]
+
+
+def observe_wide_composed(env, spec, out=None, n_rows=None):
+    """What BatchedEnv.observe_wide_device gives, from the four calls it replaces (ebc_observe twice, ebc_row_counts,
+    ebc_occupancy_rows) and a cat: the composition the kernel is held to byte for byte, and measured against."""
+    import torch
+    dev = torch.device("cuda", env.device)
+    rot = torch.empty((env.E, env.R, env.T), dtype=torch.float32, device=dev)
+    ob = torch.empty((env.E, env.R, 5), dtype=torch.float64, device=dev)
+    n = torch.empty((env.E,), dtype=torch.int64, device=dev) if n_rows is None else n_rows
+    env.observe_device(rot)
+    env.observe_ob_device(ob)
+    env.row_counts_device(n)
+    om, _ = occupancy_rows_device(ob, n, spec)
+    wide = torch.cat([rot, om], dim=2)
+    if out is not None:
+        out.copy_(wide)
+        return out
+    return wide
+
+
 def occupancy_rows_device(next_ob, n_valid, spec, rows=None, om_out=None, wide_out=None, want_om=True):
     """ebc_occupancy_rows on torch CUDA tensors, enqueued on the current stream: next_ob [E, R, 5] float64, n_valid [E]
     int64 or None, rows [E, A, R, T] float32 or None -> (om [E, R, W] or None, rows_wide [E, A, R, T + W] or None).

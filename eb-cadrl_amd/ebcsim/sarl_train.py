@@ -12,8 +12,11 @@ comparison path, and what the CPU tests drive.  ebcsim.train.DataParallelTrainer
 The loss is the reference's (rl/utils/trainer.py:74-100): the mean squared error between the network's value of a state
 and its target.  optimize_epoch and optimize_batch are cadrl_train's (they take any trainer with this interface);
 run_sarl_training is the schedule of rl/train.py:99-260 on the generic pieces of ebcsim.train with this trainer in the
-optimizer's place and DeviceSarlPolicy deciding.  Occupancy maps are not part of the schedule (the kernel takes the wide
-rows; the replay and the collection do not)."""
+optimizer's place and DeviceSarlPolicy deciding.
+
+OM-SARL (om_width = W > 0, run_sarl_training(om=spec)): mlp1's first layer takes T + W inputs, the kernel's network is
+ebc_sarl_net_create_om's, the stored states are the wide ones (BatchedEnv.observe_wide_device, ebc_step_k_om) and
+DeviceSarlPolicy(om=spec) decides.  The width of the maps is not in a state_dict (only T + W is): it is given explicitly."""
 import collections
 import ctypes as C
 import os
@@ -29,6 +32,7 @@ LAYER_KEYS = ("mlp1.0", "mlp1.2", "mlp2.0", "mlp2.2", "attention.0", "attention.
               "mlp3.6")
 STACKS = (("mlp1", 2), ("mlp2", 2), ("attention", 3), ("mlp3", 4))
 MAX_IN, MAX_WIDTH = 64, 256  # csrc/ebc_sarl_grad_rule.h
+MAX_OM, MAX_WIDE = 192, 224  # the same: the widest map behind a row, the widest row with its map
 
 
 def _stack_keys(sd):
@@ -113,9 +117,10 @@ def module_of(sd):
 class SarlNet(object):
     """The kernel's network object (ebc_sarl_net_*): the packed image of a state_dict in device memory."""
 
-    def __init__(self, sd, device_index, widths=None, self_state_dim=None, with_global_state=None, stack_layers=None):
+    def __init__(self, sd, device_index, widths=None, self_state_dim=None, with_global_state=None, stack_layers=None, om_width=None):
         """widths / self_state_dim / with_global_state / stack_layers override what the state_dict says (the tests of the
-        entry's refusals)."""
+        entry's refusals).  om_width: None = ebc_sarl_net_create; an int W = ebc_sarl_net_create_om, whose rotated width
+        is mlp1.0.weight.shape[1] - W (widths[0], when given, is that rotated width)."""
         from . import _capi
         self._L = _capi.lib()
         keys = [k for ks in _stack_keys(sd).values() for k in ks]
@@ -132,7 +137,7 @@ class SarlNet(object):
         att_in = int(sd["attention.0.weight"].shape[1])
         w.with_global_state = int(att_in == 2 * H) if with_global_state is None else int(with_global_state)
         units = [int(a.shape[0]) for a, _ in host] if widths is None else list(widths[1:])
-        w.input_dim = int(host[0][0].shape[1]) if widths is None else int(widths[0])
+        w.input_dim = int(host[0][0].shape[1]) - int(om_width or 0) if widths is None else int(widths[0])
         F = units[counts[0] + counts[1] - 1]
         w.self_state_dim = int(sd["mlp3.0.weight"].shape[1]) - F if self_state_dim is None else int(self_state_dim)
         for i, v in enumerate(units):
@@ -140,8 +145,12 @@ class SarlNet(object):
         for i, (a, b) in enumerate(host):
             w.weight[i], w.bias[i] = a.ctypes.data, b.ctypes.data
         self._h = C.c_void_p()
-        _capi.check(self._L.ebc_sarl_net_create(C.addressof(w), int(device_index), C.byref(self._h)))
-        self.widths = [w.input_dim] + units
+        if om_width is None:
+            _capi.check(self._L.ebc_sarl_net_create(C.addressof(w), int(device_index), C.byref(self._h)))
+        else:
+            _capi.check(self._L.ebc_sarl_net_create_om(C.addressof(w), int(om_width), int(device_index), C.byref(self._h)))
+        self.om_width = int(om_width or 0)
+        self.widths = [w.input_dim + self.om_width] + units  # [0]: the rows ebc_sarl_grad takes
 
     def packed_floats(self):
         from . import _capi
@@ -197,13 +206,21 @@ class SarlNet(object):
 class SarlTrainer(object):
     """module_or_state_dict: a SarlModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
-    (HIP devices only; the default there) or torch autograd of SarlModule."""
+    (HIP devices only; the default there) or torch autograd of SarlModule.  om_width: the W of OM-SARL's maps; the
+    network's mlp1.0 then takes T + W inputs, T = widths[0] - W the rotated width (1 .. 64), W <= 192, T + W <= 224."""
 
-    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None):
+    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, om_width=0):
         sd = module_or_state_dict.state_dict() if isinstance(module_or_state_dict, torch.nn.Module) else module_or_state_dict
         sd = collections.OrderedDict((k, v.detach().to("cpu", torch.float32)) for k, v in sd.items())
         self.device = torch.device(device)
         self.widths, self.self_state_dim, self.with_global_state = shape_of(sd)
+        self.om_width = int(om_width)
+        if not 0 <= self.om_width <= MAX_OM:
+            raise NotImplementedError("SarlTrainer: om_width %d outside 0 .. %d" % (self.om_width, MAX_OM))
+        if self.widths[0] - self.om_width < 1:
+            raise ValueError("SarlTrainer: om_width %d leaves no rotated columns of mlp1.0's %d inputs" % (self.om_width, self.widths[0]))
+        if self.om_width and self.widths[0] > MAX_WIDE:
+            raise NotImplementedError("SarlTrainer: T + om_width = %d columns, the gradient takes up to %d" % (self.widths[0], MAX_WIDE))
         self.native = (self.device.type == "cuda") if native is None else bool(native)
         if self.native and self.device.type != "cuda":
             raise NotImplementedError("SarlTrainer(native=True) needs a HIP device: the kernel has no CPU form")
@@ -215,7 +232,7 @@ class SarlTrainer(object):
         self.net = None
         if self.native:
             idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.net = SarlNet(sd, idx)
+            self.net = SarlNet(sd, idx, om_width=self.om_width or None)
 
     def set_learning_rate(self, lr):
         """Trainer.set_optimizer (trainer.py:24-45): a new optimizer at the stage's learning rate."""
@@ -329,7 +346,7 @@ class SarlTrainer(object):
 def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,
                       rl_learning_rate=0.001, train_iterations=0, steps_per_iteration=1, train_batches=100, batch_size=100,
                       capacity=100000, epsilon_start=0.5, epsilon_end=0.1, epsilon_decay=4000, target_update_interval=50,
-                      generator=None, log=None, output_dir=None, checkpoint_interval=0, rank=0, after_il=None):
+                      generator=None, log=None, output_dir=None, checkpoint_interval=0, rank=0, after_il=None, om=None):
     """The schedule of cadrl_train.run_cadrl_training (rl/train.py:99-260) for SARL on one rank's env slice: imitation
     learning with the robot on ORCA, then `train_iterations` rounds of [epsilon-greedy rollout with DeviceSarlPolicy ->
     `train_batches` optimizer steps on DeviceReplay samples -> the deciding network's tensors and matrix-core blocks
@@ -337,19 +354,24 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     env: BatchedEnv with auto-reset semantics (a scene pool) on the trainer's HIP device.  output_dir: `il_model.pth`
     after imitation learning and `rl_model_<round>.pth` every `checkpoint_interval` rounds and at the end.  A reward,
     value target or loss that is not finite raises FloatingPointError at once, before an optimizer step sees it.
+    om (an occupancy.OccupancySpec): OM-SARL.  The trainer's network takes T + om.width columns (SarlTrainer(om_width=
+    om.width)), the replay and the episode store hold the wide states, collect_il and collect store them (ebc_step_k_om,
+    ebc_observe_wide) and DeviceSarlPolicy(om=om) decides.
     Returns a dict of what happened."""
     import torch.distributed as dist
     from .train import DeviceReplay, EpisodeStore, _multi_rank, all_ranks, collect, collect_il
     dev = trainer.device
     if dev.type != "cuda":
         raise NotImplementedError("run_sarl_training: the rollouts run on a HIP device")
-    if env.T != trainer.widths[0]:
-        raise NotImplementedError("run_sarl_training: the env's rows are %d wide, the network takes %d (occupancy maps are not "
-                                  "part of the schedule)" % (env.T, trainer.widths[0]))
+    W = 0 if om is None else int(om.width)
+    if env.T + W != trainer.widths[0] or W != getattr(trainer, "om_width", 0):
+        raise NotImplementedError("run_sarl_training: the env's rows are %d wide and the occupancy maps %d, the network takes %d "
+                                  "(%d of them maps)" % (env.T, W, trainer.widths[0], getattr(trainer, "om_width", 0)))
     if trainer.native and env.R > trainer.net.grad_max_rows():
         raise NotImplementedError("run_sarl_training: %d rows per state, ebc_sarl_grad takes %d for this network; use native=False"
                                   % (env.R, trainer.net.grad_max_rows()))
-    memory = DeviceReplay(capacity, env.R, env.T, dev)
+    memory = DeviceReplay(capacity, env.R, env.T + W, dev)
+    om_kw = {} if om is None else {"om": om}  # without maps: the calls as they were
     hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}
 
     def save(name):
@@ -363,7 +385,7 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     red_dev = dev if (_multi_rank() and dist.get_backend() == "nccl") else None
     trainer.set_learning_rate(il_learning_rate)
     if il_steps > 0:
-        hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space)
+        hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space, **om_kw)
         if il_epochs > 0 and all_ranks(len(memory) > 0, red_dev):
             _finite(memory.values[:len(memory)], "imitation learning: a value target in the replay memory", env)
             hist["il_loss"] = optimize_epoch(trainer, memory, il_epochs, batch_size, generator)
@@ -377,12 +399,12 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     kw = dict(device=dev, with_global_state=trainer.with_global_state, self_state_dim=trainer.self_state_dim)
     net = SarlValueNet(trainer.state_dict(), **kw)
     target_net = SarlValueNet(trainer.state_dict(), **kw)  # explorer.update_target_model (train.py:195)
-    policy = DeviceSarlPolicy(net, actions, gamma)
+    policy = DeviceSarlPolicy(net, actions, gamma, **om_kw)
     t_max = int(round(env.params.time_limit / env.params.time_step)) + 2
-    store = EpisodeStore(env.E, t_max, env.R, env.T, dev)
+    store = EpisodeStore(env.E, t_max, env.R, env.T + W, dev)
     for it in range(int(train_iterations)):
         eps = epsilon_start + (epsilon_end - epsilon_start) / epsilon_decay * it if it < epsilon_decay else epsilon_end
-        mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator, store=store)
+        mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator, store=store, **om_kw)
         _finite(mean_r, "round %d: the rollout's mean reward" % it, env)
         _finite(memory.values[:len(memory)], "round %d: a value target in the replay memory" % it, env)
         trained = all_ranks(len(memory) > 0, red_dev)

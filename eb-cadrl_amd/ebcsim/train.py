@@ -327,19 +327,28 @@ class DataParallelTrainer(object):
 
 
 def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generator=None,
-            human_policy=_abi.HUMAN_ORCA, store=None, state_transform=None):
+            human_policy=_abi.HUMAN_ORCA, store=None, state_transform=None, om=None):
     """Roll the rank's env slice `steps` decisions forward with an epsilon-greedy SARL policy
     (multi_human_rl.py:31-33, :84-85) and push (state, value target) pairs.  env: BatchedEnv on
     the policy's device with auto-reset; returns the mean reward.  With an EpisodeStore the pairs
     reach the memory as the reference's do: per finished episode, successes and collisions only;
     without one every step's pair goes in at once.  state_transform(rows, n_valid) -> rows, when given, is applied to the
     state that is stored and to the next state the target network values, not to what the policy decides on (LSTM-RL:
-    lstm_train.sort_rows_by_distance); None leaves every byte as it was."""
+    lstm_train.sort_rows_by_distance); None leaves every byte as it was.
+    om (an occupancy.OccupancySpec; the policy decides with the same spec): the state that is stored and the next state
+    the target network values are the wide ones, [R, T + om.width] (multi_human_rl.py:128-149 transform with maps) — one
+    observe_wide_device after the step is both the next state and the following decision's stored state (a terminal
+    env's shows its restart scene there; value_targets discards it).  None changes no byte and no launch."""
     dev = policy.net.device
     E, R, T = env.E, env.R, env.T
-    cur = torch.zeros((E, R, T), dtype=torch.float32, device=dev)
-    outs = env.alloc_step_outputs(("reward", "done", "info", "obs_rotated"))
-    env.observe_device(cur)
+    wide = om is not None
+    cur = torch.zeros((E, R, T + (om.width if wide else 0)), dtype=torch.float32, device=dev)
+    spare = torch.zeros_like(cur) if wide else None
+    outs = env.alloc_step_outputs(("reward", "done", "info") + (() if wide else ("obs_rotated",)))
+    if wide:
+        env.observe_wide_device(cur, om)
+    else:
+        env.observe_device(cur)
     v_pref = uniform_v_pref(env)
     gamma_bar = gamma ** (env.params.time_step * v_pref)
     A = len(policy.actions_np)
@@ -356,7 +365,12 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
                         flags=_abi.FLAG_AUTO_RESET)
         # the returned observation belongs to the scene that was stepped (a terminal env's target is its
         # reward, its restart scene shows up in `cur` below): its row count is the decision's
-        nxt = outs["obs_rotated"] if state_transform is None else state_transform(outs["obs_rotated"], nv_cur)
+        if wide:
+            env.observe_wide_device(spare, om)
+            after = spare
+        else:
+            after = outs["obs_rotated"]
+        nxt = after if state_transform is None else state_transform(after, nv_cur)
         targets = value_targets(outs["reward"], outs["done"], nxt, target_net, gamma_bar, nv_cur)
         kept = cur if state_transform is None else state_transform(cur, nv_cur)
         if store is None:
@@ -366,13 +380,16 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
             store.end(outs["done"], outs["info"], memory)
         total += float(outs["reward"].mean())
         # the next decision's state: the returned observation, or the reset scene after a terminal step
-        env.observe_device(cur)
+        if wide:
+            cur, spare = spare, cur
+        else:
+            env.observe_device(cur)
     env.synchronize()  # surfaces a mailbox fault of any step above (EBC_ERR_DEVICE) instead of training on it
     return total / steps
 
 
 def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HUMAN_ORCA, persistent_sim=True,
-               one_launch=False):
+               one_launch=False, om=None):
     """The imitation-learning stage's rollouts (rl/train.py:124-133, explorer.py:33-92 with
     imitation_learning=True): the robot of every env of the rank's slice on ORCA (ebc_robot_orca ->
     ebc_step, auto-reset) for `steps` steps; the states of every episode that ended inside the window in
@@ -385,7 +402,9 @@ def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HU
     episode sequence equals the reference's serial sequence on the same scenes (tests: il_persistent_* goldens).
     persistent_sim=False: the demonstrator sees every state's own radii (a fresh policy object per step).
     one_launch=True: the window runs as ONE kernel launch (EBC_FLAG_ONE_LAUNCH, ORCA humans only): the same memory,
-    bit for bit."""
+    bit for bit.
+    om (an occupancy.OccupancySpec): the stored states are the wide ones, [R, T + om.width] (ebc_step_k_om; per-step form
+    only: with one_launch the library refuses by name).  None changes no byte and no launch."""
     E, R, T = env.E, env.R, env.T
     env.robot_orca_sim(bool(persistent_sim))
     v_pref = uniform_v_pref(env)
@@ -394,16 +413,21 @@ def collect_il(env, memory, steps, gamma, safety_space=0.0, human_policy=_abi.HU
     # the whole window in ONE call through the C ABI (ebc_step_k): per step the library enqueues the state the
     # policy sees (policy.last_state transformed, explorer.py:43, :162), the robot's ORCA action and the step,
     # every output written at its step index; no host work between the steps
-    keys = ("state_rotated", "reward", "done", "info") + (("n_rows",) if ragged else ())
-    outs = env.alloc_step_k_outputs(steps, keys)
-    env.step_k_device(outs, steps, human_policy=human_policy, robot_policy=_abi.ROBOT_ORCA,
-                      flags=_abi.FLAG_AUTO_RESET | (_abi.FLAG_ONE_LAUNCH if one_launch else 0),
-                      robot_safety_space=safety_space)
-    states, rewards, dones, infos = outs["state_rotated"], outs["reward"], outs["done"], outs["info"]
+    state_key = "state_rotated" if om is None else "state_wide"
+    keys = (state_key, "reward", "done", "info") + (("n_rows",) if ragged else ())
+    outs = env.alloc_step_k_outputs(steps, keys) if om is None else env.alloc_step_k_outputs(steps, keys, om=om)
+    flags = _abi.FLAG_AUTO_RESET | (_abi.FLAG_ONE_LAUNCH if one_launch else 0)
+    if om is None:
+        env.step_k_device(outs, steps, human_policy=human_policy, robot_policy=_abi.ROBOT_ORCA, flags=flags,
+                          robot_safety_space=safety_space)
+    else:
+        env.step_k_device(outs, steps, human_policy=human_policy, robot_policy=_abi.ROBOT_ORCA, flags=flags,
+                          robot_safety_space=safety_space, om=om)
+    states, rewards, dones, infos = outs[state_key], outs["reward"], outs["done"], outs["info"]
     rows = outs["n_rows"] if ragged else None
     values, keep = il_value_targets(rewards, dones, gamma_bar, infos)
     keep = keep.reshape(-1)
-    memory.push(states.reshape(steps * E, R, T)[keep], values.reshape(-1)[keep],
+    memory.push(states.reshape(steps * E, R, states.shape[-1])[keep], values.reshape(-1)[keep],
                 rows.reshape(-1)[keep] if ragged else None)
     env.synchronize()  # a natural sync point: also surfaces a mailbox fault of any step above
     return int(keep.sum()), int(dones.sum())

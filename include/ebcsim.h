@@ -665,6 +665,39 @@ typedef struct EbcOmArgs {
 } EbcOmArgs;
 int ebc_occupancy_rows(int device_id, void *stream, const EbcOmArgs *args);
 
+/* ---- the state OM-SARL stores for training (rl/policy/multi_human_rl.py:128-149 transform = [rotate(state) |
+ * build_occupancy_maps(state.agent_states)], in imitation learning and in RL alike): the env's CURRENT state, read once,
+ * as one kernel (csrc/ebc_om_state.h; a workgroup per env).  In bytes:
+ *   state_wide[e][r][0 .. T)     = ebc_observe's obs_rotated (zeros for rows that do not exist)
+ *   state_wide[e][r][T .. T + W) = ebc_occupancy_rows' om on ebc_observe's ob with ebc_row_counts' counts (0 for rows
+ *                                  that do not exist)
+ *   n_rows[e]                    = ebc_row_counts (may be NULL)
+ * Device pointers.  The spec has ebc_occupancy_rows' limits and its refusals by name (channels outside {1, 2, 3},
+ * cell_num < 1, cell_size not a finite positive number, W > 192, R > 128, T + W > 224: EBC_ERR_UNSUPPORTED); a stream
+ * under capture is refused with EBC_ERR_UNSUPPORTED; before ebc_reset and on a faulted handle EBC_ERR_STATE. */
+typedef struct EbcOmSpec {
+  uint32_t struct_size;
+  int32_t cell_num;        /* [om] cell_num */
+  int32_t channels;        /* [om] om_channel_size */
+  int32_t reserved;
+  double cell_size;        /* [om] cell_size */
+} EbcOmSpec;
+/* state_wide: device float32 [E][R][T + W]; n_rows: device int64 [E], or NULL */
+int ebc_observe_wide(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows);
+
+/* ebc_step_k(handle, args) in its per-step form — the same outputs at the same [k], the same launches — and before
+ * step k also the wide state of the state the policy sees: one enqueue of ebc_observe_wide's kernel per step, no host
+ * work between steps.  What an imitation window (EBC_ROBOT_ORCA) needs to fill OM-SARL's replay.  EBC_FLAG_ONE_LAUNCH is
+ * EBC_ERR_UNSUPPORTED (the window with maps has the per-step form only, the choice ebc_sail_dagger_k made);
+ * state_wide is a device pointer whatever args->location says. */
+typedef struct EbcStepKOm {
+  uint32_t struct_size;
+  int32_t reserved;
+  EbcOmSpec spec;
+  float *state_wide;       /* device float32 [K][E][R][T + W] */
+} EbcStepKOm;
+int ebc_step_k_om(void *handle, const EbcStepKArgs *args, const EbcStepKOm *om);
+
 /* ---- the SAIL policy (rl/policy/sail.py): one small network from the robot's state and the world-frame states of
  * exactly adult_num others straight to a continuous action, no look-ahead and no action space; one kernel per batch of
  * decisions.  The arithmetic is csrc/ebc_sail_rule.h (one definition for the kernel and for the host build
@@ -927,6 +960,12 @@ typedef struct EbcSarlGradArgs {
   float *attention;             /* device float32 [B][R], or NULL */
 } EbcSarlGradArgs;
 int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_id, void **net_out);
+/* The network of OM-SARL (multi_human_rl.py:151-154: input_dim = T + cell_num^2 * om_channel_size): input_dim stays the
+ * rotated width T (1 .. 64, self_state_dim <= T), om_width = W is 0 .. 192 and T + W <= 224, else EBC_ERR_UNSUPPORTED by
+ * name.  mlp1's first layer has T + W inputs (weight[0] is [out][T + W]); the packed image follows the rule above with
+ * that K; ebc_sarl_grad on such a network takes args.T == T + W and ebc_sarl_net_grad_max_rows answers for the wide row.
+ * om_width = 0 is ebc_sarl_net_create: the same network, packed image and bytes. */
+int ebc_sarl_net_create_om(const EbcSarlNetWeights *weights, int om_width, int device_id, void **net_out);
 int ebc_sarl_net_destroy(void *net);
 int ebc_sarl_net_packed_floats(void *net, int64_t *floats_out);
 int ebc_sarl_net_get_packed(void *net, void *stream, float *dst_dev);

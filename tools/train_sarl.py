@@ -16,7 +16,12 @@ target network refreshed every 10, where run_sarl_training and the reference's t
 10 000 rounds; pass those for a run of that length.
 
 A reward, value target or loss that is not finite stops the run with an error before an optimizer step sees it; --out is
-written only by a run that ended.  Occupancy maps are not part of the schedule."""
+written only by a run that ended.
+
+OM-SARL: a policy config with [sarl] with_om = true (eb-cadrl_amd/configs/policy_om.config) trains the network whose mlp1
+takes T + cell_num^2 * om_channel_size columns, on the wide states the device builds (ebc_observe_wide, ebc_step_k_om),
+and scores it with the OM policy; the saved file's keys and shapes are the reference's ValueNetwork built with that
+input_dim."""
 import argparse
 import configparser
 import json
@@ -64,6 +69,7 @@ def main():
     import torch
     from ebcsim import _abi, actions as ebc_actions, config as ebc_config, scene as ebc_scene
     from ebcsim.batched import BatchedEnv
+    from ebcsim.occupancy import OccupancySpec
     from ebcsim.sarl import DeviceSarlPolicy, SarlValueNet
     from ebcsim.sarl_train import SarlTrainer, run_sarl_training
     from ebcsim.train import SarlModule, evaluate
@@ -75,6 +81,8 @@ def main():
     dims = {k: [int(x) for x in pol.get("sarl", k, fallback=d).split(",")] for k, d in (
         ("mlp1_dims", "150, 100"), ("mlp2_dims", "100, 50"), ("attention_dims", "100, 100, 1"), ("mlp3_dims", "150, 100, 100, 1"))}
     with_global_state = pol.getboolean("sarl", "with_global_state", fallback=True)
+    om = OccupancySpec.from_config(pol)
+    om_kw = {} if om is None else {"om": om}
     sc = ebc_scene.SceneConfig.from_config(cfg)
     gen, test = ebc_scene.gen_struct(sc, "train"), ebc_scene.gen_struct(sc, "test")
     S = ebc_scene.max_static_rows(sc)
@@ -87,7 +95,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
-        policy = DeviceSarlPolicy(SarlValueNet.load(path, device="cuda:0", with_global_state=with_global_state), space, gamma)
+        policy = DeviceSarlPolicy(SarlValueNet.load(path, device="cuda:0", with_global_state=with_global_state), space, gamma, **om_kw)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
         env.close()
@@ -106,10 +114,11 @@ def main():
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 8 * E)
     torch.manual_seed(args.seed)
-    start = SarlModule(env.T, dims["mlp1_dims"], dims["mlp2_dims"], dims["mlp3_dims"], dims["attention_dims"], with_global_state=with_global_state)
+    start = SarlModule(env.T + (om.width if om else 0), dims["mlp1_dims"], dims["mlp2_dims"], dims["mlp3_dims"], dims["attention_dims"], with_global_state=with_global_state)
     if args.weights:
         start.load_state_dict(torch.load(args.weights, map_location="cpu"), strict=True)
-    trainer = SarlTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd)
+    trainer = SarlTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd,
+                          om_width=om.width if om else 0)
     g = torch.Generator(device="cuda:0").manual_seed(args.seed)
     common = dict(il_learning_rate=args.il_lr, il_safety_space=args.safety_space, rl_learning_rate=args.rl_lr, steps_per_iteration=args.steps_per_iteration,
                   train_batches=args.train_batches, batch_size=args.batch_size, capacity=args.capacity, epsilon_start=args.epsilon_start,
@@ -121,13 +130,13 @@ def main():
     def after_il(h):
         torch.cuda.synchronize()
         mark["il_s"] = time.perf_counter() - t0
-        print("imitation learning (%s): %d envs x %d steps, %d states of %d episodes, %d epochs in %.2f s"
-              % ("torch autograd" if args.autograd else "ebc_sarl_grad", E, args.il_steps, h["il_stored"], h["il_episodes"], args.il_epochs, mark["il_s"]))
+        print("imitation learning (%s%s): %d envs x %d steps, %d states of %d episodes, %d epochs in %.2f s"
+              % ("torch autograd" if args.autograd else "ebc_sarl_grad", "" if om is None else ", rows %d + %d wide" % (env.T, om.width), E, args.il_steps, h["il_stored"], h["il_episodes"], args.il_epochs, mark["il_s"]))
         mark["after_il"] = evaluate_saved(os.path.join(out_dir, "il_model.pth"), "after imitation learning")
         mark["t_rl"] = time.perf_counter()
 
     hist = run_sarl_training(env, trainer, space, gamma, il_steps=args.il_steps, il_epochs=args.il_epochs, train_iterations=args.iterations,
-                             after_il=after_il, **common)
+                             after_il=after_il, **om_kw, **common)
     torch.cuda.synchronize()
     rl_s = time.perf_counter() - mark["t_rl"]
     print("RL: %d rounds of %d decisions per env and %d optimizer steps of batch %d in %.2f s; loss first %.3e, last %.3e; replay memory %d"
