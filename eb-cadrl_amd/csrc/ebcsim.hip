@@ -943,25 +943,33 @@ int check_om_spec(const Handle *h, const EbcOmSpec *spec, const char *what) {
   return EBC_OK;
 }
 
-// observe_wide_kernel for every env (a checked spec) -> d_wide [E][R][T + W], d_rows [E] or nullptr, on the handle's stream
-int launch_observe_wide(Handle *h, const EbcOmSpec &spec, float *d_wide, long long *d_rows) {
-  if (h->s.E == 0) return EBC_OK;
-  const int R = h->s.N + h->s.S;
-  const size_t lds = ebc::om_state_lds_bytes(R, (int)om_width(spec), h->T);  // <= 110.5 KB at R = 128, W = 192, T = 17
-  const void *fn = h->T == 17 ? (const void *)ebc::observe_wide_kernel<17> : (const void *)ebc::observe_wide_kernel<13>;
-  static size_t raised_dev[2][64] = {{0}};  // more than the 64 KB a launch gets by default; a function attribute is per device
-  size_t &raised = raised_dev[h->T == 17][h->device & 63];
-  if (lds > 65536 && lds > raised) {
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+// observe_wide_kernel — `sorted`: observe_wide_sorted_kernel — for every env (a checked spec) -> d_wide [E][R][T + W],
+// d_rows [E] or nullptr, on the handle's stream
+template <typename Kernel>
+int launch_observe_wide_as(Handle *h, Kernel kernel, size_t lds, size_t &raised, const EbcOmSpec &spec, float *d_wide, long long *d_rows) {
+  if (lds > 65536 && lds > raised) {  // more than the 64 KB a launch gets by default; a function attribute is per device
+    HIP_TRY(hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     raised = lds;
   }
   const ebc::OmStateSpec sp = {spec.cell_size, spec.cell_num, spec.channels};
-  if (h->T == 17)
-    hipLaunchKernelGGL((ebc::observe_wide_kernel<17>), dim3((unsigned)h->s.E), dim3(EBC_OMS_THREADS), lds, h->stream, h->p, h->s, sp, d_wide, d_rows);
-  else
-    hipLaunchKernelGGL((ebc::observe_wide_kernel<13>), dim3((unsigned)h->s.E), dim3(EBC_OMS_THREADS), lds, h->stream, h->p, h->s, sp, d_wide, d_rows);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)h->s.E), dim3(EBC_OMS_THREADS), lds, h->stream, h->p, h->s, sp, d_wide, d_rows);
   HIP_TRY(hipGetLastError());
   return EBC_OK;
+}
+
+int launch_observe_wide(Handle *h, const EbcOmSpec &spec, float *d_wide, long long *d_rows, bool sorted = false) {
+  if (h->s.E == 0) return EBC_OK;
+  const int R = h->s.N + h->s.S, W = (int)om_width(spec);
+  static size_t raised_dev[2][2][64] = {{{0}}};
+  size_t &raised = raised_dev[sorted][h->T == 17][h->device & 63];
+  if (sorted) {
+    const size_t lds = ebc::om_state_sorted_lds_bytes(R, W, h->T);  // <= 111 KB at R = 128, W = 192, T = 17
+    return h->T == 17 ? launch_observe_wide_as(h, ebc::observe_wide_sorted_kernel<17>, lds, raised, spec, d_wide, d_rows)
+                      : launch_observe_wide_as(h, ebc::observe_wide_sorted_kernel<13>, lds, raised, spec, d_wide, d_rows);
+  }
+  const size_t lds = ebc::om_state_lds_bytes(R, W, h->T);  // <= 110.5 KB at R = 128, W = 192, T = 17
+  return h->T == 17 ? launch_observe_wide_as(h, ebc::observe_wide_kernel<17>, lds, raised, spec, d_wide, d_rows)
+                    : launch_observe_wide_as(h, ebc::observe_wide_kernel<13>, lds, raised, spec, d_wide, d_rows);
 }
 
 // EBC_FLAG_ONE_LAUNCH: rollout_kernel (ebc_rollout.h), a workgroup per group of envs for all K steps.
@@ -1586,19 +1594,29 @@ int ebc_row_counts(void *handle, int location, long long *n_rows) {
   return EBC_OK;
 }
 
-int ebc_observe_wide(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows) {
+// ebc_observe_wide and ebc_observe_wide_sorted: the same checks, refusals and states, under the entry's own name
+static int observe_wide_entry(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows, bool sorted) {
+  const std::string who = sorted ? "ebc_observe_wide_sorted" : "ebc_observe_wide";
   if (!spec || spec->struct_size != sizeof(EbcOmSpec)) return fail(EBC_ERR_INVALID, "EbcOmSpec.struct_size");
   Handle *h;
   int rc = check_handle(handle, &h);
   if (rc) return rc;
-  if (!h->has_reset) return fail(EBC_ERR_STATE, "ebc_observe_wide before ebc_reset");
-  if (h->faulted) return fail(EBC_ERR_STATE, "ebc_observe_wide: the handle reported a mailbox fault; ebc_reset re-arms it");
-  if (!state_wide) return fail(EBC_ERR_INVALID, "ebc_observe_wide: state_wide is NULL");
-  if ((rc = check_om_spec(h, spec, "ebc_observe_wide")) != EBC_OK) return rc;
+  if (!h->has_reset) return fail(EBC_ERR_STATE, who + " before ebc_reset");
+  if (h->faulted) return fail(EBC_ERR_STATE, who + ": the handle reported a mailbox fault; ebc_reset re-arms it");
+  if (!state_wide) return fail(EBC_ERR_INVALID, who + ": state_wide is NULL");
+  if ((rc = check_om_spec(h, spec, who.c_str())) != EBC_OK) return rc;
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
   if (hipStreamIsCapturing(h->stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
-    return fail(EBC_ERR_UNSUPPORTED, "ebc_observe_wide: the stream is being captured into a HIP graph; the maps must be launched, not replayed");
-  return launch_observe_wide(h, *spec, state_wide, n_rows);
+    return fail(EBC_ERR_UNSUPPORTED, who + ": the stream is being captured into a HIP graph; the maps must be launched, not replayed");
+  return launch_observe_wide(h, *spec, state_wide, n_rows, sorted);
+}
+
+int ebc_observe_wide(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows) {
+  return observe_wide_entry(handle, spec, state_wide, n_rows, false);
+}
+
+int ebc_observe_wide_sorted(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows) {
+  return observe_wide_entry(handle, spec, state_wide, n_rows, true);
 }
 
 int ebc_il_targets(void *stream, const double *reward, const uint8_t *done, const uint8_t *info, int K, int E,

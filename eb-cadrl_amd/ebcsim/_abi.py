@@ -209,7 +209,8 @@ class EbcOmArgs(C.Structure):
 
 
 class EbcOmSpec(C.Structure):
-    """include/ebcsim.h: [om] cell_num / om_channel_size / cell_size, what ebc_observe_wide and ebc_step_k_om build the maps with."""
+    """include/ebcsim.h: [om] cell_num / om_channel_size / cell_size, what ebc_observe_wide, ebc_observe_wide_sorted and
+    ebc_step_k_om build the maps with."""
     _fields_ = [("struct_size", C.c_uint32), ("cell_num", C.c_int32), ("channels", C.c_int32), ("reserved", C.c_int32),
                 ("cell_size", C.c_double)]
 

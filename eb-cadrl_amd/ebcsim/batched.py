@@ -320,6 +320,17 @@ class BatchedEnv:
         s = _abi.om_spec(spec)
         _capi.check(self._L.ebc_observe_wide(self._h, C.addressof(s), out.data_ptr(), None if n_rows is None else n_rows.data_ptr()))
 
+    def observe_wide_sorted_device(self, out, spec, n_rows=None):
+        """The state OM-LSTM stores in RL (lstm_rl.py:117-123, then multi_human_rl.py:128-149 transform): observe_wide_device
+        with each env's existing rows in LstmRL.predict's order (lstm_train.sort_rows_by_distance's) and the maps built from
+        the rows in THAT order, one kernel (ebc_observe_wide_sorted).  The arguments are observe_wide_device's."""
+        if out.dtype.itemsize != 4 or out.numel() != self.E * self.R * (self.T + spec.width) or not out.is_contiguous():
+            raise ValueError("out must be a contiguous float32 [E, R, %d] tensor" % (self.T + spec.width))
+        if n_rows is not None and (n_rows.dtype.itemsize != 8 or n_rows.numel() != self.E or not n_rows.is_contiguous()):
+            raise ValueError("n_rows must be a contiguous int64 [E] tensor")
+        s = _abi.om_spec(spec)
+        _capi.check(self._L.ebc_observe_wide_sorted(self._h, C.addressof(s), out.data_ptr(), None if n_rows is None else n_rows.data_ptr()))
+
     def robot_orca(self, safety_space=0.0):
         """ORCA.predict with the robot as the agent, every env (ebc_robot_orca) -> actions [E, 2]:
         the imitation-learning demonstrator (rl/train.py:99-143)."""

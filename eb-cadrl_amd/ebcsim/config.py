@@ -27,7 +27,7 @@ _HUMAN_ORCA = {"safety_space": "orca_safety_space", "neighbor_dist": "orca_neigh
 
 def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="sarl", human_orca=None):
     """env_cfg / policy_cfg: RawConfigParser objects in the reference's schema.  policy: the robot's policy;
-    "lstm_rl", "cadrl" and "sail" never read with_agent_type (rl/policy/lstm_rl.py:79-100, rl/policy/cadrl.py:66-82,
+    "lstm_rl", "om_lstm_rl", "cadrl" and "sail" never read with_agent_type (rl/policy/lstm_rl.py:79-100, rl/policy/cadrl.py:66-82,
     rl/policy/sail.py:109-112), so their rows are 13 wide whatever [sarl] says.  human_orca: attributes of the humans'
     ORCA policy objects by the reference's names (safety_space, neighbor_dist, max_neighbors, time_horizon), which no
     config file sets (simulator/policy/orca.py:63-80): the defaults are that constructor's."""
@@ -60,7 +60,7 @@ def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="
             kin = policy_cfg.get("action_space", "kinematics")
         if policy_cfg.has_option("sarl", "with_agent_type"):
             p.with_agent_type = int(policy_cfg.getboolean("sarl", "with_agent_type"))
-        if policy in ("lstm_rl", "cadrl", "sail"):
+        if policy in ("lstm_rl", "om_lstm_rl", "cadrl", "sail"):
             p.with_agent_type = 0
     kin = kin or "holonomic"
     # agents treat every non-"holonomic" string as rotational (agent.py:166-169);
@@ -72,10 +72,13 @@ def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="
 
 def occupancy_from_config(policy_cfg, policy="sarl"):
     """The occupancy maps a policy config asks for: an ebcsim.occupancy.OccupancySpec for policy "sarl" with [sarl]
-    with_om = true (OM-SARL, multi_human_rl.py:151-227), else None.  EbcParams has no field for them: the maps are built
-    from the look-ahead's next_ob by ebc_occupancy_rows, outside the env handle.  "lstm_rl" with with_om is refused by its
-    policy object, and the reference's CADRL.configure never reads with_om."""
+    with_om = true (OM-SARL, multi_human_rl.py:151-227) and for policy "om_lstm_rl" with [lstm_rl] with_om = true
+    (OM-LSTM), else None.  EbcParams has no field for them: the maps are built from the look-ahead's next_ob by
+    ebc_occupancy_rows, outside the env handle.  "lstm_rl" with with_om is refused by its policy object, and the
+    reference's CADRL.configure never reads with_om."""
     from .occupancy import OccupancySpec
+    if policy == "om_lstm_rl":
+        return OccupancySpec.from_config(policy_cfg, section="lstm_rl")
     return OccupancySpec.from_config(policy_cfg) if policy == "sarl" else None
 
 

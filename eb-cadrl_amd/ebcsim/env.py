@@ -346,17 +346,18 @@ def make(env_id=ENV_ID, **kwargs):
 def _policy_factory():
     """rl/policy/policy_factory.py:8-12 extends the simulator's table with the learnt policies.  When the
     caller's `rl` package is importable its table is used as it is (its SARL then drives this env through
-    `onestep_lookahead`); otherwise `sarl`, `lstm_rl` and `cadrl` are this package's own policies (one sweep + one
+    `onestep_lookahead`); otherwise `sarl`, `lstm_rl`, `om_lstm_rl` and `cadrl` are this package's own policies (one sweep + one
     batched forward) and `sail` its own SAIL (one network forward, no sweep)."""
     try:
         from rl.policy.policy_factory import policy_factory as table
         return table
     except ImportError:
         from .policy import policy_factory
-        from .rl_policy import CADRL, SAIL, SARL, LstmRL
+        from .rl_policy import CADRL, SAIL, SARL, LstmRL, OmLstmRL
         table = dict(policy_factory)
         table["sarl"] = SARL
         table["lstm_rl"] = LstmRL
+        table["om_lstm_rl"] = OmLstmRL
         table["cadrl"] = CADRL
         table["sail"] = SAIL
         return table

@@ -9,7 +9,8 @@ beyond it never enter.
 LstmModule is the torch module (state_dict keys and shapes of the reference's networks: their .pth files load as they
 are).  LstmValueNet is the inference view with the surface DeviceSarlPolicy and evaluate() drive: on a HIP device every
 value is float32 from the library — the two-layer blocks' float32 form (ebc_mlp2_forward_f32) around the LSTM scan
-kernel (ebc_lstm_forward), which also writes the joint vector; on the CPU it is torch."""
+kernel (ebc_lstm_forward), which also writes the joint vector; on the CPU it is torch.  OM-LSTM (with_om = true) is the
+same two networks on rows 13 + W wide, up to the kernels' 64 columns."""
 import torch
 
 from . import _abi
@@ -171,12 +172,22 @@ class LstmValueNet(object):
     def load(cls, path, device="cpu", **kw):
         return cls(torch.load(path, map_location="cpu"), device=device, **kw)
 
+    MAX_INPUT_DIM = 64  # csrc/ebc_lstm_cell.h EBC_LSTM_MAX_DIM (the scan), csrc/ebc_lstm_grad_rule.h EBC_LSTM_GRAD_MAX_IN (training)
+
+    def check_native_width(self):
+        """The row width the library's LSTM path takes: 13 (LSTM-RL), 13 + W up to 64 (OM-LSTM: 61 at the reference's [om]),
+        with mlp1 and without (ValueNetwork1: the cell's own input is that wide).  A wider network is refused by name."""
+        if self.input_dim > self.MAX_INPUT_DIM:
+            raise NotImplementedError("LstmValueNet on a HIP device: rows %d wide, the LSTM kernels take rows up to %d wide "
+                                      "(EBC_LSTM_MAX_DIM, EBC_LSTM_GRAD_MAX_IN)" % (self.input_dim, self.MAX_INPUT_DIM))
+
     def _native_blocks(self):
         """(mlp1 as two blocks or (), the LSTM, mlp as two blocks) on a HIP device; None on the CPU.  A network the
         blocks do not take (other layer counts, widths past the kernels' limits) is an error, never a torch path."""
         if self.device.type != "cuda":
             return None
         if self._native is None:
+            self.check_native_width()
             m = self.module
             idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
             mlp, mlp1 = _stack(m.mlp), (_stack(m.mlp1) if m.with_interaction_module else [])
@@ -214,8 +225,8 @@ class LstmValueNet(object):
         """rows [B, R, T] float32; n_valid [B] or None = all -> values [B] float32."""
         B, R, T = rows.shape
         if T != self.input_dim:
-            raise ValueError("LstmValueNet: rows are %d wide, the network takes %d (LSTM-RL runs with with_agent_type = 0)"
-                             % (T, self.input_dim))
+            raise ValueError("LstmValueNet: rows are %d wide, the network takes %d (LSTM-RL runs with with_agent_type = 0; "
+                             "OM-LSTM's rows carry their maps)" % (T, self.input_dim))
         with torch.no_grad():
             nat = self._native_blocks() if rows.is_cuda else None
             if nat is None:

@@ -15,7 +15,12 @@ run_lstm_training is the schedule of rl/train.py:99-260 with this trainer in the
 over LstmValueNet deciding.  It differs from run_sarl_training in what the reference itself does differently: in RL mode
 the replay holds the policy's last_state, whose rows LstmRL.predict has sorted by decreasing distance to the robot
 (lstm_rl.py:117-123, explorer.py:44), and the next state the target network values is sorted the same way; the imitation
-states stay in the env's order (explorer.py:161).  OM-LSTM is not part of it."""
+states stay in the env's order (explorer.py:161).
+
+OM-LSTM ([lstm_rl] with_om = true) is the same trainer and schedule on rows T + W wide (13 + 4 * 4 * 3 = 61 at the
+reference's settings; the kernels take up to 64): run_lstm_training(..., om=spec) fills the replay with wide states — the
+imitation window's from ebc_step_k_om in the env's order, the RL rounds' from ebc_observe_wide_sorted, whose maps are built
+from the rows in the sorted order as the reference's transform(state) builds them — and DeviceSarlPolicy(om=spec) decides."""
 import collections
 import ctypes as C
 import os
@@ -118,17 +123,23 @@ def module_of(sd):
     return LstmModule.from_state_dict({k: v.detach() for k, v in sd.items()}, S)
 
 
-def sort_rows_by_distance(rows, n_valid=None):
-    """LstmRL.predict's order (lstm_rl.py:117-123: sorted by the distance to the robot, reverse=True) on rotated rows, on
-    their device: each state's existing rows [0, n_valid) in a stable descending order of their own distance column
-    (index 11, `da`), the padding rows left where they are, at the end.  rows [B, R, T]; n_valid [B] or None = all R."""
-    B, R, _ = rows.shape
+def distance_order(rows, n_valid=None):
+    """LstmRL.predict's order (lstm_rl.py:117-123: sorted by the distance to the robot, reverse=True) of rotated rows, on
+    their device: for each state the indices of its existing rows [0, n_valid) in a stable descending order of their own
+    distance column (index 11, `da`), then the padding rows where they are, at the end.  rows [B, R, >= 12] -> int64 [B, R];
+    n_valid [B] or None = all R."""
+    R = rows.shape[1]
     key = -rows[:, :, DISTANCE_COLUMN]
     last = torch.full_like(key, float("inf"))
     key = torch.where(key != key, last, key)  # a NaN distance sorts behind every number, as +inf does: a stable sort then
     if n_valid is not None:                   # keeps the padding rows (+inf too, at the higher indices) behind every row
         key = torch.where(torch.arange(R, device=rows.device)[None, :] < n_valid.to(rows.device)[:, None], key, last)
-    order = torch.sort(key, dim=1, stable=True).indices
+    return torch.sort(key, dim=1, stable=True).indices
+
+
+def sort_rows_by_distance(rows, n_valid=None):
+    """The rows of each state in distance_order: rows [B, R, T]; n_valid [B] or None = all R."""
+    order = distance_order(rows, n_valid)
     return torch.gather(rows, 1, order[:, :, None].expand_as(rows))
 
 
@@ -338,7 +349,7 @@ class LstmTrainer(object):
 def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,
                       rl_learning_rate=0.001, train_iterations=0, steps_per_iteration=1, train_batches=100, batch_size=100,
                       capacity=100000, epsilon_start=0.5, epsilon_end=0.1, epsilon_decay=4000, target_update_interval=50,
-                      generator=None, log=None, output_dir=None, checkpoint_interval=0, rank=0, after_il=None):
+                      generator=None, log=None, output_dir=None, checkpoint_interval=0, rank=0, after_il=None, om=None):
     """The schedule of sarl_train.run_sarl_training (rl/train.py:99-260) for LSTM-RL on one rank's env slice: imitation
     learning with the robot on ORCA (its states in the env's order, explorer.py:161), then `train_iterations` rounds of
     [epsilon-greedy rollout with DeviceSarlPolicy over LstmValueNet, the stored state and the next state the target network
@@ -347,19 +358,27 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     target network refreshed every `target_update_interval` rounds.  env: BatchedEnv with auto-reset semantics (a scene
     pool) on the trainer's HIP device, rows 13 wide.  output_dir: `il_model.pth` after imitation learning and
     `rl_model_<round>.pth` every `checkpoint_interval` rounds and at the end.  A reward, value target or loss that is not
-    finite raises FloatingPointError at once, before an optimizer step sees it.  Returns a dict of what happened."""
+    finite raises FloatingPointError at once, before an optimizer step sees it.  Returns a dict of what happened.
+    om (an occupancy.OccupancySpec): OM-LSTM.  The network's rows are env.T + om.width wide; the imitation states are
+    collect_il(om=om)'s (the env's order with maps), the RL rounds' stored and next states are
+    collect(om=om, sorted_rows=True)'s (one observe_wide_sorted_device after the step is both) and DeviceSarlPolicy(om=om)
+    decides.  None changes no byte and no launch."""
     import torch.distributed as dist
     from .train import DeviceReplay, EpisodeStore, _multi_rank, all_ranks, collect, collect_il
     dev = trainer.device
     if dev.type != "cuda":
         raise NotImplementedError("run_lstm_training: the rollouts run on a HIP device")
-    if env.T != trainer.widths[0]:
+    width = env.T + (om.width if om is not None else 0)
+    if width != trainer.widths[0]:
+        if om is not None:
+            raise NotImplementedError("run_lstm_training: the env's rows are %d wide and the maps add %d, the network takes %d"
+                                      % (env.T, om.width, trainer.widths[0]))
         raise NotImplementedError("run_lstm_training: the env's rows are %d wide, the network takes %d (LSTM-RL runs with "
-                                  "with_agent_type = 0 and without occupancy maps)" % (env.T, trainer.widths[0]))
+                                  "with_agent_type = 0; OM-LSTM needs om=)" % (env.T, trainer.widths[0]))
     if trainer.native and env.R > trainer.net.grad_max_rows():
         raise NotImplementedError("run_lstm_training: %d rows per state, ebc_lstm_grad takes %d for this network; use native=False"
                                   % (env.R, trainer.net.grad_max_rows()))
-    memory = DeviceReplay(capacity, env.R, env.T, dev)
+    memory = DeviceReplay(capacity, env.R, width, dev)
     hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}
 
     def save(name):
@@ -373,7 +392,10 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     red_dev = dev if (_multi_rank() and dist.get_backend() == "nccl") else None
     trainer.set_learning_rate(il_learning_rate)
     if il_steps > 0:
-        hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space)
+        if om is None:
+            hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space)
+        else:
+            hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space, om=om)
         if il_epochs > 0 and all_ranks(len(memory) > 0, red_dev):
             _finite(memory.values[:len(memory)], "imitation learning: a value target in the replay memory", env)
             hist["il_loss"] = optimize_epoch(trainer, memory, il_epochs, batch_size, generator)
@@ -386,13 +408,17 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     trainer.set_learning_rate(rl_learning_rate)
     net = LstmValueNet(trainer.state_dict(), device=dev, self_state_dim=trainer.self_state_dim)
     target_net = LstmValueNet(trainer.state_dict(), device=dev, self_state_dim=trainer.self_state_dim)  # explorer.update_target_model
-    policy = DeviceSarlPolicy(net, actions, gamma)
+    policy = DeviceSarlPolicy(net, actions, gamma) if om is None else DeviceSarlPolicy(net, actions, gamma, om=om)
     t_max = int(round(env.params.time_limit / env.params.time_step)) + 2
-    store = EpisodeStore(env.E, t_max, env.R, env.T, dev)
+    store = EpisodeStore(env.E, t_max, env.R, width, dev)
     for it in range(int(train_iterations)):
         eps = epsilon_start + (epsilon_end - epsilon_start) / epsilon_decay * it if it < epsilon_decay else epsilon_end
-        mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator, store=store,
-                         state_transform=sort_rows_by_distance)
+        if om is None:
+            mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator,
+                             store=store, state_transform=sort_rows_by_distance)
+        else:
+            mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator,
+                             store=store, om=om, sorted_rows=True)
         _finite(mean_r, "round %d: the rollout's mean reward" % it, env)
         _finite(memory.values[:len(memory)], "round %d: a value target in the replay memory" % it, env)
         trained = all_ranks(len(memory) > 0, red_dev)

@@ -160,6 +160,51 @@ def observe_wide_composed(env, spec, out=None, n_rows=None):
     return wide
 
 
+DISTANCE_COLUMN = 11  # `da` of a rotated row: the sort key of LstmRL.predict's order (lstm_train.DISTANCE_COLUMN)
+
+
+def distance_order(rotated, n_valid=None):
+    """lstm_train.distance_order in numpy: rotated [E, R, >= 12] float32 -> int64 [E, R], each state's existing rows in a
+    stable descending order of their float32 column 11 (a NaN behind every number), the padding rows where they are."""
+    rotated = np.asarray(rotated, dtype=np.float32)
+    E, R = rotated.shape[:2]
+    key = -rotated[:, :, DISTANCE_COLUMN]
+    key = np.where(np.isnan(key), np.float32(np.inf), key)
+    if n_valid is not None:
+        n = np.clip(np.asarray(n_valid, dtype=np.int64), 0, R)
+        key = np.where(np.arange(R)[None, :] < n[:, None], key, np.float32(np.inf))
+    return np.argsort(key, axis=1, kind="stable").astype(np.int64)
+
+
+def wide_state_sorted(rotated, ob, n_valid, spec):
+    """The state OM-LSTM stores in RL: LstmRL.predict sorts the agents by decreasing distance (lstm_rl.py:117-123) and
+    transform builds the maps from the SORTED list (multi_human_rl.py:142-146), so a cell's sums walk its occupants in
+    that order.  rotated [E, R, T] float32, ob [E, R, >= 4] float64, n_valid [E] or None -> [E, R, T + W] float32:
+    both permuted by `distance_order`, then `wide_state`.  The CPU path, and the checker of ebc_observe_wide_sorted."""
+    rotated = np.asarray(rotated, dtype=np.float32)
+    ob = np.asarray(ob, dtype=np.float64)
+    order = distance_order(rotated, n_valid)[:, :, None]
+    return wide_state(np.take_along_axis(rotated, order, axis=1), np.take_along_axis(ob, order, axis=1), n_valid, spec)
+
+
+def observe_wide_sorted_composed(env, spec, n_rows=None):
+    """What BatchedEnv.observe_wide_sorted_device gives, from the calls it replaces: ebc_observe twice, ebc_row_counts, a
+    torch sort of the distance column and two gathers, ebc_occupancy_rows on the gathered ob, and a cat.  The composition
+    the kernel is held to byte for byte, and measured against."""
+    import torch
+    from .lstm_train import distance_order as order_of
+    dev = torch.device("cuda", env.device)
+    rot = torch.empty((env.E, env.R, env.T), dtype=torch.float32, device=dev)
+    ob = torch.empty((env.E, env.R, 5), dtype=torch.float64, device=dev)
+    n = torch.empty((env.E,), dtype=torch.int64, device=dev) if n_rows is None else n_rows
+    env.observe_device(rot)
+    env.observe_ob_device(ob)
+    env.row_counts_device(n)
+    order = order_of(rot, n)[:, :, None]
+    om, _ = occupancy_rows_device(torch.gather(ob, 1, order.expand_as(ob)).contiguous(), n, spec)
+    return torch.cat([torch.gather(rot, 1, order.expand_as(rot)), om], dim=2)
+
+
 def occupancy_rows_device(next_ob, n_valid, spec, rows=None, om_out=None, wide_out=None, want_om=True):
     """ebc_occupancy_rows on torch CUDA tensors, enqueued on the current stream: next_ob [E, R, 5] float64, n_valid [E]
     int64 or None, rows [E, A, R, T] float32 or None -> (om [E, R, W] or None, rows_wide [E, A, R, T + W] or None).

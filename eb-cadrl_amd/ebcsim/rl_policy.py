@@ -242,7 +242,8 @@ class LstmRL(Policy):
         dims = lambda key: [int(x) for x in config.get("lstm_rl", key).split(", ")]  # noqa: E731
         self.with_om = config.getboolean("lstm_rl", "with_om")
         if self.with_om:
-            raise NotImplementedError("occupancy maps (OM-LSTM) are outside the accelerated path")
+            raise NotImplementedError("LstmRL is the policy without occupancy maps; [lstm_rl] with_om = true (OM-LSTM) is "
+                                      "OmLstmRL, policy=\"om_lstm_rl\"")
         if not self.query_env:
             raise NotImplementedError("query_env = false ends in the reference's own NotImplementedError "
                                       "(multi_human_rl.py:89-91)")
@@ -297,7 +298,7 @@ class LstmRL(Policy):
             chosen = self.action_space[np.random.choice(len(self.action_space))]
         else:
             sweep = env.lookahead_all(self._action_rows)
-            rows = torch.from_numpy(sweep["rows_rotated"][:, :sweep["n_rows"]]).to(self.device)
+            rows = self._sweep_rows(sweep)
             discount = pow(self.gamma, self.time_step * state.self_state.v_pref)
             reward = torch.from_numpy(np.ascontiguousarray(sweep["reward"], dtype=np.float64)).to(self.device)
             values = self._value_net().action_values(rows[None], reward[None], discount)[0].cpu().numpy()
@@ -306,6 +307,10 @@ class LstmRL(Policy):
         if self.phase == "train":
             self.last_state = self.transform(state, env, order)
         return chosen
+
+    def _sweep_rows(self, sweep):
+        """The rows the network sees for every candidate action, [A, rows, T], in the env's order."""
+        return torch.from_numpy(sweep["rows_rotated"][:, :sweep["n_rows"]]).to(self.device)
 
     def transform(self, state, env=None, order=None):
         """multi_human_rl.py:128-149 of the (sorted) state: with the env, the rows it keeps for its current state
@@ -317,6 +322,65 @@ class LstmRL(Policy):
             return rows.to(self.device)
         rows = torch.Tensor([tuple(state.self_state + other) for other in state.agent_states])
         return self.rotate(rows).to(self.device)
+
+
+class OmLstmRL(LstmRL):
+    """OM-LSTM: rl/policy/lstm_rl.py:72-124 with [lstm_rl] with_om = true.  The occupancy maps of
+    multi_human_rl.py:156-227 are appended to every row the LSTM value network sees: in the decision to the sweep's rows,
+    built once from the sweep's next_ob in the env's order (multi_human_rl.py:62-69); in `last_state` (phase "train") to
+    the rows sorted by decreasing distance, built from the SORTED state (lstm_rl.py:117-123, then transform), so a cell's
+    sums run over its occupants in the sorted order (ebcsim.occupancy.wide_state_sorted)."""
+    MAX_INPUT_DIM = 64  # csrc/ebc_lstm_cell.h EBC_LSTM_MAX_DIM, csrc/ebc_lstm_grad_rule.h EBC_LSTM_GRAD_MAX_IN
+
+    def __init__(self):
+        LstmRL.__init__(self)
+        self.name = "OM-LSTM-RL"
+
+    def configure(self, config):
+        """cadrl.py:72-81 + lstm_rl.py:79-106 with with_om"""
+        from .lstm_rl import LstmModule
+        from .occupancy import OccupancySpec
+        CADRL.set_common_parameters(self, config)
+        dims = lambda key: [int(x) for x in config.get("lstm_rl", key).split(", ")]  # noqa: E731
+        self.with_om = config.getboolean("lstm_rl", "with_om")
+        if not self.with_om:
+            raise ValueError("OmLstmRL is OM-LSTM: [lstm_rl] with_om = false is LstmRL, policy=\"lstm_rl\"")
+        if not self.query_env:
+            raise NotImplementedError("query_env = false ends in the reference's own NotImplementedError "
+                                      "(multi_human_rl.py:89-91)")
+        self._spec = OccupancySpec(self.cell_num, self.cell_size, self.om_channel_size)
+        if self.input_dim() > self.MAX_INPUT_DIM:
+            raise NotImplementedError("OmLstmRL: rows of 13 + %d map columns = %d, the LSTM kernels take rows up to %d wide"
+                                      % (self._spec.width, self.input_dim(), self.MAX_INPUT_DIM))
+        self.with_interaction_module = config.getboolean("lstm_rl", "with_interaction_module")
+        self.model = LstmModule(self.input_dim(), self.self_state_dim, dims("mlp2_dims"),
+                                config.getint("lstm_rl", "global_state_dim"),
+                                dims("mlp1_dims") if self.with_interaction_module else None)
+        self.multiagent_training = config.getboolean("lstm_rl", "multiagent_training")
+
+    def spec(self):
+        """The [om] section as an OccupancySpec."""
+        return self._spec
+
+    om_spec = spec
+
+    def _sweep_rows(self, sweep):
+        from .occupancy import occupancy_maps, widen
+        n = sweep["n_rows"]
+        if n == 1:
+            raise ValueError("need at least one array to concatenate")  # build_occupancy_maps of a one-row state
+        rows = LstmRL._sweep_rows(self, sweep)
+        om = occupancy_maps(sweep["next_ob"][None, :n], None, self._spec)[0]
+        return widen(rows, torch.from_numpy(om).to(self.device))
+
+    def transform(self, state, env=None, order=None):
+        """multi_human_rl.py:128-149 of the (sorted) state with its maps: [rows, 13 + W] float32."""
+        from .occupancy import wide_state_sorted
+        if len(state.agent_states) == 1:
+            raise ValueError("need at least one array to concatenate")
+        rows = LstmRL.transform(self, state, env, order).cpu().numpy()
+        ob = np.array([[a.px, a.py, a.vx, a.vy] for a in state.agent_states], dtype=np.float64)
+        return torch.from_numpy(wide_state_sorted(rows[None], ob[None], None, self._spec)[0]).to(self.device)
 
 
 class CADRL(Policy):

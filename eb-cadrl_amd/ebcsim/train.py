@@ -327,7 +327,7 @@ class DataParallelTrainer(object):
 
 
 def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generator=None,
-            human_policy=_abi.HUMAN_ORCA, store=None, state_transform=None, om=None):
+            human_policy=_abi.HUMAN_ORCA, store=None, state_transform=None, om=None, sorted_rows=False):
     """Roll the rank's env slice `steps` decisions forward with an epsilon-greedy SARL policy
     (multi_human_rl.py:31-33, :84-85) and push (state, value target) pairs.  env: BatchedEnv on
     the policy's device with auto-reset; returns the mean reward.  With an EpisodeStore the pairs
@@ -338,15 +338,24 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
     om (an occupancy.OccupancySpec; the policy decides with the same spec): the state that is stored and the next state
     the target network values are the wide ones, [R, T + om.width] (multi_human_rl.py:128-149 transform with maps) — one
     observe_wide_device after the step is both the next state and the following decision's stored state (a terminal
-    env's shows its restart scene there; value_targets discards it).  None changes no byte and no launch."""
+    env's shows its restart scene there; value_targets discards it).  None changes no byte and no launch.
+    sorted_rows (OM-LSTM; needs om): those wide states come from observe_wide_sorted_device — each env's rows in
+    LstmRL.predict's order (lstm_rl.py:117-123) with the maps built from the rows in that order — and no state_transform
+    runs; the policy still decides on the env's own order.  False changes no byte and no launch."""
+    if sorted_rows and om is None:
+        raise ValueError("collect: sorted_rows needs om (the sorted wide state is ebc_observe_wide_sorted's; without maps "
+                         "pass state_transform=lstm_train.sort_rows_by_distance)")
+    if sorted_rows and state_transform is not None:
+        raise ValueError("collect: sorted_rows and state_transform are two orders for one state; give one")
     dev = policy.net.device
     E, R, T = env.E, env.R, env.T
     wide = om is not None
     cur = torch.zeros((E, R, T + (om.width if wide else 0)), dtype=torch.float32, device=dev)
     spare = torch.zeros_like(cur) if wide else None
     outs = env.alloc_step_outputs(("reward", "done", "info") + (() if wide else ("obs_rotated",)))
+    observe_wide = env.observe_wide_sorted_device if sorted_rows else env.observe_wide_device if wide else None
     if wide:
-        env.observe_wide_device(cur, om)
+        observe_wide(cur, om)
     else:
         env.observe_device(cur)
     v_pref = uniform_v_pref(env)
@@ -366,7 +375,7 @@ def collect(env, policy, target_net, memory, steps, gamma, epsilon=0.0, generato
         # the returned observation belongs to the scene that was stepped (a terminal env's target is its
         # reward, its restart scene shows up in `cur` below): its row count is the decision's
         if wide:
-            env.observe_wide_device(spare, om)
+            observe_wide(spare, om)
             after = spare
         else:
             after = outs["obs_rotated"]

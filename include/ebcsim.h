@@ -685,6 +685,19 @@ typedef struct EbcOmSpec {
 /* state_wide: device float32 [E][R][T + W]; n_rows: device int64 [E], or NULL */
 int ebc_observe_wide(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows);
 
+/* ---- the state OM-LSTM stores in RL (rl/policy/lstm_rl.py:117-123: LstmRL.predict sorts state.agent_states by decreasing
+ * distance to the robot, then transform(state) builds the maps from the SORTED list): ebc_observe_wide with the env's
+ * existing rows in that order, as one kernel (csrc/ebc_om_state.h).  The order: the rows r < n_rows[e] in a stable
+ * descending order of their own rotated float32 column 11 (`da`), a NaN behind every number, several NaNs in the env's
+ * order; slots past the rows stay where they are, zero rows and zero maps.  A cell's sums run over its occupants in the
+ * sorted order, so this is no permutation of ebc_observe_wide's rows.  In bytes: permute ebc_observe's ob and obs_rotated
+ * by that order; then
+ *   state_wide[e][i][0 .. T)     = the permuted obs_rotated
+ *   state_wide[e][i][T .. T + W) = ebc_occupancy_rows' om on the permuted ob with ebc_row_counts' counts
+ *   n_rows[e]                    = ebc_row_counts (may be NULL)
+ * Limits, refusals and states are ebc_observe_wide's. */
+int ebc_observe_wide_sorted(void *handle, const EbcOmSpec *spec, float *state_wide, long long *n_rows);
+
 /* ebc_step_k(handle, args) in its per-step form — the same outputs at the same [k], the same launches — and before
  * step k also the wide state of the state the policy sees: one enqueue of ebc_observe_wide's kernel per step, no host
  * work between steps.  What an imitation window (EBC_ROBOT_ORCA) needs to fill OM-SARL's replay.  EBC_FLAG_ONE_LAUNCH is

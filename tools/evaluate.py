@@ -15,6 +15,10 @@ reference's metrics at the end.
                                          (lstm_rl: the LSTM-RL value network, either of the reference's two; rows 13
                                           wide whatever [sarl] says.  The reference ships no trained LSTM-RL model and
                                           the repository carries none: --weights is required, what rl/train.py saved)
+    python3 tools/evaluate.py --policy lstm_rl --policy-config eb-cadrl_amd/configs/policy_om_lstm.config --weights OM_LSTM_FILE
+                                         (lstm_rl with [lstm_rl] with_om = true in the policy config: OM-LSTM, the
+                                          occupancy maps of its [om] section appended to every row on the device, rows
+                                          13 + 48 = 61 wide; --weights is required, what tools/train_lstm.py saved)
     python3 tools/evaluate.py --policy cadrl --weights CADRL_STATE_DICT_FILE
                                          (cadrl: the CADRL value network, value_network.{0,2,4,6}; the minimum over the
                                           rows and the choice are one kernel.  Rows 13 wide; neither tree ships a
@@ -71,6 +75,7 @@ def main():
     pol_cfg = configparser.RawConfigParser()
     pol_cfg.read(args.policy_config)
     with_om = args.policy == "sarl" and pol_cfg.getboolean("sarl", "with_om", fallback=False)
+    lstm_om = args.policy == "lstm_rl" and pol_cfg.getboolean("lstm_rl", "with_om", fallback=False)
     if with_om and not args.weights:
         ap.error("--policy sarl with [sarl] with_om = true needs --weights: a state_dict file of an OM-SARL network (no tree ships one)")
     import torch
@@ -112,6 +117,8 @@ def main():
         kw = {}
         if with_om:
             kw["om"] = ebc_config.occupancy_from_config(pol, policy=args.policy)
+        if lstm_om:
+            kw["om"] = ebc_config.occupancy_from_config(pol, policy="om_lstm_rl")
         policy = make_policy(net, ebc_actions.build_action_space(v_pref), args.gamma, **kw)
         decide, hp = (lambda e: policy.decide(e)[0]), _abi.HUMAN_CACHED
     elif args.policy == "sail":

@@ -18,8 +18,15 @@ The tool's defaults are a SHORT schedule, not the reference's: 200 RL rounds wit
 target network refreshed every 10, where run_lstm_training and the reference's train.config use 4000 and 50 for runs of
 10 000 rounds; pass those for a run of that length.
 
+OM-LSTM: with [lstm_rl] with_om = true in the policy config (eb-cadrl_amd/configs/policy_om_lstm.config: [om] 4 / 1 / 3) the
+network's rows are 13 + cell_num^2 * om_channel_size = 61 wide and the schedule is run_lstm_training(..., om=spec): the
+imitation window stores the wide states in the env's order (ebc_step_k_om), the RL rounds the sorted wide state — the rows
+by decreasing distance with the maps built from the rows in THAT order, one kernel (ebc_observe_wide_sorted) — and
+DeviceSarlPolicy(om=spec) decides and scores.  The saved file loads into the reference's ValueNetwork1(61, ...) /
+ValueNetwork2(61, ...) with strict=True; tools/evaluate.py --policy lstm_rl --policy-config that config --weights scores it.
+
 A reward, value target or loss that is not finite stops the run with an error before an optimizer step sees it; --out is
-written only by a run that ended.  Occupancy maps (OM-LSTM) are not part of the schedule."""
+written only by a run that ended."""
 import argparse
 import configparser
 import json
@@ -82,8 +89,9 @@ def main():
         ("mlp1_dims", "150, 100, 100, 50"), ("mlp2_dims", "150, 100, 100, 1"))}
     hidden = pol.getint("lstm_rl", "global_state_dim", fallback=50)
     two = pol.getboolean("lstm_rl", "with_interaction_module", fallback=True) if args.interaction_module is None else args.interaction_module == "true"
-    if pol.getboolean("lstm_rl", "with_om", fallback=False):
-        ap.error("[lstm_rl] with_om = true: occupancy maps are not part of the LSTM-RL schedule")
+    from ebcsim.occupancy import OccupancySpec
+    om = OccupancySpec.from_config(pol, section="lstm_rl")  # None without [lstm_rl] with_om = true
+    kw_om = {} if om is None else {"om": om}
     sc = ebc_scene.SceneConfig.from_config(cfg)
     gen, test = ebc_scene.gen_struct(sc, "train"), ebc_scene.gen_struct(sc, "test")
     S = ebc_scene.max_static_rows(sc)
@@ -96,7 +104,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
-        policy = DeviceSarlPolicy(LstmValueNet.load(path, device="cuda:0"), space, gamma)
+        policy = DeviceSarlPolicy(LstmValueNet.load(path, device="cuda:0"), space, gamma, **kw_om)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
         env.close()
@@ -115,7 +123,10 @@ def main():
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 8 * E)
     torch.manual_seed(args.seed)
-    start = LstmModule(env.T, 6, dims["mlp2_dims"], hidden, dims["mlp1_dims"] if two else None)
+    width = env.T + (om.width if om is not None else 0)
+    if width > 64:
+        ap.error("rows of %d + %d map columns = %d: the LSTM kernels take rows up to 64 wide" % (env.T, om.width, width))
+    start = LstmModule(width, 6, dims["mlp2_dims"], hidden, dims["mlp1_dims"] if two else None)
     if args.weights:
         start.load_state_dict(torch.load(args.weights, map_location="cpu"), strict=True)
     trainer = LstmTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd)
@@ -130,13 +141,13 @@ def main():
     def after_il(h):
         torch.cuda.synchronize()
         mark["il_s"] = time.perf_counter() - t0
-        print("imitation learning (%s): %d envs x %d steps, %d states of %d episodes, %d epochs in %.2f s"
-              % ("torch autograd" if args.autograd else "ebc_lstm_grad", E, args.il_steps, h["il_stored"], h["il_episodes"], args.il_epochs, mark["il_s"]))
+        print("imitation learning (%s, rows %d wide): %d envs x %d steps, %d states of %d episodes, %d epochs in %.2f s"
+              % ("torch autograd" if args.autograd else "ebc_lstm_grad", width, E, args.il_steps, h["il_stored"], h["il_episodes"], args.il_epochs, mark["il_s"]))
         mark["after_il"] = evaluate_saved(os.path.join(out_dir, "il_model.pth"), "after imitation learning")
         mark["t_rl"] = time.perf_counter()
 
     hist = run_lstm_training(env, trainer, space, gamma, il_steps=args.il_steps, il_epochs=args.il_epochs, train_iterations=args.iterations,
-                             after_il=after_il, **common)
+                             after_il=after_il, **common, **kw_om)
     torch.cuda.synchronize()
     rl_s = time.perf_counter() - mark["t_rl"]
     print("RL: %d rounds of %d decisions per env and %d optimizer steps of batch %d in %.2f s; loss first %.3e, last %.3e; replay memory %d"
@@ -146,7 +157,7 @@ def main():
     trainer.save(args.out)
     print("saved %s" % args.out)
     after_rl = evaluate_saved(args.out, "after RL")
-    print(json.dumps({"network": "ValueNetwork2" if two else "ValueNetwork1", "envs": E, "il_steps": args.il_steps, "il_epochs": args.il_epochs, "il_stored": hist["il_stored"], "il_loss": hist["il_loss"],
+    print(json.dumps({"network": "ValueNetwork2" if two else "ValueNetwork1", "row_width": width, "envs": E, "il_steps": args.il_steps, "il_epochs": args.il_epochs, "il_stored": hist["il_stored"], "il_loss": hist["il_loss"],
                       "iterations": args.iterations, "rl_loss": [hist["rl_loss"][0], hist["rl_loss"][-1]] if hist["rl_loss"] else [],
                       "il_s": mark["il_s"], "rl_s": rl_s, "cases": args.cases, "after_il": mark["after_il"], "after_rl": after_rl}))
 
