@@ -26,6 +26,14 @@
 // zero vector (h[-1]).  At the reference widths with mlp1 776 floats per slot and 518 per state: 70 KB at R = 5, 133 KB at
 // R = 10, and R <= 12 fits the 160 KB of a gfx950 workgroup; without mlp1 372 per slot and R <= 26.  The weights (349 KB at the
 // reference widths) stay in L2.
+//
+// Passes (lstm_grad_kernel<true>): the chunk's states run SP in {4, 2, 1} at a time, LDS sized for SP states, so that more
+// rows fit (R <= 25 at SP = 2, 52 at SP = 1 at the reference widths with mlp1).  A pass is the whole forward, recurrence
+// and backward of its states (with SP = 1 the gate step's pair is the one state alone); the thread that owns entries of a
+// layer or of the cell's weights owns them in every pass, and from the second pass on it loads them from the chunk's
+// partial (global memory, its own earlier store) and continues the fmaf chain where the pass before left it: the same
+// chain, the same bytes, whatever SP.  The chunk's float64 loss and count carry on in the same way with thread 0.  The
+// first pass always has a state and starts every chain at 0, live or not.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +58,7 @@ struct LstmGradLaunch {
   float grad_scale;
   int B, R;
   int chunk0;                 // the first chunk of this launch
+  int SP;                     // states per pass: 4, 2 or 1 (read by the pass form only)
   ebc_lstmg::GradDims D;
 };
 
@@ -59,24 +68,24 @@ struct LstmGradLds {
   int *LIVE, *N;
   int Tp, Jp, Hp, xis, RS;  // strides: X, J, a unit vector, XI (X's without mlp1), a step's record
 };
-__host__ __device__ inline size_t lstm_grad_lds_floats(const ebc_lstmg::GradDims &D, int R) {
+// the floats of LDS for SP states at a time (SP = the chunk: the whole chunk at once); the arrays that are SP long are
+// padded to 4 floats each, so that what follows them keeps its 16-byte (LOSS: 8-byte) alignment at every SP
+__host__ __device__ inline size_t lstm_grad_lds_floats(const ebc_lstmg::GradDims &D, int R, int SP = EBC_LSTM_GRAD_CHUNK) {
   using namespace ebc_lstmg;
-  constexpr int C = EBC_LSTM_GRAD_CHUNK;
   const int Hp = pad4(D.H);
   const size_t slot = (size_t)pad4(D.T) + D.Op[L_M1A] + D.Op[L_M1B] + D.Op[L_M1C] + D.Op[L_M1D] + 4 * D.H + 3 * Hp;
-  const size_t state = (size_t)pad4(D.K[L_MA]) + D.Op[L_MA] + D.Op[L_MB] + D.Op[L_MC] + 2 * Hp + 6;
-  return (size_t)C * R * slot + C * state + Hp;
+  const size_t state = (size_t)pad4(D.K[L_MA]) + D.Op[L_MA] + D.Op[L_MB] + D.Op[L_MC] + 2 * Hp;
+  return (size_t)SP * R * slot + SP * state + Hp + 4 * (size_t)pad4(SP) + pad4(2 * SP);
 }
-// the largest R whose chunk fits a workgroup's LDS (0: not even one row)
-__host__ __device__ inline int lstm_grad_max_rows(const ebc_lstmg::GradDims &D) {
+// the largest R at which SP states fit a workgroup's LDS (0: not even one row)
+__host__ __device__ inline int lstm_grad_max_rows(const ebc_lstmg::GradDims &D, int SP = EBC_LSTM_GRAD_CHUNK) {
   int R = 0;
-  while (R < 1024 && lstm_grad_lds_floats(D, R + 1) * sizeof(float) <= EBC_LSTM_GRAD_LDS_BYTES) ++R;
+  while (R < 1024 && lstm_grad_lds_floats(D, R + 1, SP) * sizeof(float) <= EBC_LSTM_GRAD_LDS_BYTES) ++R;
   return R;
 }
-__device__ __forceinline__ LstmGradLds lstm_grad_lds(float *p, const ebc_lstmg::GradDims &D, int R) {
+__device__ __forceinline__ LstmGradLds lstm_grad_lds(float *p, const ebc_lstmg::GradDims &D, int R, int SP) {
   using namespace ebc_lstmg;
-  constexpr int C = EBC_LSTM_GRAD_CHUNK;
-  const int NR = C * R;
+  const int NR = SP * R, SPp = pad4(SP);
   LstmGradLds L;
   L.Tp = pad4(D.T), L.Jp = pad4(D.K[L_MA]), L.Hp = pad4(D.H), L.RS = 4 * D.H + 3 * L.Hp;
   L.X = p, p += NR * L.Tp;
@@ -86,17 +95,17 @@ __device__ __forceinline__ LstmGradLds lstm_grad_lds(float *p, const ebc_lstmg::
   L.XI = D.two ? p : L.X, p += NR * D.Op[L_M1D];
   L.xis = D.two ? D.Op[L_M1D] : L.Tp;
   L.REC = p, p += NR * L.RS;
-  L.J = p, p += C * L.Jp;
-  L.M1 = p, p += C * D.Op[L_MA];
-  L.M2 = p, p += C * D.Op[L_MB];
-  L.M3 = p, p += C * D.Op[L_MC];
-  L.DH = p, p += C * L.Hp;
-  L.DC = p, p += C * L.Hp;
+  L.J = p, p += SP * L.Jp;
+  L.M1 = p, p += SP * D.Op[L_MA];
+  L.M2 = p, p += SP * D.Op[L_MB];
+  L.M3 = p, p += SP * D.Op[L_MC];
+  L.DH = p, p += SP * L.Hp;
+  L.DC = p, p += SP * L.Hp;
   L.ZERO = p, p += L.Hp;
-  L.OUT = p, p += C;
-  L.SEED = p, p += C;
-  L.LOSS = reinterpret_cast<double *>(p), p += 2 * C;  // every offset so far is a multiple of 4 floats
-  L.LIVE = reinterpret_cast<int *>(p), p += C;
+  L.OUT = p, p += SPp;
+  L.SEED = p, p += SPp;
+  L.LOSS = reinterpret_cast<double *>(p), p += pad4(2 * SP);  // every array is a multiple of 4 floats long: so is every offset
+  L.LIVE = reinterpret_cast<int *>(p), p += SPp;
   L.N = reinterpret_cast<int *>(p);
   return L;
 }
@@ -135,14 +144,16 @@ __device__ __forceinline__ void lstmg_layer(const float *__restrict__ W, int K, 
 
 // a layer's dW and db into G (the layer's place in the chunk's partial, (K + 1) * Op floats) over the chunk's live states
 // s < nc ascending and, with per_row, their steps r < N[s] ascending: delta at delta + q * ds, the input at x + q * xs (q the
-// slot, or the state without per_row).  Pad entries get 0.
+// slot, or the state without per_row).  Pad entries get 0.  cont (a later pass of the chunk): the chain goes on from what
+// this thread stored into G in the pass before, not from 0.
 __device__ __forceinline__ void lstmg_dw(float *__restrict__ G, int K, int O, int Op, const float *delta, int ds, const float *x, int xs, int R,
-                                         int nc, const int *N, const int *live, bool per_row) {
+                                         int nc, const int *N, const int *live, bool per_row, bool cont) {
   const int total = (K + 1) * Op;
   for (int idx = threadIdx.x; idx < total; idx += kLstmGradNT) {
     const int k = idx / Op, u = idx - k * Op;
     float acc = 0.0f;
     if (u < O) {
+      if (cont) acc = G[idx];
       for (int s = 0; s < nc; ++s) {
         if (!live[s]) continue;
         const int n = per_row ? N[s] : 1, q0 = per_row ? s * R : s;
@@ -190,201 +201,212 @@ __device__ __forceinline__ void lstmg_dx(const float *__restrict__ W, int k0, in
   }
 }
 
+// PASSES false: the whole chunk at once.  true: a.SP states at a time (see "Passes" above).
+template <bool PASSES>
 __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__restrict__ P, const LstmGradLaunch a) {
   extern __shared__ float4 lstm_grad_lds4[];
   constexpr int C = EBC_LSTM_GRAD_CHUNK, NT = kLstmGradNT;
   using namespace ebc_lstmg;
   const GradDims &D = a.D;
   const int tid = threadIdx.x, R = a.R, T = D.T, S = D.S, I = D.I, H = D.H, H4 = 4 * D.H;
-  const LstmGradLds L = lstm_grad_lds(reinterpret_cast<float *>(lstm_grad_lds4), D, R);
+  const int SP = PASSES ? a.SP : C;
+  const LstmGradLds L = lstm_grad_lds(reinterpret_cast<float *>(lstm_grad_lds4), D, R, SP);
   const int Tp = L.Tp, Jp = L.Jp, Hp = L.Hp, RS = L.RS, xis = L.xis;
   const int CO = H4, TCO = H4 + Hp, HO = H4 + 2 * Hp;  // c, tanh(c) and h in a step's record, after its 4 H gates
   const int O0 = D.Op[L_M1A], O1 = D.Op[L_M1B], O2 = D.Op[L_M1C], O4 = D.Op[L_MA], O5 = D.Op[L_MB], O6 = D.Op[L_MC];
-  const long long c0 = ((long long)a.chunk0 + blockIdx.x) * C;
-  const int nc = a.B - c0 < C ? (int)(a.B - c0) : C;  // states of this chunk, >= 1
-  const int nq = nc * R;
+  const long long chunk_at = ((long long)a.chunk0 + blockIdx.x) * C;
+  const int chunk_n = a.B - chunk_at < C ? (int)(a.B - chunk_at) : C;  // states of this chunk, >= 1
   float *const part = a.partial + (size_t)blockIdx.x * D.floats;
   const float *const Wih = P + D.at_cell, *const Whh = Wih + (size_t)I * H4, *const Bih = Whh + (size_t)H * H4, *const Bhh = Bih + H4;
 #define AT(l) (P + D.at[l])
 #define GAT(l) (part + D.at[l])
 
-  // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
-  if (tid < C) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
-  if (tid < Hp) L.ZERO[tid] = 0.0f;
-  __syncthreads();
-  for (int i = tid; i < nq * T; i += NT) {
-    const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
-    L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
-  }
-  int nmax = 0;
-  for (int s = 0; s < nc; ++s) nmax = L.N[s] > nmax ? L.N[s] : nmax;
-  __syncthreads();
+  int at = 0;  // the pass's first state in the chunk
+  do {
+    const bool cont = PASSES && at > 0;
+    const long long c0 = chunk_at + at;
+    const int nc = chunk_n - at < SP ? chunk_n - at : SP;  // states of this pass, >= 1
+    const int nq = nc * R;
 
-  // ---- forward: mlp1
-  if (D.two) {
-    lstmg_layer<true>(AT(L_M1A), T, D.O[L_M1A], O0, L.X, Tp, L.A1, O0, nq);
+    // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
+    if (tid < SP) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
+    if (tid < Hp) L.ZERO[tid] = 0.0f;
     __syncthreads();
-    lstmg_layer<true>(AT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A1, O0, L.A2, O1, nq);
+    for (int i = tid; i < nq * T; i += NT) {
+      const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
+      L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
+    }
+    int nmax = 0;
+    for (int s = 0; s < nc; ++s) nmax = L.N[s] > nmax ? L.N[s] : nmax;
     __syncthreads();
-    lstmg_layer<true>(AT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A2, O1, L.A3, O2, nq);
-    __syncthreads();
-    lstmg_layer<false>(AT(L_M1D), D.K[L_M1D], I, xis, L.A3, O2, L.XI, xis, nq);
-    __syncthreads();
-  }
 
-  // ---- forward: the recurrence, a step at a time
-  const int pairs = (nc + 1) / 2;
-  for (int t = 0; t < nmax; ++t) {
-    for (int idx = tid; idx < pairs * H4; idx += NT) {
-      const int pair = idx / H4, q = idx - pair * H4, s0 = 2 * pair, s1 = s0 + 1 < nc ? s0 + 1 : s0;
-      const float *x0 = L.XI + (size_t)(s0 * R + t) * xis, *x1 = L.XI + (size_t)(s1 * R + t) * xis;
-      const float *h0 = t ? L.REC + (size_t)(s0 * R + t - 1) * RS + HO : L.ZERO, *h1 = t ? L.REC + (size_t)(s1 * R + t - 1) * RS + HO : L.ZERO;
-      float acc0 = gate_bias(Bih[q], Bhh[q]), acc1 = acc0;
-      for (int k = 0; k < I; ++k) {
-        const float w = Wih[(size_t)k * H4 + q];
-        acc0 = gate_chain(w, x0[k], acc0);
-        acc1 = gate_chain(w, x1[k], acc1);
+    // ---- forward: mlp1
+    if (D.two) {
+      lstmg_layer<true>(AT(L_M1A), T, D.O[L_M1A], O0, L.X, Tp, L.A1, O0, nq);
+      __syncthreads();
+      lstmg_layer<true>(AT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A1, O0, L.A2, O1, nq);
+      __syncthreads();
+      lstmg_layer<true>(AT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A2, O1, L.A3, O2, nq);
+      __syncthreads();
+      lstmg_layer<false>(AT(L_M1D), D.K[L_M1D], I, xis, L.A3, O2, L.XI, xis, nq);
+      __syncthreads();
+    }
+
+    // ---- forward: the recurrence, a step at a time
+    const int pairs = (nc + 1) / 2;
+    for (int t = 0; t < nmax; ++t) {
+      for (int idx = tid; idx < pairs * H4; idx += NT) {
+        const int pair = idx / H4, q = idx - pair * H4, s0 = 2 * pair, s1 = s0 + 1 < nc ? s0 + 1 : s0;
+        const float *x0 = L.XI + (size_t)(s0 * R + t) * xis, *x1 = L.XI + (size_t)(s1 * R + t) * xis;
+        const float *h0 = t ? L.REC + (size_t)(s0 * R + t - 1) * RS + HO : L.ZERO, *h1 = t ? L.REC + (size_t)(s1 * R + t - 1) * RS + HO : L.ZERO;
+        float acc0 = gate_bias(Bih[q], Bhh[q]), acc1 = acc0;
+        for (int k = 0; k < I; ++k) {
+          const float w = Wih[(size_t)k * H4 + q];
+          acc0 = gate_chain(w, x0[k], acc0);
+          acc1 = gate_chain(w, x1[k], acc1);
+        }
+        for (int k = 0; k < H; ++k) {
+          const float w = Whh[(size_t)k * H4 + q];
+          acc0 = gate_chain(w, h0[k], acc0);
+          acc1 = gate_chain(w, h1[k], acc1);
+        }
+        if (t < L.N[s0]) L.REC[(size_t)(s0 * R + t) * RS + q] = acc0;
+        if (s1 != s0 && t < L.N[s1]) L.REC[(size_t)(s1 * R + t) * RS + q] = acc1;
       }
-      for (int k = 0; k < H; ++k) {
-        const float w = Whh[(size_t)k * H4 + q];
-        acc0 = gate_chain(w, h0[k], acc0);
-        acc1 = gate_chain(w, h1[k], acc1);
+      __syncthreads();
+      for (int idx = tid; idx < nc * H; idx += NT) {
+        const int s = idx / H, u = idx - s * H;
+        if (t >= L.N[s]) continue;
+        float *rec = L.REC + (size_t)(s * R + t) * RS;
+        const float c_prev = t ? rec[CO + u - RS] : 0.0f;
+        cell_forward(rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], c_prev, rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], rec[CO + u],
+                     rec[TCO + u], rec[HO + u]);
       }
-      if (t < L.N[s0]) L.REC[(size_t)(s0 * R + t) * RS + q] = acc0;
-      if (s1 != s0 && t < L.N[s1]) L.REC[(size_t)(s1 * R + t) * RS + q] = acc1;
+      __syncthreads();
+    }
+
+    // ---- the joint vector: the self state of row 0 and h of the state's last step
+    for (int i = tid; i < nc * (S + H); i += NT) {
+      const int s = i / (S + H), k = i - s * (S + H), n = L.N[s];
+      const float v = n < 1 ? 0.0f : (k < S ? L.X[(s * R) * Tp + k] : L.REC[(size_t)(s * R + n - 1) * RS + HO + (k - S)]);
+      L.J[s * Jp + k] = v;
+      if (a.joint) a.joint[(size_t)(c0 + s) * (S + H) + k] = n < 1 ? 0.0f : canon(v);
     }
     __syncthreads();
-    for (int idx = tid; idx < nc * H; idx += NT) {
-      const int s = idx / H, u = idx - s * H;
-      if (t >= L.N[s]) continue;
-      float *rec = L.REC + (size_t)(s * R + t) * RS;
-      const float c_prev = t ? rec[CO + u - RS] : 0.0f;
-      cell_forward(rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], c_prev, rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], rec[CO + u],
-                   rec[TCO + u], rec[HO + u]);
-    }
+    // ---- mlp
+    lstmg_layer<true>(AT(L_MA), S + H, D.O[L_MA], O4, L.J, Jp, L.M1, O4, nc);
     __syncthreads();
-  }
-
-  // ---- the joint vector: the self state of row 0 and h of the state's last step
-  for (int i = tid; i < nc * (S + H); i += NT) {
-    const int s = i / (S + H), k = i - s * (S + H), n = L.N[s];
-    const float v = n < 1 ? 0.0f : (k < S ? L.X[(s * R) * Tp + k] : L.REC[(size_t)(s * R + n - 1) * RS + HO + (k - S)]);
-    L.J[s * Jp + k] = v;
-    if (a.joint) a.joint[(size_t)(c0 + s) * (S + H) + k] = n < 1 ? 0.0f : canon(v);
-  }
-  __syncthreads();
-  // ---- mlp
-  lstmg_layer<true>(AT(L_MA), S + H, D.O[L_MA], O4, L.J, Jp, L.M1, O4, nc);
-  __syncthreads();
-  lstmg_layer<true>(AT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M1, O4, L.M2, O5, nc);
-  __syncthreads();
-  lstmg_layer<true>(AT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M2, O5, L.M3, O6, nc);
-  __syncthreads();
-  lstmg_layer<false>(AT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.M3, O6, L.OUT, 1, nc);
-  __syncthreads();
-
-  // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
-  if (tid < C) L.LIVE[tid] = 0;
-  if (tid < nc) {
-    const long long b = c0 + tid;
-    const float val = grad_value(L.OUT[tid], L.N[tid]);
-    if (a.value) a.value[b] = val;
-    const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
-    L.LIVE[tid] = live ? 1 : 0;
-    if (live) {
-      const float d = grad_diff(val, a.target[b]);
-      L.LOSS[tid] = grad_loss(d);
-      L.SEED[tid] = a.grad_scale * d;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double loss = 0.0;
-    long long count = 0;
-    for (int s = 0; s < nc; ++s) {
-      if (!L.LIVE[s]) continue;
-      loss = loss + L.LOSS[s];
-      count += 1;
-    }
-    a.loss_part[blockIdx.x] = loss;
-    a.count_part[blockIdx.x] = count;
-  }
-
-  // ---- backward: mlp
-  lstmg_dw(GAT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  lstmg_dx<true>(AT(L_MD), 0, D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, false);
-  __syncthreads();
-  lstmg_dw(GAT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  lstmg_dx<true>(AT(L_MC), 0, D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, true);
-  __syncthreads();
-  lstmg_dw(GAT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  lstmg_dx<true>(AT(L_MB), 0, D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, true);
-  __syncthreads();
-  lstmg_dw(GAT(L_MA), S + H, D.O[L_MA], O4, L.M1, O4, L.J, Jp, R, nc, L.N, L.LIVE, false);
-  lstmg_dx<false>(AT(L_MA), S, S + H, D.O[L_MA], O4, L.M1, O4, L.DH, Hp, R, nc, L.N, L.LIVE, false, true);  // dh of the last step
-  for (int i = tid; i < nc * H; i += NT) L.DC[(i / H) * Hp + (i % H)] = 0.0f;
-  __syncthreads();
-
-  // ---- backward through time: the gates become their deltas
-  for (int t = nmax - 1; t >= 0; --t) {
-    for (int idx = tid; idx < nc * H; idx += NT) {
-      const int s = idx / H, u = idx - s * H;
-      if (!L.LIVE[s] || t >= L.N[s]) continue;
-      float *rec = L.REC + (size_t)(s * R + t) * RS;
-      const float c_prev = t ? rec[CO + u - RS] : 0.0f;
-      cell_back(L.DH[s * Hp + u], L.DC[s * Hp + u], rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], rec[TCO + u], c_prev, rec[u], rec[H + u],
-                rec[2 * H + u], rec[3 * H + u], L.DC[s * Hp + u]);
-    }
+    lstmg_layer<true>(AT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M1, O4, L.M2, O5, nc);
     __syncthreads();
-    if (t == 0) break;
-    for (int idx = tid; idx < nc * H; idx += NT) {
-      const int k = idx / nc, s = idx - k * nc;
-      if (!L.LIVE[s] || t >= L.N[s]) continue;
-      L.DH[s * Hp + k] = lstmg_dot(Whh + (size_t)k * H4, L.REC + (size_t)(s * R + t) * RS, H4, true);
-    }
+    lstmg_layer<true>(AT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M2, O5, L.M3, O6, nc);
     __syncthreads();
-  }
+    lstmg_layer<false>(AT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.M3, O6, L.OUT, 1, nc);
+    __syncthreads();
 
-  // ---- the cell's weights: w_ih [I][4 H] | w_hh [H][4 H] | b_ih | b_hh are (I + H + 2) rows of 4 H in the image
-  for (int idx = tid; idx < (I + H + 2) * H4; idx += NT) {
-    const int k = idx / H4, q = idx - k * H4;
-    float acc = 0.0f;
-    for (int s = 0; s < nc; ++s) {
-      if (!L.LIVE[s]) continue;
-      const int n = L.N[s];
-      const float *rec = L.REC + (size_t)(s * R) * RS;
-      if (k < I) {
-        for (int t = 0; t < n; ++t) acc = chain(rec[(size_t)t * RS + q], L.XI[(size_t)(s * R + t) * xis + k], acc);
-      } else if (k < I + H) {
-        for (int t = 0; t < n; ++t) acc = chain(rec[(size_t)t * RS + q], t ? rec[(size_t)(t - 1) * RS + HO + (k - I)] : 0.0f, acc);
-      } else {
-        for (int t = 0; t < n; ++t) acc = acc + rec[(size_t)t * RS + q];
+    // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
+    if (tid < SP) L.LIVE[tid] = 0;
+    if (tid < nc) {
+      const long long b = c0 + tid;
+      const float val = grad_value(L.OUT[tid], L.N[tid]);
+      if (a.value) a.value[b] = val;
+      const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
+      L.LIVE[tid] = live ? 1 : 0;
+      if (live) {
+        const float d = grad_diff(val, a.target[b]);
+        L.LOSS[tid] = grad_loss(d);
+        L.SEED[tid] = a.grad_scale * d;
       }
     }
-    part[D.at_cell + idx] = acc;
-  }
-  if (D.two) {
-    // ---- mlp1: xi becomes its delta (the cell's dW above has read it)
     __syncthreads();
-    lstmg_dx<false>(Wih, 0, I, H4, H4, L.REC, RS, L.XI, xis, R, nc, L.N, L.LIVE, true, true);
+    if (tid == 0) {
+      double loss = cont ? a.loss_part[blockIdx.x] : 0.0;
+      long long count = cont ? a.count_part[blockIdx.x] : 0;
+      for (int s = 0; s < nc; ++s) {
+        if (!L.LIVE[s]) continue;
+        loss = loss + L.LOSS[s];
+        count += 1;
+      }
+      a.loss_part[blockIdx.x] = loss;
+      a.count_part[blockIdx.x] = count;
+    }
+
+    // ---- backward: mlp
+    lstmg_dw(GAT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dw(GAT(L_M1D), D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true);
+    lstmg_dx<true>(AT(L_MD), 0, D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, false);
     __syncthreads();
-    lstmg_dx<true>(AT(L_M1D), 0, D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, true);
+    lstmg_dw(GAT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dw(GAT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true);
+    lstmg_dx<true>(AT(L_MC), 0, D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    lstmg_dx<true>(AT(L_M1C), 0, D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, true);
+    lstmg_dw(GAT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dw(GAT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true);
+    lstmg_dx<true>(AT(L_MB), 0, D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    lstmg_dx<true>(AT(L_M1B), 0, D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
+    lstmg_dw(GAT(L_MA), S + H, D.O[L_MA], O4, L.M1, O4, L.J, Jp, R, nc, L.N, L.LIVE, false, cont);
+    lstmg_dx<false>(AT(L_MA), S, S + H, D.O[L_MA], O4, L.M1, O4, L.DH, Hp, R, nc, L.N, L.LIVE, false, true);  // dh of the last step
+    for (int i = tid; i < nc * H; i += NT) L.DC[(i / H) * Hp + (i % H)] = 0.0f;
     __syncthreads();
-    lstmg_dw(GAT(L_M1A), T, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, R, nc, L.N, L.LIVE, true);
-  }
+
+    // ---- backward through time: the gates become their deltas
+    for (int t = nmax - 1; t >= 0; --t) {
+      for (int idx = tid; idx < nc * H; idx += NT) {
+        const int s = idx / H, u = idx - s * H;
+        if (!L.LIVE[s] || t >= L.N[s]) continue;
+        float *rec = L.REC + (size_t)(s * R + t) * RS;
+        const float c_prev = t ? rec[CO + u - RS] : 0.0f;
+        cell_back(L.DH[s * Hp + u], L.DC[s * Hp + u], rec[u], rec[H + u], rec[2 * H + u], rec[3 * H + u], rec[TCO + u], c_prev, rec[u], rec[H + u],
+                  rec[2 * H + u], rec[3 * H + u], L.DC[s * Hp + u]);
+      }
+      __syncthreads();
+      if (t == 0) break;
+      for (int idx = tid; idx < nc * H; idx += NT) {
+        const int k = idx / nc, s = idx - k * nc;
+        if (!L.LIVE[s] || t >= L.N[s]) continue;
+        L.DH[s * Hp + k] = lstmg_dot(Whh + (size_t)k * H4, L.REC + (size_t)(s * R + t) * RS, H4, true);
+      }
+      __syncthreads();
+    }
+
+    // ---- the cell's weights: w_ih [I][4 H] | w_hh [H][4 H] | b_ih | b_hh are (I + H + 2) rows of 4 H in the image
+    for (int idx = tid; idx < (I + H + 2) * H4; idx += NT) {
+      const int k = idx / H4, q = idx - k * H4;
+      float acc = cont ? part[D.at_cell + idx] : 0.0f;
+      for (int s = 0; s < nc; ++s) {
+        if (!L.LIVE[s]) continue;
+        const int n = L.N[s];
+        const float *rec = L.REC + (size_t)(s * R) * RS;
+        if (k < I) {
+          for (int t = 0; t < n; ++t) acc = chain(rec[(size_t)t * RS + q], L.XI[(size_t)(s * R + t) * xis + k], acc);
+        } else if (k < I + H) {
+          for (int t = 0; t < n; ++t) acc = chain(rec[(size_t)t * RS + q], t ? rec[(size_t)(t - 1) * RS + HO + (k - I)] : 0.0f, acc);
+        } else {
+          for (int t = 0; t < n; ++t) acc = acc + rec[(size_t)t * RS + q];
+        }
+      }
+      part[D.at_cell + idx] = acc;
+    }
+    if (D.two) {
+      // ---- mlp1: xi becomes its delta (the cell's dW above has read it)
+      __syncthreads();
+      lstmg_dx<false>(Wih, 0, I, H4, H4, L.REC, RS, L.XI, xis, R, nc, L.N, L.LIVE, true, true);
+      __syncthreads();
+      lstmg_dw(GAT(L_M1D), D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, cont);
+      __syncthreads();
+      lstmg_dx<true>(AT(L_M1D), 0, D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, true);
+      __syncthreads();
+      lstmg_dw(GAT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, cont);
+      __syncthreads();
+      lstmg_dx<true>(AT(L_M1C), 0, D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, true);
+      __syncthreads();
+      lstmg_dw(GAT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, cont);
+      __syncthreads();
+      lstmg_dx<true>(AT(L_M1B), 0, D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
+      __syncthreads();
+      lstmg_dw(GAT(L_M1A), T, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, R, nc, L.N, L.LIVE, true, cont);
+    }
+    if (PASSES) __syncthreads();  // the next pass's forward overwrites what this pass's dW reads
+  } while (PASSES && (at += SP) < chunk_n);
 #undef AT
 #undef GAT
 }

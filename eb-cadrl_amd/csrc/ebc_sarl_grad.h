@@ -20,6 +20,13 @@
 // delta) and the weight; per state the mean G (later the mean's delta), the joint vector J, its delta DWF, M1, M2, M3,
 // the output, the seed, the loss and two ints.  At the reference widths 622 floats per slot and 566 per state: 59 KB at
 // R = 5, 109 KB at R = 10, and R <= 15 (158 KB) fits the 160 KB of a gfx950 workgroup.  The weights (381 KB at the reference widths) stay in L2.
+//
+// Passes (sarl_grad_kernel<true>): the chunk's states run SP in {4, 2, 1} at a time, LDS sized for SP states, so that more
+// rows fit (R <= 32 at SP = 2, 64 at SP = 1 at the reference widths).  A pass is the whole forward and backward of its
+// states; the thread that owns entries (k, u) of a layer owns them in every pass, and from the second pass on it loads
+// its entries from the chunk's partial (global memory, its own earlier store) and continues the fmaf chain where the
+// pass before left it: the same chain, the same bytes, whatever SP.  The chunk's float64 loss and count carry on in the
+// same way with thread 0.  The first pass always has a state and starts every chain at 0, live or not.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -44,6 +51,7 @@ struct SarlGradLaunch {
   float grad_scale;
   int B, R;
   int chunk0;                 // the first chunk of this launch
+  int SP;                     // states per pass: 4, 2 or 1 (read by the pass form only)
   ebc_sarl::GradDims D;
 };
 
@@ -53,23 +61,23 @@ struct SarlGradLds {
   int *LIVE, *N;
   int Tp, Jp;
 };
-__host__ __device__ inline size_t sarl_grad_lds_floats(const ebc_sarl::GradDims &D, int R) {
+// the floats of LDS for SP states at a time (SP = the chunk: the whole chunk at once); the arrays that are SP * R or SP long
+// are padded to 4 floats each, so that what follows them keeps its 16-byte (LOSS: 8-byte) alignment at every SP and R
+__host__ __device__ inline size_t sarl_grad_lds_floats(const ebc_sarl::GradDims &D, int R, int SP = EBC_SARL_GRAD_CHUNK) {
   using namespace ebc_sarl;
-  constexpr int C = EBC_SARL_GRAD_CHUNK;
-  const size_t slot = (size_t)pad4(D.T) + D.Op[L_M1A] + D.Op[L_M1B] + D.Op[L_M2A] + D.Op[L_M2B] + D.Op[L_ATA] + D.Op[L_ATB] + 2;
-  const size_t state = (size_t)D.Op[L_M1B] + pad4(D.K[L_M3A]) + D.Op[L_M2B] + D.Op[L_M3A] + D.Op[L_M3B] + D.Op[L_M3C] + 6;
-  return (size_t)C * R * slot + C * state;
+  const size_t slot = (size_t)pad4(D.T) + D.Op[L_M1A] + D.Op[L_M1B] + D.Op[L_M2A] + D.Op[L_M2B] + D.Op[L_ATA] + D.Op[L_ATB];
+  const size_t state = (size_t)D.Op[L_M1B] + pad4(D.K[L_M3A]) + D.Op[L_M2B] + D.Op[L_M3A] + D.Op[L_M3B] + D.Op[L_M3C];
+  return (size_t)SP * R * slot + 2 * (size_t)pad4(SP * R) + SP * state + 4 * (size_t)pad4(SP) + pad4(2 * SP);
 }
-// the largest R whose chunk fits a workgroup's LDS (0: not even one row)
-__host__ __device__ inline int sarl_grad_max_rows(const ebc_sarl::GradDims &D) {
+// the largest R at which SP states fit a workgroup's LDS (0: not even one row)
+__host__ __device__ inline int sarl_grad_max_rows(const ebc_sarl::GradDims &D, int SP = EBC_SARL_GRAD_CHUNK) {
   int R = 0;
-  while (R < 1024 && sarl_grad_lds_floats(D, R + 1) * sizeof(float) <= EBC_SARL_GRAD_LDS_BYTES) ++R;
+  while (R < 1024 && sarl_grad_lds_floats(D, R + 1, SP) * sizeof(float) <= EBC_SARL_GRAD_LDS_BYTES) ++R;
   return R;
 }
-__device__ __forceinline__ SarlGradLds sarl_grad_lds(float *p, const ebc_sarl::GradDims &D, int R) {
+__device__ __forceinline__ SarlGradLds sarl_grad_lds(float *p, const ebc_sarl::GradDims &D, int R, int SP) {
   using namespace ebc_sarl;
-  constexpr int C = EBC_SARL_GRAD_CHUNK;
-  const int NR = C * R;
+  const int NR = SP * R, NRp = pad4(NR), SPp = pad4(SP);
   SarlGradLds L;
   L.Tp = pad4(D.T), L.Jp = pad4(D.K[L_M3A]);
   L.X = p, p += NR * L.Tp;
@@ -79,18 +87,18 @@ __device__ __forceinline__ SarlGradLds sarl_grad_lds(float *p, const ebc_sarl::G
   L.FT = p, p += NR * D.Op[L_M2B];
   L.C1 = p, p += NR * D.Op[L_ATA];
   L.C2 = p, p += NR * D.Op[L_ATB];
-  L.SC = p, p += NR;
-  L.WT = p, p += NR;
-  L.G = p, p += C * D.Op[L_M1B];
-  L.J = p, p += C * L.Jp;
-  L.DWF = p, p += C * D.Op[L_M2B];
-  L.M1 = p, p += C * D.Op[L_M3A];
-  L.M2 = p, p += C * D.Op[L_M3B];
-  L.M3 = p, p += C * D.Op[L_M3C];
-  L.OUT = p, p += C;
-  L.SEED = p, p += C;
-  L.LOSS = reinterpret_cast<double *>(p), p += 2 * C;  // every offset so far is a multiple of 4 floats
-  L.LIVE = reinterpret_cast<int *>(p), p += C;
+  L.SC = p, p += NRp;
+  L.WT = p, p += NRp;
+  L.G = p, p += SP * D.Op[L_M1B];
+  L.J = p, p += SP * L.Jp;
+  L.DWF = p, p += SP * D.Op[L_M2B];
+  L.M1 = p, p += SP * D.Op[L_M3A];
+  L.M2 = p, p += SP * D.Op[L_M3B];
+  L.M3 = p, p += SP * D.Op[L_M3C];
+  L.OUT = p, p += SPp;
+  L.SEED = p, p += SPp;
+  L.LOSS = reinterpret_cast<double *>(p), p += pad4(2 * SP);  // every array is a multiple of 4 floats long: so is every offset
+  L.LIVE = reinterpret_cast<int *>(p), p += SPp;
   L.N = reinterpret_cast<int *>(p);
   return L;
 }
@@ -138,14 +146,16 @@ __device__ __forceinline__ void sarl_layer(const float *__restrict__ W, int K1, 
 
 // a layer's dW and db into G (the layer's place in the chunk's partial, (K1 + K2 + 1) * Op floats) over the chunk's live
 // states s < nc ascending and, with per_row, their rows r < N[s] ascending: delta at delta + q * ds, the input at x + q * xs
-// (q the slot, or the state without per_row), inputs K1 .. of the state's x2 + s * x2s.  Pad entries get 0.
+// (q the slot, or the state without per_row), inputs K1 .. of the state's x2 + s * x2s.  Pad entries get 0.  cont (a later
+// pass of the chunk): the chain goes on from what this thread stored into G in the pass before, not from 0.
 __device__ __forceinline__ void sarl_dw(float *__restrict__ G, int K1, int K2, int O, int Op, const float *delta, int ds, const float *x, int xs,
-                                        const float *x2, int x2s, int R, int nc, const int *N, const int *live, bool per_row) {
+                                        const float *x2, int x2s, int R, int nc, const int *N, const int *live, bool per_row, bool cont) {
   const int K = K1 + K2, total = (K + 1) * Op;
   for (int idx = threadIdx.x; idx < total; idx += kSarlNT) {
     const int k = idx / Op, u = idx - k * Op;
     float acc = 0.0f;
     if (u < O) {
+      if (cont) acc = G[idx];
       for (int s = 0; s < nc; ++s) {
         if (!live[s]) continue;
         const int n = per_row ? N[s] : 1, q0 = per_row ? s * R : s;
@@ -196,201 +206,212 @@ __device__ __forceinline__ void sarl_dx(const float *__restrict__ W, int k0, int
   }
 }
 
+// PASSES false: the whole chunk at once.  true: a.SP states at a time (see "Passes" above).
+template <bool PASSES>
 __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restrict__ P, const SarlGradLaunch a) {
   extern __shared__ float4 sarl_grad_lds4[];
   constexpr int C = EBC_SARL_GRAD_CHUNK, NT = kSarlNT;
   using namespace ebc_sarl;
   const GradDims &D = a.D;
   const int tid = threadIdx.x, R = a.R, T = D.T, S = D.S;
-  const SarlGradLds L = sarl_grad_lds(reinterpret_cast<float *>(sarl_grad_lds4), D, R);
+  const int SP = PASSES ? a.SP : C;
+  const SarlGradLds L = sarl_grad_lds(reinterpret_cast<float *>(sarl_grad_lds4), D, R, SP);
   const int Tp = L.Tp, Jp = L.Jp;
   const int O0 = D.Op[L_M1A], O1 = D.Op[L_M1B], O2 = D.Op[L_M2A], O3 = D.Op[L_M2B], O4 = D.Op[L_ATA], O5 = D.Op[L_ATB];
   const int O7 = D.Op[L_M3A], O8 = D.Op[L_M3B], O9 = D.Op[L_M3C];
   const int H = D.O[L_M1B], F = D.O[L_M2B], KG = D.global ? H : 0;
-  const long long c0 = ((long long)a.chunk0 + blockIdx.x) * C;
-  const int nc = a.B - c0 < C ? (int)(a.B - c0) : C;  // states of this chunk, >= 1
-  const int nq = nc * R;
+  const long long chunk_at = ((long long)a.chunk0 + blockIdx.x) * C;
+  const int chunk_n = a.B - chunk_at < C ? (int)(a.B - chunk_at) : C;  // states of this chunk, >= 1
   float *const part = a.partial + (size_t)blockIdx.x * D.floats;
 #define AT(l) (P + D.at[l])
 #define GAT(l) (part + D.at[l])
 
-  // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
-  if (tid < C) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
-  __syncthreads();
-  for (int i = tid; i < nq * T; i += NT) {
-    const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
-    L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
-  }
-  __syncthreads();
+  int at = 0;  // the pass's first state in the chunk
+  do {
+    const bool cont = PASSES && at > 0;
+    const long long c0 = chunk_at + at;
+    const int nc = chunk_n - at < SP ? chunk_n - at : SP;  // states of this pass, >= 1
+    const int nq = nc * R;
 
-  // ---- forward: mlp1, mlp2
-  sarl_layer<true>(AT(L_M1A), T, 0, D.O[L_M1A], O0, L.X, Tp, nullptr, 0, R, L.A1, O0, nq);
-  __syncthreads();
-  sarl_layer<true>(AT(L_M1B), D.K[L_M1B], 0, H, O1, L.A1, O0, nullptr, 0, R, L.H1, O1, nq);
-  __syncthreads();
-  sarl_layer<true>(AT(L_M2A), H, 0, D.O[L_M2A], O2, L.H1, O1, nullptr, 0, R, L.B1, O2, nq);
-  if (D.global)
-    for (int i = tid; i < nc * H; i += NT) {
-      const int s = i / H, k = i - s * H, n = L.N[s];
-      if (n < 1) continue;
-      float acc = 0.0f;
-      for (int r = 0; r < n; ++r) acc = acc + L.H1[(s * R + r) * O1 + k];
-      L.G[s * O1 + k] = over_rows(acc, n);
-    }
-  __syncthreads();
-  sarl_layer<false>(AT(L_M2B), D.K[L_M2B], 0, F, O3, L.B1, O2, nullptr, 0, R, L.FT, O3, nq);
-  // ---- attention
-  sarl_layer<true>(AT(L_ATA), H, KG, D.O[L_ATA], O4, L.H1, O1, L.G, O1, R, L.C1, O4, nq);
-  __syncthreads();
-  sarl_layer<true>(AT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C1, O4, nullptr, 0, R, L.C2, O5, nq);
-  __syncthreads();
-  sarl_layer<false>(AT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.C2, O5, nullptr, 0, R, L.SC, 1, nq);
-  __syncthreads();
-  if (tid < nc) {
-    const int n = L.N[tid], q0 = tid * R;
-    float sum = 0.0f;
-    for (int r = 0; r < n; ++r) {
-      const float e = score_exp(L.SC[q0 + r]);
-      L.WT[q0 + r] = e;
-      sum = sum + e;
-    }
-    for (int r = 0; r < n; ++r) L.WT[q0 + r] = quotient(L.WT[q0 + r], sum);
-    if (a.attention)
-      for (int r = 0; r < R; ++r) a.attention[(size_t)(c0 + tid) * R + r] = r < n ? canon(L.WT[q0 + r]) : 0.0f;
-  }
-  __syncthreads();
-  // ---- the joint vector: the self state of row 0 and the weighted feature
-  for (int i = tid; i < nc * (S + F); i += NT) {
-    const int s = i / (S + F), k = i - s * (S + F);
-    float v;
-    if (k < S) {
-      v = L.X[(s * R) * Tp + k];
-    } else {
-      v = 0.0f;
-      for (int r = 0; r < L.N[s]; ++r) v = chain(L.WT[s * R + r], L.FT[(s * R + r) * O3 + (k - S)], v);
-    }
-    L.J[s * Jp + k] = v;
-  }
-  __syncthreads();
-  // ---- mlp3
-  sarl_layer<true>(AT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.J, Jp, nullptr, 0, 1, L.M1, O7, nc);
-  __syncthreads();
-  sarl_layer<true>(AT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M1, O7, nullptr, 0, 1, L.M2, O8, nc);
-  __syncthreads();
-  sarl_layer<true>(AT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M2, O8, nullptr, 0, 1, L.M3, O9, nc);
-  __syncthreads();
-  sarl_layer<false>(AT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.M3, O9, nullptr, 0, 1, L.OUT, 1, nc);
-  __syncthreads();
-
-  // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
-  if (tid < C) L.LIVE[tid] = 0;
-  if (tid < nc) {
-    const long long b = c0 + tid;
-    const float val = grad_value(L.OUT[tid], L.N[tid]);
-    if (a.value) a.value[b] = val;
-    const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
-    L.LIVE[tid] = live ? 1 : 0;
-    if (live) {
-      const float d = grad_diff(val, a.target[b]);
-      L.LOSS[tid] = grad_loss(d);
-      L.SEED[tid] = a.grad_scale * d;
-    }
-  }
-  __syncthreads();
-  if (tid == 0) {
-    double loss = 0.0;
-    long long count = 0;
-    for (int s = 0; s < nc; ++s) {
-      if (!L.LIVE[s]) continue;
-      loss = loss + L.LOSS[s];
-      count += 1;
-    }
-    a.loss_part[blockIdx.x] = loss;
-    a.count_part[blockIdx.x] = count;
-  }
-
-  // ---- backward: mlp3
-  sarl_dw(GAT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, nullptr, 0, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  sarl_dx<true>(AT(L_M3D), 0, D.K[L_M3D], 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, R, nc, L.N, L.LIVE, false, false);
-  __syncthreads();
-  sarl_dw(GAT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M3, O9, L.M2, O8, nullptr, 0, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  sarl_dx<true>(AT(L_M3C), 0, D.K[L_M3C], D.O[L_M3C], O9, L.M3, O9, L.M2, O8, R, nc, L.N, L.LIVE, false, true);
-  __syncthreads();
-  sarl_dw(GAT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M2, O8, L.M1, O7, nullptr, 0, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  sarl_dx<true>(AT(L_M3B), 0, D.K[L_M3B], D.O[L_M3B], O8, L.M2, O8, L.M1, O7, R, nc, L.N, L.LIVE, false, true);
-  __syncthreads();
-  sarl_dw(GAT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.M1, O7, L.J, Jp, nullptr, 0, R, nc, L.N, L.LIVE, false);
-  __syncthreads();
-  sarl_dx<false>(AT(L_M3A), S, S + F, D.O[L_M3A], O7, L.M1, O7, L.DWF, O3, R, nc, L.N, L.LIVE, false, true);  // dwf; J keeps wf
-  __syncthreads();
-
-  // ---- the weighted sum and the softmax
-  for (int q = tid; q < nq; q += NT) {
-    const int s = q / R;
-    if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
-    float acc = 0.0f;
-    for (int f = 0; f < F; ++f) acc = chain(L.DWF[s * O3 + f], centred(L.FT[q * O3 + f], L.J[s * Jp + S + f]), acc);
-    L.SC[q] = acc;
-  }
-  __syncthreads();
-  if (tid < nc && L.LIVE[tid]) {
-    const int n = L.N[tid], q0 = tid * R;
-    float m = 0.0f;
-    for (int r = 0; r < n; ++r) m = chain(L.WT[q0 + r], L.SC[q0 + r], m);
-    for (int r = 0; r < n; ++r) L.SC[q0 + r] = score_back(L.WT[q0 + r], L.SC[q0 + r], m);
-  }
-  for (int i = tid; i < nq * F; i += NT) {
-    const int q = i / F, f = i - q * F, s = q / R;
-    if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
-    L.FT[q * O3 + f] = L.WT[q] * L.DWF[s * O3 + f];
-  }
-  __syncthreads();
-
-  // ---- mlp2's last layer and attention's last layer
-  sarl_dw(GAT(L_M2B), D.K[L_M2B], 0, F, O3, L.FT, O3, L.B1, O2, nullptr, 0, R, nc, L.N, L.LIVE, true);
-  sarl_dw(GAT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, nullptr, 0, R, nc, L.N, L.LIVE, true);
-  __syncthreads();
-  sarl_dx<true>(AT(L_M2B), 0, D.K[L_M2B], F, O3, L.FT, O3, L.B1, O2, R, nc, L.N, L.LIVE, true, true);
-  sarl_dx<true>(AT(L_ATC), 0, D.K[L_ATC], 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, R, nc, L.N, L.LIVE, true, false);
-  __syncthreads();
-  sarl_dw(GAT(L_M2A), H, 0, D.O[L_M2A], O2, L.B1, O2, L.H1, O1, nullptr, 0, R, nc, L.N, L.LIVE, true);
-  sarl_dw(GAT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C2, O5, L.C1, O4, nullptr, 0, R, nc, L.N, L.LIVE, true);
-  __syncthreads();
-  sarl_dx<true>(AT(L_ATB), 0, D.K[L_ATB], D.O[L_ATB], O5, L.C2, O5, L.C1, O4, R, nc, L.N, L.LIVE, true, true);
-  __syncthreads();
-  sarl_dw(GAT(L_ATA), H, KG, D.O[L_ATA], O4, L.C1, O4, L.H1, O1, L.G, O1, R, nc, L.N, L.LIVE, true);
-  __syncthreads();
-
-  // ---- h1: the mean's delta (into G), then mlp2's layer 0 + attention's layer 0 + the mean
-  if (D.global) {
-    for (int i = tid; i < nc * H; i += NT) {
-      const int k = i / nc, s = i - k * nc, n = L.N[s];
-      if (!L.LIVE[s]) continue;
-      float dg = 0.0f;
-      for (int r = 0; r < n; ++r) dg = dg + sarl_dot(AT(L_ATA) + (size_t)(H + k) * O4, L.C1 + (size_t)(s * R + r) * O4, D.O[L_ATA], true);
-      L.G[s * O1 + k] = over_rows(dg, n);
+    // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
+    if (tid < SP) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
+    __syncthreads();
+    for (int i = tid; i < nq * T; i += NT) {
+      const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
+      L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
     }
     __syncthreads();
-  }
-  for (int i = tid; i < nq * H; i += NT) {
-    const int k = i / nq, q = i - k * nq, s = q / R;
-    if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
-    const float d2 = sarl_dot(AT(L_M2A) + (size_t)k * O2, L.B1 + (size_t)q * O2, D.O[L_M2A], true);
-    const float d4 = sarl_dot(AT(L_ATA) + (size_t)k * O4, L.C1 + (size_t)q * O4, D.O[L_ATA], true);
-    float *o = L.H1 + (size_t)q * O1 + k;
-    *o = h1_back(*o, d2, d4, D.global ? L.G[s * O1 + k] : 0.0f, D.global);
-  }
-  __syncthreads();
 
-  // ---- mlp1
-  sarl_dw(GAT(L_M1B), D.K[L_M1B], 0, H, O1, L.H1, O1, L.A1, O0, nullptr, 0, R, nc, L.N, L.LIVE, true);
-  __syncthreads();
-  sarl_dx<true>(AT(L_M1B), 0, D.K[L_M1B], H, O1, L.H1, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
-  __syncthreads();
-  sarl_dw(GAT(L_M1A), T, 0, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, nullptr, 0, R, nc, L.N, L.LIVE, true);
+    // ---- forward: mlp1, mlp2
+    sarl_layer<true>(AT(L_M1A), T, 0, D.O[L_M1A], O0, L.X, Tp, nullptr, 0, R, L.A1, O0, nq);
+    __syncthreads();
+    sarl_layer<true>(AT(L_M1B), D.K[L_M1B], 0, H, O1, L.A1, O0, nullptr, 0, R, L.H1, O1, nq);
+    __syncthreads();
+    sarl_layer<true>(AT(L_M2A), H, 0, D.O[L_M2A], O2, L.H1, O1, nullptr, 0, R, L.B1, O2, nq);
+    if (D.global)
+      for (int i = tid; i < nc * H; i += NT) {
+        const int s = i / H, k = i - s * H, n = L.N[s];
+        if (n < 1) continue;
+        float acc = 0.0f;
+        for (int r = 0; r < n; ++r) acc = acc + L.H1[(s * R + r) * O1 + k];
+        L.G[s * O1 + k] = over_rows(acc, n);
+      }
+    __syncthreads();
+    sarl_layer<false>(AT(L_M2B), D.K[L_M2B], 0, F, O3, L.B1, O2, nullptr, 0, R, L.FT, O3, nq);
+    // ---- attention
+    sarl_layer<true>(AT(L_ATA), H, KG, D.O[L_ATA], O4, L.H1, O1, L.G, O1, R, L.C1, O4, nq);
+    __syncthreads();
+    sarl_layer<true>(AT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C1, O4, nullptr, 0, R, L.C2, O5, nq);
+    __syncthreads();
+    sarl_layer<false>(AT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.C2, O5, nullptr, 0, R, L.SC, 1, nq);
+    __syncthreads();
+    if (tid < nc) {
+      const int n = L.N[tid], q0 = tid * R;
+      float sum = 0.0f;
+      for (int r = 0; r < n; ++r) {
+        const float e = score_exp(L.SC[q0 + r]);
+        L.WT[q0 + r] = e;
+        sum = sum + e;
+      }
+      for (int r = 0; r < n; ++r) L.WT[q0 + r] = quotient(L.WT[q0 + r], sum);
+      if (a.attention)
+        for (int r = 0; r < R; ++r) a.attention[(size_t)(c0 + tid) * R + r] = r < n ? canon(L.WT[q0 + r]) : 0.0f;
+    }
+    __syncthreads();
+    // ---- the joint vector: the self state of row 0 and the weighted feature
+    for (int i = tid; i < nc * (S + F); i += NT) {
+      const int s = i / (S + F), k = i - s * (S + F);
+      float v;
+      if (k < S) {
+        v = L.X[(s * R) * Tp + k];
+      } else {
+        v = 0.0f;
+        for (int r = 0; r < L.N[s]; ++r) v = chain(L.WT[s * R + r], L.FT[(s * R + r) * O3 + (k - S)], v);
+      }
+      L.J[s * Jp + k] = v;
+    }
+    __syncthreads();
+    // ---- mlp3
+    sarl_layer<true>(AT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.J, Jp, nullptr, 0, 1, L.M1, O7, nc);
+    __syncthreads();
+    sarl_layer<true>(AT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M1, O7, nullptr, 0, 1, L.M2, O8, nc);
+    __syncthreads();
+    sarl_layer<true>(AT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M2, O8, nullptr, 0, 1, L.M3, O9, nc);
+    __syncthreads();
+    sarl_layer<false>(AT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.M3, O9, nullptr, 0, 1, L.OUT, 1, nc);
+    __syncthreads();
+
+    // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
+    if (tid < SP) L.LIVE[tid] = 0;
+    if (tid < nc) {
+      const long long b = c0 + tid;
+      const float val = grad_value(L.OUT[tid], L.N[tid]);
+      if (a.value) a.value[b] = val;
+      const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
+      L.LIVE[tid] = live ? 1 : 0;
+      if (live) {
+        const float d = grad_diff(val, a.target[b]);
+        L.LOSS[tid] = grad_loss(d);
+        L.SEED[tid] = a.grad_scale * d;
+      }
+    }
+    __syncthreads();
+    if (tid == 0) {
+      double loss = cont ? a.loss_part[blockIdx.x] : 0.0;
+      long long count = cont ? a.count_part[blockIdx.x] : 0;
+      for (int s = 0; s < nc; ++s) {
+        if (!L.LIVE[s]) continue;
+        loss = loss + L.LOSS[s];
+        count += 1;
+      }
+      a.loss_part[blockIdx.x] = loss;
+      a.count_part[blockIdx.x] = count;
+    }
+
+    // ---- backward: mlp3
+    sarl_dw(GAT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_M3D), 0, D.K[L_M3D], 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, R, nc, L.N, L.LIVE, false, false);
+    __syncthreads();
+    sarl_dw(GAT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M3, O9, L.M2, O8, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_M3C), 0, D.K[L_M3C], D.O[L_M3C], O9, L.M3, O9, L.M2, O8, R, nc, L.N, L.LIVE, false, true);
+    __syncthreads();
+    sarl_dw(GAT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M2, O8, L.M1, O7, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_M3B), 0, D.K[L_M3B], D.O[L_M3B], O8, L.M2, O8, L.M1, O7, R, nc, L.N, L.LIVE, false, true);
+    __syncthreads();
+    sarl_dw(GAT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.M1, O7, L.J, Jp, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    __syncthreads();
+    sarl_dx<false>(AT(L_M3A), S, S + F, D.O[L_M3A], O7, L.M1, O7, L.DWF, O3, R, nc, L.N, L.LIVE, false, true);  // dwf; J keeps wf
+    __syncthreads();
+
+    // ---- the weighted sum and the softmax
+    for (int q = tid; q < nq; q += NT) {
+      const int s = q / R;
+      if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
+      float acc = 0.0f;
+      for (int f = 0; f < F; ++f) acc = chain(L.DWF[s * O3 + f], centred(L.FT[q * O3 + f], L.J[s * Jp + S + f]), acc);
+      L.SC[q] = acc;
+    }
+    __syncthreads();
+    if (tid < nc && L.LIVE[tid]) {
+      const int n = L.N[tid], q0 = tid * R;
+      float m = 0.0f;
+      for (int r = 0; r < n; ++r) m = chain(L.WT[q0 + r], L.SC[q0 + r], m);
+      for (int r = 0; r < n; ++r) L.SC[q0 + r] = score_back(L.WT[q0 + r], L.SC[q0 + r], m);
+    }
+    for (int i = tid; i < nq * F; i += NT) {
+      const int q = i / F, f = i - q * F, s = q / R;
+      if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
+      L.FT[q * O3 + f] = L.WT[q] * L.DWF[s * O3 + f];
+    }
+    __syncthreads();
+
+    // ---- mlp2's last layer and attention's last layer
+    sarl_dw(GAT(L_M2B), D.K[L_M2B], 0, F, O3, L.FT, O3, L.B1, O2, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    sarl_dw(GAT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_M2B), 0, D.K[L_M2B], F, O3, L.FT, O3, L.B1, O2, R, nc, L.N, L.LIVE, true, true);
+    sarl_dx<true>(AT(L_ATC), 0, D.K[L_ATC], 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, R, nc, L.N, L.LIVE, true, false);
+    __syncthreads();
+    sarl_dw(GAT(L_M2A), H, 0, D.O[L_M2A], O2, L.B1, O2, L.H1, O1, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    sarl_dw(GAT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C2, O5, L.C1, O4, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_ATB), 0, D.K[L_ATB], D.O[L_ATB], O5, L.C2, O5, L.C1, O4, R, nc, L.N, L.LIVE, true, true);
+    __syncthreads();
+    sarl_dw(GAT(L_ATA), H, KG, D.O[L_ATA], O4, L.C1, O4, L.H1, O1, L.G, O1, R, nc, L.N, L.LIVE, true, cont);
+    __syncthreads();
+
+    // ---- h1: the mean's delta (into G), then mlp2's layer 0 + attention's layer 0 + the mean
+    if (D.global) {
+      for (int i = tid; i < nc * H; i += NT) {
+        const int k = i / nc, s = i - k * nc, n = L.N[s];
+        if (!L.LIVE[s]) continue;
+        float dg = 0.0f;
+        for (int r = 0; r < n; ++r) dg = dg + sarl_dot(AT(L_ATA) + (size_t)(H + k) * O4, L.C1 + (size_t)(s * R + r) * O4, D.O[L_ATA], true);
+        L.G[s * O1 + k] = over_rows(dg, n);
+      }
+      __syncthreads();
+    }
+    for (int i = tid; i < nq * H; i += NT) {
+      const int k = i / nq, q = i - k * nq, s = q / R;
+      if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
+      const float d2 = sarl_dot(AT(L_M2A) + (size_t)k * O2, L.B1 + (size_t)q * O2, D.O[L_M2A], true);
+      const float d4 = sarl_dot(AT(L_ATA) + (size_t)k * O4, L.C1 + (size_t)q * O4, D.O[L_ATA], true);
+      float *o = L.H1 + (size_t)q * O1 + k;
+      *o = h1_back(*o, d2, d4, D.global ? L.G[s * O1 + k] : 0.0f, D.global);
+    }
+    __syncthreads();
+
+    // ---- mlp1
+    sarl_dw(GAT(L_M1B), D.K[L_M1B], 0, H, O1, L.H1, O1, L.A1, O0, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    __syncthreads();
+    sarl_dx<true>(AT(L_M1B), 0, D.K[L_M1B], H, O1, L.H1, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
+    __syncthreads();
+    sarl_dw(GAT(L_M1A), T, 0, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    if (PASSES) __syncthreads();  // the next pass's forward overwrites what this dW reads
+  } while (PASSES && (at += SP) < chunk_n);
 #undef AT
 #undef GAT
 }

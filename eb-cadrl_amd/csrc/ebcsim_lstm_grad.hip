@@ -19,10 +19,16 @@ struct LstmNet {
   int device = 0;
   ebc_lstmg::GradDims D;
   int max_rows = 0;          // the largest R whose chunk fits a workgroup's LDS
+  int max_rows_at[3] = {0, 0, 0};  // the same with 4, 2, 1 states per pass
   float *P = nullptr;        // the packed image
   void *scratch = nullptr;   // float64 sums | chunk losses | chunk counts | chunk partials
   size_t scratch_bytes = 0;
 };
+
+// states_per_pass 4, 2, 1 -> 0, 1, 2; anything else -1
+int pass_index(int states_per_pass) {
+  return states_per_pass == 4 ? 0 : states_per_pass == 2 ? 1 : states_per_pass == 1 ? 2 : -1;
+}
 
 bool capturing(void *stream) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -74,6 +80,7 @@ extern "C" int ebc_lstm_net_create(const EbcLstmNetWeights *weights, int device_
   n->device = device_id;
   n->D = ebc_lstmg::grad_dims(widths, w.self_state_dim, two);
   n->max_rows = ebc::lstm_grad_max_rows(n->D);
+  for (int sp = 4, i = 0; sp >= 1; sp /= 2, ++i) n->max_rows_at[i] = ebc::lstm_grad_max_rows(n->D, sp);
   std::vector<float> image(n->D.floats);
   ebc_lstmg::grad_pack(n->D, w.weight, w.bias, w.w_ih, w.w_hh, w.b_ih, w.b_hh, image.data());
   hipError_t err = hipMalloc(&n->P, image.size() * sizeof(float));
@@ -109,6 +116,16 @@ extern "C" int ebc_lstm_net_grad_max_rows(void *net, int *rows_out) {
   return EBC_OK;
 }
 
+extern "C" int ebc_lstm_net_grad_max_rows_at(void *net, int states_per_pass, int *rows_out) {
+  if (!net || !rows_out) return fail(EBC_ERR_INVALID, "ebc_lstm_net_grad_max_rows_at: null argument");
+  const int i = pass_index(states_per_pass);
+  if (states_per_pass != 0 && i < 0)
+    return fail(EBC_ERR_INVALID, "ebc_lstm_net_grad_max_rows_at: states_per_pass " + std::to_string(states_per_pass) + " is none of 0, 4, 2, 1");
+  const LstmNet *n = static_cast<LstmNet *>(net);
+  *rows_out = states_per_pass == 0 ? n->max_rows : n->max_rows_at[i];
+  return EBC_OK;
+}
+
 extern "C" int ebc_lstm_net_get_packed(void *net, void *stream, float *dst_dev) {
   if (!net || !dst_dev) return fail(EBC_ERR_INVALID, "ebc_lstm_net_get_packed: null argument");
   if (capturing(stream)) return fail(EBC_ERR_UNSUPPORTED, "ebc_lstm_net_get_packed: the stream is being captured into a HIP graph");
@@ -132,14 +149,20 @@ extern "C" int ebc_lstm_grad(void *net, void *stream, const EbcLstmGradArgs *arg
   if (!args || args->struct_size != sizeof(EbcLstmGradArgs)) return fail(EBC_ERR_INVALID, "EbcLstmGradArgs.struct_size");
   if (!args->grad || !args->loss_sum || !args->count || args->B < 0) return fail(EBC_ERR_INVALID, "ebc_lstm_grad: grad, loss_sum, count, B");
   if (args->B > 0 && (!args->rows || !args->target)) return fail(EBC_ERR_INVALID, "ebc_lstm_grad: rows, target");
+  const int sp = args->states_per_pass, pi = pass_index(sp);  // 0: the whole chunk at once, today's kernel
+  if (sp != 0 && pi < 0) return fail(EBC_ERR_INVALID, "ebc_lstm_grad: states_per_pass " + std::to_string(sp) + " is none of 0, 4, 2, 1");
   LstmNet *n = static_cast<LstmNet *>(net);
   const ebc_lstmg::GradDims &D = n->D;
   if (args->T != D.T)
     return fail(EBC_ERR_INVALID, "ebc_lstm_grad: rows are " + std::to_string(args->T) + " wide, the network takes " + std::to_string(D.T));
   if (args->R < 1) return fail(EBC_ERR_UNSUPPORTED, "ebc_lstm_grad: R < 1 row slots per state (" + std::to_string(args->R) + ")");
-  if (args->R > n->max_rows)
+  if (sp == 0 && args->R > n->max_rows)
     return fail(EBC_ERR_UNSUPPORTED, "ebc_lstm_grad: R = " + std::to_string(args->R) + " row slots per state, a chunk of this network fits a workgroup's " +
                                          std::to_string(EBC_LSTM_GRAD_LDS_BYTES / 1024) + " KB of LDS up to R = " + std::to_string(n->max_rows));
+  if (sp != 0 && args->R > n->max_rows_at[pi])
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_lstm_grad: R = " + std::to_string(args->R) + " row slots per state with S = " + std::to_string(sp) +
+                                         " states per pass, that many states of this network fit a workgroup's " +
+                                         std::to_string(EBC_LSTM_GRAD_LDS_BYTES / 1024) + " KB of LDS up to R = " + std::to_string(n->max_rows_at[pi]));
   if (capturing(stream))
     return fail(EBC_ERR_UNSUPPORTED, "ebc_lstm_grad: the stream is being captured into a HIP graph; the gradient must be launched, not replayed");
   HIP_TRY(hipSetDevice(n->device));
@@ -164,9 +187,11 @@ extern "C" int ebc_lstm_grad(void *net, void *stream, const EbcLstmGradArgs *arg
   long long *count_part = reinterpret_cast<long long *>(loss_part + per);
   float *partial = reinterpret_cast<float *>(static_cast<char *>(n->scratch) + part_at);
 
-  const size_t lds = ebc::lstm_grad_lds_floats(D, args->R) * sizeof(float);  // <= 160 KB: R <= max_rows
-  static size_t raised_dev[64] = {0};
-  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::lstm_grad_kernel, n->device, lds, raised_dev));
+  // <= 160 KB: R <= max_rows, or max_rows_at of this pass size
+  const size_t lds = ebc::lstm_grad_lds_floats(D, args->R, sp ? sp : EBC_LSTM_GRAD_CHUNK) * sizeof(float);
+  const auto kernel = sp ? ebc::lstm_grad_kernel<true> : ebc::lstm_grad_kernel<false>;
+  static size_t raised_dev[2][64] = {{0}, {0}};  // the attribute is per kernel and device
+  HIP_TRY(ebc_host::raise_dynamic_lds(kernel, n->device, lds, raised_dev[sp ? 1 : 0]));
   const unsigned reduce_blocks = (unsigned)((PF + 255) / 256);
   long long done = 0;
   do {
@@ -186,8 +211,9 @@ extern "C" int ebc_lstm_grad(void *net, void *stream, const EbcLstmGradArgs *arg
       a.B = B;
       a.R = args->R;
       a.chunk0 = (int)done;
+      a.SP = sp;
       a.D = D;
-      hipLaunchKernelGGL(ebc::lstm_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_LSTM_GRAD_WAVES), lds, st, n->P, a);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)now), dim3(64 * EBC_LSTM_GRAD_WAVES), lds, st, n->P, a);
       HIP_TRY(hipGetLastError());
     }
     const int first = done == 0, last = done + now >= chunks;

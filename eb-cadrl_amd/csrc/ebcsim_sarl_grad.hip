@@ -19,10 +19,16 @@ struct SarlNet {
   int device = 0;
   ebc_sarl::GradDims D;
   int max_rows = 0;          // the largest R whose chunk fits a workgroup's LDS
+  int max_rows_at[3] = {0, 0, 0};  // the same with 4, 2, 1 states per pass
   float *P = nullptr;        // the packed image
   void *scratch = nullptr;   // float64 sums | chunk losses | chunk counts | chunk partials
   size_t scratch_bytes = 0;
 };
+
+// states_per_pass 4, 2, 1 -> 0, 1, 2; anything else -1
+int pass_index(int states_per_pass) {
+  return states_per_pass == 4 ? 0 : states_per_pass == 2 ? 1 : states_per_pass == 1 ? 2 : -1;
+}
 
 bool capturing(void *stream) {
   hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
@@ -69,6 +75,7 @@ static int net_create(const EbcSarlNetWeights *weights, int om_width, int device
   widths[0] += om_width;  // the rows the gradient reads: the rotated columns, then the map
   n->D = ebc_sarl::grad_dims(widths, w.self_state_dim, w.with_global_state);
   n->max_rows = ebc::sarl_grad_max_rows(n->D);
+  for (int sp = 4, i = 0; sp >= 1; sp /= 2, ++i) n->max_rows_at[i] = ebc::sarl_grad_max_rows(n->D, sp);
   std::vector<float> image(n->D.floats);
   ebc_sarl::grad_pack(n->D, w.weight, w.bias, image.data());
   hipError_t err = hipMalloc(&n->P, image.size() * sizeof(float));
@@ -112,6 +119,16 @@ extern "C" int ebc_sarl_net_grad_max_rows(void *net, int *rows_out) {
   return EBC_OK;
 }
 
+extern "C" int ebc_sarl_net_grad_max_rows_at(void *net, int states_per_pass, int *rows_out) {
+  if (!net || !rows_out) return fail(EBC_ERR_INVALID, "ebc_sarl_net_grad_max_rows_at: null argument");
+  const int i = pass_index(states_per_pass);
+  if (states_per_pass != 0 && i < 0)
+    return fail(EBC_ERR_INVALID, "ebc_sarl_net_grad_max_rows_at: states_per_pass " + std::to_string(states_per_pass) + " is none of 0, 4, 2, 1");
+  const SarlNet *n = static_cast<SarlNet *>(net);
+  *rows_out = states_per_pass == 0 ? n->max_rows : n->max_rows_at[i];
+  return EBC_OK;
+}
+
 extern "C" int ebc_sarl_net_get_packed(void *net, void *stream, float *dst_dev) {
   if (!net || !dst_dev) return fail(EBC_ERR_INVALID, "ebc_sarl_net_get_packed: null argument");
   if (capturing(stream)) return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_get_packed: the stream is being captured into a HIP graph");
@@ -135,14 +152,20 @@ extern "C" int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *arg
   if (!args || args->struct_size != sizeof(EbcSarlGradArgs)) return fail(EBC_ERR_INVALID, "EbcSarlGradArgs.struct_size");
   if (!args->grad || !args->loss_sum || !args->count || args->B < 0) return fail(EBC_ERR_INVALID, "ebc_sarl_grad: grad, loss_sum, count, B");
   if (args->B > 0 && (!args->rows || !args->target)) return fail(EBC_ERR_INVALID, "ebc_sarl_grad: rows, target");
+  const int sp = args->states_per_pass, pi = pass_index(sp);  // 0: the whole chunk at once, today's kernel
+  if (sp != 0 && pi < 0) return fail(EBC_ERR_INVALID, "ebc_sarl_grad: states_per_pass " + std::to_string(sp) + " is none of 0, 4, 2, 1");
   SarlNet *n = static_cast<SarlNet *>(net);
   const ebc_sarl::GradDims &D = n->D;
   if (args->T != D.T)
     return fail(EBC_ERR_INVALID, "ebc_sarl_grad: rows are " + std::to_string(args->T) + " wide, the network takes " + std::to_string(D.T));
   if (args->R < 1) return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_grad: R < 1 row slots per state (" + std::to_string(args->R) + ")");
-  if (args->R > n->max_rows)
+  if (sp == 0 && args->R > n->max_rows)
     return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_grad: R = " + std::to_string(args->R) + " row slots per state, a chunk of this network fits a workgroup's " +
                                          std::to_string(EBC_SARL_GRAD_LDS_BYTES / 1024) + " KB of LDS up to R = " + std::to_string(n->max_rows));
+  if (sp != 0 && args->R > n->max_rows_at[pi])
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_grad: R = " + std::to_string(args->R) + " row slots per state with S = " + std::to_string(sp) +
+                                         " states per pass, that many states of this network fit a workgroup's " +
+                                         std::to_string(EBC_SARL_GRAD_LDS_BYTES / 1024) + " KB of LDS up to R = " + std::to_string(n->max_rows_at[pi]));
   if (capturing(stream))
     return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_grad: the stream is being captured into a HIP graph; the gradient must be launched, not replayed");
   HIP_TRY(hipSetDevice(n->device));
@@ -167,9 +190,11 @@ extern "C" int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *arg
   long long *count_part = reinterpret_cast<long long *>(loss_part + per);
   float *partial = reinterpret_cast<float *>(static_cast<char *>(n->scratch) + part_at);
 
-  const size_t lds = ebc::sarl_grad_lds_floats(D, args->R) * sizeof(float);  // <= 160 KB: R <= max_rows
-  static size_t raised_dev[64] = {0};
-  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::sarl_grad_kernel, n->device, lds, raised_dev));
+  // <= 160 KB: R <= max_rows, or max_rows_at of this pass size
+  const size_t lds = ebc::sarl_grad_lds_floats(D, args->R, sp ? sp : EBC_SARL_GRAD_CHUNK) * sizeof(float);
+  const auto kernel = sp ? ebc::sarl_grad_kernel<true> : ebc::sarl_grad_kernel<false>;
+  static size_t raised_dev[2][64] = {{0}, {0}};  // the attribute is per kernel and device
+  HIP_TRY(ebc_host::raise_dynamic_lds(kernel, n->device, lds, raised_dev[sp ? 1 : 0]));
   const unsigned reduce_blocks = (unsigned)((PF + 255) / 256);
   long long done = 0;
   do {
@@ -189,8 +214,9 @@ extern "C" int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *arg
       a.B = B;
       a.R = args->R;
       a.chunk0 = (int)done;
+      a.SP = sp;
       a.D = D;
-      hipLaunchKernelGGL(ebc::sarl_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_SARL_GRAD_WAVES), lds, st, n->P, a);
+      hipLaunchKernelGGL(kernel, dim3((unsigned)now), dim3(64 * EBC_SARL_GRAD_WAVES), lds, st, n->P, a);
       HIP_TRY(hipGetLastError());
     }
     const int first = done == 0, last = done + now >= chunks;

@@ -295,9 +295,9 @@ class EbcSarlNetWeights(C.Structure):
 class EbcSarlGradArgs(C.Structure):
     """include/ebcsim.h: one ebc_sarl_grad (rows [B][R][T] float32, n_valid [B] int64 or NULL, target [B] float32, sample_mask
     [B] uint8 or NULL -> grad float32 [packed floats], loss_sum float64 [1], count int64 [1], value [B] float32 or NULL,
-    attention [B][R] float32 or NULL)."""
+    attention [B][R] float32 or NULL).  states_per_pass: 0 = the whole chunk at once, 4 / 2 / 1 = that many states at a time."""
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
-                ("reserved", C.c_int32)] + [
+                ("states_per_pass", C.c_int32)] + [
         (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "attention")]
 
 
@@ -317,7 +317,7 @@ class EbcLstmNetWeights(C.Structure):
 class EbcLstmGradArgs(C.Structure):
     """include/ebcsim.h: one ebc_lstm_grad (rows [B][R][T] float32, n_valid [B] int64 or NULL, target [B] float32, sample_mask
     [B] uint8 or NULL -> grad float32 [packed floats], loss_sum float64 [1], count int64 [1], value [B] float32 or NULL,
-    joint [B][S + H] float32 or NULL)."""
+    joint [B][S + H] float32 or NULL).  states_per_pass: 0 = the whole chunk at once, 4 / 2 / 1 = that many states at a time."""
     _fields_ = [("struct_size", C.c_uint32), ("B", C.c_int32), ("R", C.c_int32), ("T", C.c_int32), ("grad_scale", C.c_float),
-                ("reserved", C.c_int32)] + [
+                ("states_per_pass", C.c_int32)] + [
         (k, C.c_void_p) for k in ("rows", "n_valid", "target", "sample_mask", "grad", "loss_sum", "count", "value", "joint")]

@@ -100,6 +100,7 @@ SYMBOLS = {
     "ebc_sarl_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sarl_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sarl_net_grad_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "ebc_sarl_net_grad_max_rows_at": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "ebc_sarl_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_lstm_net_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_lstm_net_destroy": (C.c_int, [C.c_void_p]),
@@ -107,6 +108,7 @@ SYMBOLS = {
     "ebc_lstm_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_lstm_net_set_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_lstm_net_grad_max_rows": (C.c_int, [C.c_void_p, C.POINTER(C.c_int)]),
+    "ebc_lstm_net_grad_max_rows_at": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),
     "ebc_lstm_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 

@@ -31,6 +31,7 @@ from . import _abi
 from .cadrl_train import _finite, live_states, optimize_batch, optimize_epoch, pad4  # noqa: F401 (re-exported)
 from .lstm_rl import LstmModule, LstmValueNet
 from .sarl import DeviceSarlPolicy
+from .sarl_train import PASS_SIZES, PassChoice, checked_states_per_pass, pick_states_per_pass  # noqa: F401 (re-exported)
 
 MLP1_KEYS = ("mlp1.0", "mlp1.2", "mlp1.4", "mlp1.6")
 MLP_KEYS = ("mlp.0", "mlp.2", "mlp.4", "mlp.6")
@@ -173,11 +174,15 @@ class LstmNet(object):
         _capi.check(self._L.ebc_lstm_net_packed_floats(self._h, C.byref(n)))
         return int(n.value)
 
-    def grad_max_rows(self):
-        """The largest R ebc_lstm_grad takes for this network (a chunk's activations fit a workgroup's LDS)."""
+    def grad_max_rows(self, states_per_pass=0):
+        """The largest R ebc_lstm_grad takes for this network: a chunk's activations (states_per_pass 4, 2, 1: those of
+        that many states) fit a workgroup's LDS."""
         from . import _capi
         n = C.c_int()
-        _capi.check(self._L.ebc_lstm_net_grad_max_rows(self._h, C.byref(n)))
+        if states_per_pass == 0:
+            _capi.check(self._L.ebc_lstm_net_grad_max_rows(self._h, C.byref(n)))
+        else:
+            _capi.check(self._L.ebc_lstm_net_grad_max_rows_at(self._h, int(states_per_pass), C.byref(n)))
         return int(n.value)
 
     def get_packed(self, out):
@@ -191,15 +196,18 @@ class LstmNet(object):
         assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.is_cuda and flat.numel() == self.packed_floats()
         _capi.check(self._L.ebc_lstm_net_set_packed(self._h, torch.cuda.current_stream(flat.device).cuda_stream, flat.data_ptr()))
 
-    def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, joint=None, T=None):
+    def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, joint=None, T=None,
+             states_per_pass=0):
         """One ebc_lstm_grad on the current stream: rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None,
         mask [B] uint8 or None -> grad [packed floats], loss_sum 0-d float64, count 0-d int64, value [B] float32 and
-        joint [B, S + H] float32 when given; every tensor contiguous on the network's device."""
+        joint [B, S + H] float32 when given; every tensor contiguous on the network's device.  states_per_pass: 0 = the
+        whole chunk at once; 4, 2, 1 = that many of a chunk's states at a time (more rows fit, the same bytes)."""
         from . import _capi
         B, R, Tr = (int(x) for x in rows.shape)
         a = _abi.EbcLstmGradArgs()
         a.struct_size = C.sizeof(a)
         a.B, a.R, a.T, a.grad_scale = B, R, Tr if T is None else int(T), float(grad_scale)
+        a.states_per_pass = int(states_per_pass)
         for name, t, dtype, numel in (("rows", rows, torch.float32, B * R * Tr), ("target", target, torch.float32, B),
                                       ("n_valid", n_valid, torch.int64, B), ("sample_mask", mask, torch.uint8, B),
                                       ("grad", grad, torch.float32, self.packed_floats()), ("loss_sum", loss_sum, torch.float64, 1),
@@ -221,13 +229,17 @@ class LstmNet(object):
 class LstmTrainer(object):
     """module_or_state_dict: an LstmModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
-    (HIP devices only; the default there) or torch autograd of LstmModule."""
+    (HIP devices only; the default there) or torch autograd of LstmModule.  states_per_pass (native only; native=False
+    ignores it): None = the kernel's default call, the whole chunk of 4 states at once; 1, 2, 4 = that many states at a
+    time, which takes more rows per state (LstmNet.grad_max_rows(S)) and gives the same bytes; "auto" = per call the
+    default call where the batch's R fits it, else the largest pass that holds R."""
 
-    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None):
+    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, states_per_pass=None):
         sd = module_or_state_dict.state_dict() if isinstance(module_or_state_dict, torch.nn.Module) else module_or_state_dict
         sd = collections.OrderedDict((k, v.detach().to("cpu", torch.float32)) for k, v in sd.items())
         self.device = torch.device(device)
         self.widths, self.self_state_dim, self.with_interaction_module = shape_of(sd)
+        self.states_per_pass = checked_states_per_pass(states_per_pass, "LstmTrainer")
         self.native = (self.device.type == "cuda") if native is None else bool(native)
         if self.native and self.device.type != "cuda":
             raise NotImplementedError("LstmTrainer(native=True) needs a HIP device: the kernel has no CPU form")
@@ -240,6 +252,11 @@ class LstmTrainer(object):
         if self.native:
             idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
             self.net = LstmNet(sd, idx)
+            self.passes = PassChoice(self.net, self.states_per_pass)
+
+    def grad_max_rows(self):
+        """The most rows per state the native path takes with this trainer's states_per_pass."""
+        return self.passes.max_rows()
 
     def set_learning_rate(self, lr):
         """Trainer.set_optimizer (trainer.py:24-45): a new optimizer at the stage's learning rate."""
@@ -307,7 +324,7 @@ class LstmTrainer(object):
             count = torch.empty((), dtype=torch.int64, device=self.device)
             nv = None if n_valid is None else n_valid.to(device=self.device, dtype=torch.int64).contiguous()
             mk = None if mask is None else mask.to(device=self.device).to(torch.uint8).contiguous()
-            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, joint)
+            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, joint, states_per_pass=self.passes.of(R))
             return loss, count
         if value is not None or joint is not None:
             raise NotImplementedError("LstmTrainer(native=False): `value` and `joint` are the kernel's outputs")
@@ -375,9 +392,9 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
                                       % (env.T, om.width, trainer.widths[0]))
         raise NotImplementedError("run_lstm_training: the env's rows are %d wide, the network takes %d (LSTM-RL runs with "
                                   "with_agent_type = 0; OM-LSTM needs om=)" % (env.T, trainer.widths[0]))
-    if trainer.native and env.R > trainer.net.grad_max_rows():
+    if trainer.native and env.R > trainer.grad_max_rows():
         raise NotImplementedError("run_lstm_training: %d rows per state, ebc_lstm_grad takes %d for this network; use native=False"
-                                  % (env.R, trainer.net.grad_max_rows()))
+                                  % (env.R, trainer.grad_max_rows()))
     memory = DeviceReplay(capacity, env.R, width, dev)
     hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}
 

@@ -33,6 +33,46 @@ LAYER_KEYS = ("mlp1.0", "mlp1.2", "mlp2.0", "mlp2.2", "attention.0", "attention.
 STACKS = (("mlp1", 2), ("mlp2", 2), ("attention", 3), ("mlp3", 4))
 MAX_IN, MAX_WIDTH = 64, 256  # csrc/ebc_sarl_grad_rule.h
 MAX_OM, MAX_WIDE = 192, 224  # the same: the widest map behind a row, the widest row with its map
+PASS_SIZES = (4, 2, 1)  # EbcSarlGradArgs.states_per_pass / EbcLstmGradArgs.states_per_pass: a chunk's states, that many at a time
+
+
+def checked_states_per_pass(value, who):
+    """A trainer's states_per_pass: None (the whole chunk at once, the kernel's default call), "auto", 1, 2 or 4."""
+    if value is None or value == "auto" or (type(value) is int and value in PASS_SIZES):
+        return value
+    raise ValueError("%s: states_per_pass is None, 'auto', 1, 2 or 4, got %r" % (who, value))
+
+
+def pick_states_per_pass(R, whole_chunk, limits):
+    """What "auto" passes to the kernel for states of R rows.  whole_chunk: the largest R of the default call
+    (grad_max_rows()); limits: {S: grad_max_rows(S)} for S in PASS_SIZES.  0 (the default call) where the whole chunk
+    fits, else the largest S whose limit holds R; past every limit 1, which the kernel then refuses by R, S and limit."""
+    if R <= whole_chunk:
+        return 0
+    for S in PASS_SIZES:
+        if R <= limits[S]:
+            return S
+    return PASS_SIZES[-1]
+
+
+class PassChoice(object):
+    """A trainer's states_per_pass over its network object (SarlNet / LstmNet): what each call passes and the most rows
+    the trainer takes.  The limits are asked of the network once."""
+
+    def __init__(self, net, setting):
+        self.setting = setting
+        self.whole_chunk = net.grad_max_rows()
+        self.limits = {S: net.grad_max_rows(S) for S in PASS_SIZES}
+
+    def of(self, R):
+        if self.setting is None:
+            return 0
+        return pick_states_per_pass(R, self.whole_chunk, self.limits) if self.setting == "auto" else self.setting
+
+    def max_rows(self):
+        if self.setting is None:
+            return self.whole_chunk
+        return max(self.whole_chunk, *self.limits.values()) if self.setting == "auto" else self.limits[self.setting]
 
 
 def _stack_keys(sd):
@@ -158,11 +198,15 @@ class SarlNet(object):
         _capi.check(self._L.ebc_sarl_net_packed_floats(self._h, C.byref(n)))
         return int(n.value)
 
-    def grad_max_rows(self):
-        """The largest R ebc_sarl_grad takes for this network (a chunk's activations fit a workgroup's LDS)."""
+    def grad_max_rows(self, states_per_pass=0):
+        """The largest R ebc_sarl_grad takes for this network: a chunk's activations (states_per_pass 4, 2, 1: those of
+        that many states) fit a workgroup's LDS."""
         from . import _capi
         n = C.c_int()
-        _capi.check(self._L.ebc_sarl_net_grad_max_rows(self._h, C.byref(n)))
+        if states_per_pass == 0:
+            _capi.check(self._L.ebc_sarl_net_grad_max_rows(self._h, C.byref(n)))
+        else:
+            _capi.check(self._L.ebc_sarl_net_grad_max_rows_at(self._h, int(states_per_pass), C.byref(n)))
         return int(n.value)
 
     def get_packed(self, out):
@@ -176,15 +220,18 @@ class SarlNet(object):
         assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.is_cuda and flat.numel() == self.packed_floats()
         _capi.check(self._L.ebc_sarl_net_set_packed(self._h, torch.cuda.current_stream(flat.device).cuda_stream, flat.data_ptr()))
 
-    def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, attention=None, T=None):
+    def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, attention=None, T=None,
+             states_per_pass=0):
         """One ebc_sarl_grad on the current stream: rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None,
         mask [B] uint8 or None -> grad [packed floats], loss_sum 0-d float64, count 0-d int64, value [B] float32 and
-        attention [B, R] float32 when given; every tensor contiguous on the network's device."""
+        attention [B, R] float32 when given; every tensor contiguous on the network's device.  states_per_pass: 0 = the
+        whole chunk at once; 4, 2, 1 = that many of a chunk's states at a time (more rows fit, the same bytes)."""
         from . import _capi
         B, R, Tr = (int(x) for x in rows.shape)
         a = _abi.EbcSarlGradArgs()
         a.struct_size = C.sizeof(a)
         a.B, a.R, a.T, a.grad_scale = B, R, Tr if T is None else int(T), float(grad_scale)
+        a.states_per_pass = int(states_per_pass)
         for name, t, dtype, numel in (("rows", rows, torch.float32, B * R * Tr), ("target", target, torch.float32, B),
                                       ("n_valid", n_valid, torch.int64, B), ("sample_mask", mask, torch.uint8, B),
                                       ("grad", grad, torch.float32, self.packed_floats()), ("loss_sum", loss_sum, torch.float64, 1),
@@ -207,14 +254,18 @@ class SarlTrainer(object):
     """module_or_state_dict: a SarlModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
     (HIP devices only; the default there) or torch autograd of SarlModule.  om_width: the W of OM-SARL's maps; the
-    network's mlp1.0 then takes T + W inputs, T = widths[0] - W the rotated width (1 .. 64), W <= 192, T + W <= 224."""
+    network's mlp1.0 then takes T + W inputs, T = widths[0] - W the rotated width (1 .. 64), W <= 192, T + W <= 224.
+    states_per_pass (native only; native=False ignores it): None = the kernel's default call, the whole chunk of 4 states
+    at once; 1, 2, 4 = that many states at a time, which takes more rows per state (SarlNet.grad_max_rows(S)) and gives
+    the same bytes; "auto" = per call the default call where the batch's R fits it, else the largest pass that holds R."""
 
-    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, om_width=0):
+    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, om_width=0, states_per_pass=None):
         sd = module_or_state_dict.state_dict() if isinstance(module_or_state_dict, torch.nn.Module) else module_or_state_dict
         sd = collections.OrderedDict((k, v.detach().to("cpu", torch.float32)) for k, v in sd.items())
         self.device = torch.device(device)
         self.widths, self.self_state_dim, self.with_global_state = shape_of(sd)
         self.om_width = int(om_width)
+        self.states_per_pass = checked_states_per_pass(states_per_pass, "SarlTrainer")
         if not 0 <= self.om_width <= MAX_OM:
             raise NotImplementedError("SarlTrainer: om_width %d outside 0 .. %d" % (self.om_width, MAX_OM))
         if self.widths[0] - self.om_width < 1:
@@ -233,6 +284,11 @@ class SarlTrainer(object):
         if self.native:
             idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
             self.net = SarlNet(sd, idx, om_width=self.om_width or None)
+            self.passes = PassChoice(self.net, self.states_per_pass)
+
+    def grad_max_rows(self):
+        """The most rows per state the native path takes with this trainer's states_per_pass."""
+        return self.passes.max_rows()
 
     def set_learning_rate(self, lr):
         """Trainer.set_optimizer (trainer.py:24-45): a new optimizer at the stage's learning rate."""
@@ -304,7 +360,7 @@ class SarlTrainer(object):
             count = torch.empty((), dtype=torch.int64, device=self.device)
             nv = None if n_valid is None else n_valid.to(device=self.device, dtype=torch.int64).contiguous()
             mk = None if mask is None else mask.to(device=self.device).to(torch.uint8).contiguous()
-            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, attention)
+            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, attention, states_per_pass=self.passes.of(R))
             return loss, count
         if value is not None or attention is not None:
             raise NotImplementedError("SarlTrainer(native=False): `value` and `attention` are the kernel's outputs")
@@ -367,9 +423,9 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     if env.T + W != trainer.widths[0] or W != getattr(trainer, "om_width", 0):
         raise NotImplementedError("run_sarl_training: the env's rows are %d wide and the occupancy maps %d, the network takes %d "
                                   "(%d of them maps)" % (env.T, W, trainer.widths[0], getattr(trainer, "om_width", 0)))
-    if trainer.native and env.R > trainer.net.grad_max_rows():
+    if trainer.native and env.R > trainer.grad_max_rows():
         raise NotImplementedError("run_sarl_training: %d rows per state, ebc_sarl_grad takes %d for this network; use native=False"
-                                  % (env.R, trainer.net.grad_max_rows()))
+                                  % (env.R, trainer.grad_max_rows()))
     memory = DeviceReplay(capacity, env.R, env.T + W, dev)
     om_kw = {} if om is None else {"om": om}  # without maps: the calls as they were
     hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}

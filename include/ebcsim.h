@@ -956,12 +956,17 @@ typedef struct EbcSarlNetWeights {
  * the network and grows on demand, exactly as ebc_cadrl_grad's: at most ONE ebc_sarl_grad in flight per network.  Device
  * pointers.  1 <= R <= ebc_sarl_net_grad_max_rows (a chunk's activations must fit a workgroup's 160 KB of LDS: 15 at the
  * reference widths), else EBC_ERR_UNSUPPORTED with nothing written; T other than the network's row width is
- * EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+ * EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED.
+ * states_per_pass = S: 0 is the call above.  4, 2 or 1 runs a chunk's states S at a time, so that only S states' activations
+ * must fit the LDS: 1 <= R <= ebc_sarl_net_grad_max_rows_at(S) (15, 32 and 64 at the reference widths), else
+ * EBC_ERR_UNSUPPORTED with nothing written and a message that names R, S and that limit.  From the second pass on, the
+ * thread that owns a weight's entry continues its fmaf chain from the chunk's partial sum: the chunks, the chains and so
+ * every byte written are those of states_per_pass = 0, whatever S.  Any other value is EBC_ERR_INVALID. */
 typedef struct EbcSarlGradArgs {
   uint32_t struct_size;
   int32_t B, R, T;
   float grad_scale;
-  int32_t reserved;
+  int32_t states_per_pass;      /* 0 = the whole chunk at once; 4, 2, 1 = that many states of a chunk at a time */
   const float *rows;            /* device float32 [B][R][T] */
   const int64_t *n_valid;       /* device int64 [B]; NULL = all R rows */
   const float *target;          /* device float32 [B] */
@@ -983,8 +988,10 @@ int ebc_sarl_net_destroy(void *net);
 int ebc_sarl_net_packed_floats(void *net, int64_t *floats_out);
 int ebc_sarl_net_get_packed(void *net, void *stream, float *dst_dev);
 int ebc_sarl_net_set_packed(void *net, void *stream, const float *src_dev);
-/* the largest R ebc_sarl_grad takes for this network */
+/* the largest R ebc_sarl_grad takes for this network with the whole chunk at once (states_per_pass = 0) */
 int ebc_sarl_net_grad_max_rows(void *net, int *rows_out);
+/* the same for a value of EbcSarlGradArgs.states_per_pass: 0, 4, 2 or 1 (anything else is EBC_ERR_INVALID) */
+int ebc_sarl_net_grad_max_rows_at(void *net, int states_per_pass, int *rows_out);
 int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *args);
 
 /* ---- training the LSTM-RL value networks (rl/policy/lstm_rl.py:9-69: ValueNetwork1, rows -> LSTM -> mlp on cat(self
@@ -1034,12 +1041,15 @@ typedef struct EbcLstmNetWeights {
  * the network and grows on demand, exactly as ebc_sarl_grad's: at most ONE ebc_lstm_grad in flight per network.  Device
  * pointers.  1 <= R <= ebc_lstm_net_grad_max_rows (a chunk's activations must fit a workgroup's 160 KB of LDS: 12 at the
  * reference widths with mlp1, 26 without), else EBC_ERR_UNSUPPORTED with nothing written; T other than the network's row
- * width is EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED. */
+ * width is EBC_ERR_INVALID; a stream under capture is refused with EBC_ERR_UNSUPPORTED.
+ * states_per_pass = S: 0 is the call above.  4, 2 or 1 runs a chunk's states S at a time, exactly as EbcSarlGradArgs says:
+ * 1 <= R <= ebc_lstm_net_grad_max_rows_at(S) (12, 25 and 52 at the reference widths with mlp1), the bytes of
+ * states_per_pass = 0 whatever S, EBC_ERR_UNSUPPORTED by R, S and the limit above it, EBC_ERR_INVALID for any other value. */
 typedef struct EbcLstmGradArgs {
   uint32_t struct_size;
   int32_t B, R, T;
   float grad_scale;
-  int32_t reserved;
+  int32_t states_per_pass;      /* 0 = the whole chunk at once; 4, 2, 1 = that many states of a chunk at a time */
   const float *rows;            /* device float32 [B][R][T] */
   const int64_t *n_valid;       /* device int64 [B]; NULL = all R rows */
   const float *target;          /* device float32 [B] */
@@ -1055,8 +1065,10 @@ int ebc_lstm_net_destroy(void *net);
 int ebc_lstm_net_packed_floats(void *net, int64_t *floats_out);
 int ebc_lstm_net_get_packed(void *net, void *stream, float *dst_dev);
 int ebc_lstm_net_set_packed(void *net, void *stream, const float *src_dev);
-/* the largest R ebc_lstm_grad takes for this network */
+/* the largest R ebc_lstm_grad takes for this network with the whole chunk at once (states_per_pass = 0) */
 int ebc_lstm_net_grad_max_rows(void *net, int *rows_out);
+/* the same for a value of EbcLstmGradArgs.states_per_pass: 0, 4, 2 or 1 (anything else is EBC_ERR_INVALID) */
+int ebc_lstm_net_grad_max_rows_at(void *net, int states_per_pass, int *rows_out);
 int ebc_lstm_grad(void *net, void *stream, const EbcLstmGradArgs *args);
 
 #ifdef __cplusplus

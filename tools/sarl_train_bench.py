@@ -4,7 +4,10 @@ row, softmax, backward and the reduction of the chunk partials) and torch autogr
 backward), at the reference's batch of 100 states and at 4096, with 5 and 10 rows per state, T = 13; and a full optimizer
 step through SarlTrainer against ebcsim.train.DataParallelTrainer.optimize_batch(1), what run_training takes per step.
 
-    python3 tools/sarl_train_bench.py [--blocks 7] [--reps 20] [--out profiles/sarl_train.txt]
+    python3 tools/sarl_train_bench.py [--blocks 7] [--reps 20] [--out profiles/sarl_train.txt] [--passes]
+
+--passes instead times the pass form of the kernel (states_per_pass): 4, 2 and 1 states of a chunk at a time against the
+whole chunk at the shapes above, and states_per_pass="auto" at 16, 24 and 30 rows per state against torch autograd.
 
 Warm-up first, then the median over `--blocks` blocks of `--reps` back-to-back calls.  Two clocks per block: a pair of
 events on the stream (what the device sees from the first kernel's start to the last one's end, host gaps between the
@@ -20,6 +23,7 @@ for p in (ROOT, os.path.join(ROOT, "eb-cadrl_amd")):
     sys.path.insert(0, p)
 
 SHAPES = [(100, 5), (100, 10), (4096, 5), (4096, 10)]
+WIDE_SHAPES = [(100, 16), (100, 24), (100, 30), (4096, 16), (4096, 24), (4096, 30)]  # --passes: past the whole chunk's limit
 DIMS = dict(input_dim=13, mlp1_dims=[150, 100], mlp2_dims=[100, 50], mlp3_dims=[150, 100, 100, 1], attention_dims=[100, 100, 1])
 
 
@@ -29,6 +33,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None, help="also append the lines to this file")
+    ap.add_argument("--passes", action="store_true", help="time the pass form (states_per_pass) instead")
     args = ap.parse_args()
     import torch
     from ebcsim import _capi
@@ -70,7 +75,38 @@ def main():
     dp_model = SarlModule(**DIMS).to(dev)
     dp_model.load_state_dict(sd)
     say("# ebc_sarl_net_grad_max_rows = %d" % native.net.grad_max_rows())
-    for B, R in SHAPES:
+    if args.passes:
+        say("# ebc_sarl_net_grad_max_rows_at(4, 2, 1) = %s" % ", ".join(str(native.net.grad_max_rows(S)) for S in (4, 2, 1)))
+        by_pass = {S: SarlTrainer(sd, device=dev, optimizer="sgd", lr=1e-3, native=True, states_per_pass=S) for S in (4, 2, 1, "auto")}
+    for B, R in SHAPES + WIDE_SHAPES if args.passes else []:
+        g = torch.Generator(device=dev).manual_seed(1000 * B + R)
+        rows = torch.randn((B, R, 13), generator=g, device=dev)
+        target = 0.5 * torch.randn((B,), generator=g, device=dev)
+        if (B, R) in SHAPES:
+            native.loss_and_grad(rows, target, grad_scale=2.0 / B)
+            whole = native.flat.grad.clone()
+            k0 = timed(lambda: native.loss_and_grad(rows, target, grad_scale=2.0 / B))
+            say("B %4d R %2d  ebc_sarl_grad, the whole chunk (states_per_pass unset) : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + k0))
+            for S in (4, 2, 1):
+                tr = by_pass[S]
+                tr.loss_and_grad(rows, target, grad_scale=2.0 / B)
+                same = bool(torch.equal(tr.flat.grad.view(torch.int32), whole.view(torch.int32)))
+                k = timed(lambda: tr.loss_and_grad(rows, target, grad_scale=2.0 / B))
+                say("B %4d R %2d  ebc_sarl_grad, states_per_pass = %d                       : %8.3f ms (%.3f .. %.3f), host clock %.3f ms; "
+                    "%.2f x the whole chunk; the same bytes: %s" % ((B, R, S) + k + (k[0] / k0[0], same)))
+            continue
+        tr = by_pass["auto"]
+
+        def bare():
+            for p in module.parameters():
+                p.grad = None
+            torch.nn.functional.mse_loss(module(rows), target).backward()
+        k = timed(lambda: tr.loss_and_grad(rows, target, grad_scale=2.0 / B))
+        a = timed(bare)
+        say("B %4d R %2d  ebc_sarl_grad, states_per_pass = auto (%d)                : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R, tr.passes.of(R)) + k))
+        say("B %4d R %2d  torch autograd of SarlModule (forward, MSE, backward)    : %8.3f ms (%.3f .. %.3f), host clock %.3f ms" % ((B, R) + a))
+        say("B %4d R %2d  autograd / kernel: %.2f x by events, %.2f x by the host clock" % (B, R, a[0] / k[0], a[3] / k[3]))
+    for B, R in [] if args.passes else SHAPES:
         g = torch.Generator(device=dev).manual_seed(1000 * B + R)
         rows = torch.randn((B, R, 13), generator=g, device=dev)
         target = 0.5 * torch.randn((B,), generator=g, device=dev)

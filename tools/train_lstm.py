@@ -65,6 +65,9 @@ def main():
     ap.add_argument("--cases", type=int, default=500, help="test cases of the evaluations")
     ap.add_argument("--gamma", type=float, default=None, help="default: [rl] gamma of the policy config")
     ap.add_argument("--autograd", action="store_true", help="torch autograd instead of the kernel (the comparison path)")
+    ap.add_argument("--states-per-pass", default=None, choices=["auto", "1", "2", "4"],
+                    help="the kernel runs a chunk's 4 states that many at a time, which takes more rows per state (the same bytes); "
+                         "auto: the largest that holds the scene's rows.  Default: the whole chunk at once")
     ap.add_argument("--interaction-module", default=None, choices=["true", "false"],
                     help="ValueNetwork2 (true) or ValueNetwork1 (false); default: [lstm_rl] with_interaction_module of the policy config")
     ap.add_argument("--out", default="lstm_model.pth")
@@ -129,7 +132,8 @@ def main():
     start = LstmModule(width, 6, dims["mlp2_dims"], hidden, dims["mlp1_dims"] if two else None)
     if args.weights:
         start.load_state_dict(torch.load(args.weights, map_location="cpu"), strict=True)
-    trainer = LstmTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd)
+    spp = args.states_per_pass if args.states_per_pass in (None, "auto") else int(args.states_per_pass)
+    trainer = LstmTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd, states_per_pass=spp)
     g = torch.Generator(device="cuda:0").manual_seed(args.seed)
     common = dict(il_learning_rate=args.il_lr, il_safety_space=args.safety_space, rl_learning_rate=args.rl_lr, steps_per_iteration=args.steps_per_iteration,
                   train_batches=args.train_batches, batch_size=args.batch_size, capacity=args.capacity, epsilon_start=args.epsilon_start,
