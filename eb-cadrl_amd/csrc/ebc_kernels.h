@@ -41,6 +41,10 @@ struct DevState {
   int E, N, S, G;
   int *n_humans;
   double *px, *py, *vx, *vy, *gx, *gy, *radius, *v_pref;
+  // [E][N] the fused ORCA step writes the humans' next positions here (every slot of every env: an unused slot carries
+  // its value over), the host then swaps them with px / py, like robot / robot_n: its ROWS role reads the positions the
+  // STATE role moves, and with two buffers STATE does not wait for it.  Every other kernel works on px / py in place.
+  double *px_n, *py_n;
   uint8_t *type;
   int *n_static;
   double *spx, *spy, *sradius;
@@ -60,6 +64,7 @@ struct DevState {
   uint4 *vel;                     // [E][N] ORCA -> STATE, ROWS: {vx bits, epoch, vy bits, epoch}, one 16-byte store
   unsigned long long *env_done;   // [E] ENV -> STATE: epoch << 32 | 1 + done
   unsigned *rows_loaded;          // [E] ROWS -> STATE: = epoch once the pre-step state AND the robot's next state are in registers
+                                  //     (STATE looks at it only before it RESTARTS an env: radius, type, static rows, n_humans, robot_n)
   unsigned *robot_ready;          // [E] ENV -> ROWS: = epoch once robot_n[e] holds this step's result
   unsigned *fault;                // [1] a poll gave up (protocol broken); ebc_synchronize reports it
   ScenePool pool;  // where auto-reset takes an env's next scene from
@@ -1013,7 +1018,8 @@ __global__ __launch_bounds__(EBC_WAVE) void step_kernel(EbcParams p_in, DevState
 //          takes the robot's next state (robot_n, after robot_ready) and the human's velocity (vel),
 //          emits the raw and the rotated row
 //   STATE  lane = human slot: takes vel and env_done, moves the humans, writes the state
-//          and float tile of the next step (or the restart scene)
+//          and float tile of the next step (or the restart scene, once ROWS has the old one: rows_loaded);
+//          the positions go to px_n / py_n, which the host swaps with px / py like robot / robot_n
 //
 // Everything in a step is local to an env, so the roles meet through per-env / per-human mailbox
 // words in HBM instead of a second launch: an env's rows and state are written as soon as ITS
@@ -1029,7 +1035,8 @@ __global__ __launch_bounds__(EBC_WAVE) void step_kernel(EbcParams p_in, DevState
 //
 // Liveness: consumers (ROWS, STATE) wait only for ENV / ORCA blocks, ALL of which have lower indices
 // than any ROWS / STATE block; the dispatcher starts workgroups in index order and producers wait
-// for nothing, so every wait ends.  A poll that exceeds EBC_SPIN_LIMIT gives up and raises
+// for nothing, so every wait ends.  (Before it restarts an env, STATE also waits for the env's ROWS block: a lower
+// index again, and ROWS waits only for ENV / ORCA.)  A poll that exceeds EBC_SPIN_LIMIT gives up and raises
 // DevState::fault rather than hang the device.
 struct StepGrid {
   unsigned env_blocks, orca_blocks, rows_blocks;  // 8 Q each (ebc_step_grid.h); then the STATE blocks (64 / N envs each)
@@ -1301,6 +1308,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     // every pre-step value this env's rows need AND the robot's next state are in registers: STATE may
     // overwrite the state, and (restart) robot_n
     if (env_ok && slot + stride >= R && first == 0) mailbox_put(s.rows_loaded + ee, epoch);
+    EBC_MARK(0);  // trace build: rows_loaded put; 1: velocities in; 2: rows stored
     const bool valid = human ? slot < n : slot - N < ns;
     const int row = human ? (valid ? slot : ns + slot) : (valid ? n + slot - N : slot);
     // obs_row + rotated_row_or_zeros (ebc_step_rules.h), restated: a slot emits its row as soon as it has it
@@ -1332,6 +1340,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     const bool moving = human && valid;
     if (env_ok && !moving) emit();
     const u32x4 v = velocity_wait(vbox, env_ok && human, epoch, s.fault);
+    EBC_MARK(1);
     if (env_ok && moving) {  // Agent.step (agent.py:202-211)
       double ax, ay;
       unpack_velocity(v, ax, ay);
@@ -1341,6 +1350,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
       ovy = ay;
       emit();
     }
+    EBC_MARK(2);
   }
 }
 
@@ -1390,28 +1400,26 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
   wave_sync();  // restart_robot
   EBC_MARK(0);
   // wait for this wave's humans (every ORCA group of these envs has then read the tile and the
-  // robot), for the envs' robot-side result, and for the ROWS waves to have read the old state
-  // (one loop for the three boxes: a poll is a memory round trip, three in a row were 2 us of the step)
+  // robot) and for the envs' robot-side result
+  // (one loop for the two boxes: a poll is a memory round trip, three in a row were 2 us of the step).
+  // NOT for the ROWS waves: the positions they read are not the ones written here (px_n / py_n).
   u32x4 v = {0u, 0u, 0u, 0u};
   unsigned d = 0;
   {
-    bool wv = m.env_ok, wd = m.env_ok, wr = m.env_ok && wait_rows;
+    bool wv = m.env_ok, wd = m.env_ok;
     for (unsigned spins = 0;; ++spins) {
       unsigned long long dw = 0;
-      unsigned r = epoch;
-      // the two small loads first; the 16-byte load's wait (inside load16_device) then covers all three
+      // the small load first; the 16-byte load's wait (inside load16_device) then covers both
       if (wd) dw = __hip_atomic_load(done_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if (wr) r = __hip_atomic_load(loaded_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (wv) v = load16_device(vbox);
       wv = wv && (v.y != epoch || v.w != epoch);
       if (wd && (unsigned)(dw >> 32) == epoch) {
         d = (unsigned)dw;
         wd = false;
       }
-      wr = wr && r != epoch;
-      if (!__any(wv || wd || wr)) break;
+      if (!__any(wv || wd)) break;
       if (spins > EBC_SPIN_LIMIT) {
-        if (wv || wd || wr) atomicOr(s.fault, 1u);
+        if (wv || wd) atomicOr(s.fault, 1u);
         break;
       }
       __builtin_amdgcn_s_sleep(EBC_POLL_SLEEP);
@@ -1420,6 +1428,19 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
   EBC_MARK(1);
   if (!m.env_ok) return;
   const bool restore = io.auto_reset && d == 2u;
+  // A restart overwrites what the ROWS wave of the env reads besides the positions (radius, type, static rows,
+  // n_humans, robot_n): only these lanes wait until it has them (1-2 % of the envs of a step).
+  if (wait_rows) {
+    bool wr = restore;
+    for (unsigned spins = 0; __any(wr); ++spins) {
+      if (wr) wr = __hip_atomic_load(loaded_box, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != epoch;
+      if (spins > EBC_SPIN_LIMIT) {
+        if (wr) atomicOr(s.fault, 1u);
+        break;
+      }
+      if (__any(wr)) __builtin_amdgcn_s_sleep(EBC_POLL_SLEEP);
+    }
+  }
   const double tnew = gtime + p.time_step;
   const int N = s.N, S = s.S;
   float4 *tile = s.tile + 2 * m.k;
@@ -1445,14 +1466,15 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
       const v4f t0 = {(float)h.px, (float)h.py, (float)ax, (float)ay}, t1 = {tile_rad, tile_max, prefx, prefy};
       // streaming stores: nothing reads these again in this launch, and what is not left dirty in the L2s is not
       // waiting for the write-back at the end of the launch (-0.2 us per step, profiles/r02_state_nt_ab.txt)
-      __builtin_nontemporal_store(h.px, s.px + m.k);
-      __builtin_nontemporal_store(h.py, s.py + m.k);
       __builtin_nontemporal_store(ax, s.vx + m.k);
       __builtin_nontemporal_store(ay, s.vy + m.k);
       if (arrived_now) __builtin_nontemporal_store(h.arrival, s.arrival + m.k);  // once per episode, not every step
       __builtin_nontemporal_store(t0, reinterpret_cast<v4f *>(tile));
       __builtin_nontemporal_store(t1, reinterpret_cast<v4f *>(tile + 1));
     }
+    // the next step's positions: the other pair of buffers, every slot (an unused one carries its value over)
+    __builtin_nontemporal_store(h.px, s.px_n + m.k);
+    __builtin_nontemporal_store(h.py, s.py_n + m.k);
     if (m.leader) s.time[m.ee] = tnew;  // the robot's next state is in robot_n already (ENV)
   } else {
     // a terminal env under auto-reset takes its next scene: every per-scene field (ragged human
@@ -1460,8 +1482,8 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
     const ScenePool &P = s.pool;
     // restart_human (ebc_step_rules.h), restated over the preloaded scene
     const bool live = m.i < pre.n_humans;
-    s.px[m.k] = live ? pre.px : 0.0;
-    s.py[m.k] = live ? pre.py : 0.0;
+    s.px_n[m.k] = live ? pre.px : 0.0;  // the buffers the next step reads (swapped by the host)
+    s.py_n[m.k] = live ? pre.py : 0.0;
     s.vx[m.k] = live ? pre.vx : 0.0;
     s.vy[m.k] = live ? pre.vy : 0.0;
     s.arrival[m.k] = 0.0;

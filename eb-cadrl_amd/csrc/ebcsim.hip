@@ -250,8 +250,13 @@ int launch_orca_step(Handle *h, const StepIO &io) {
   g.total = (unsigned)blocks;
   const int rc = with_group_size<kDevHumanGs>(
       h->orca_gs, [&](auto gs) { return launch_orca_step_gs<decltype(gs)::value>(h, io, (unsigned)blocks, g); });
-  // the launch leaves the robots' next state in robot_n: that is the current state from here on
-  if (rc == EBC_OK) std::swap(h->s.robot, h->s.robot_n);
+  // the launch leaves the robots' next state in robot_n and the humans' next positions in px_n / py_n: that is the
+  // current state from here on (every other kernel and entry point reads and writes robot, px and py)
+  if (rc == EBC_OK) {
+    std::swap(h->s.robot, h->s.robot_n);
+    std::swap(h->s.px, h->s.px_n);
+    std::swap(h->s.py, h->s.py_n);
+  }
   return rc;
 }
 
@@ -538,7 +543,7 @@ int ebc_create(int device_id, int n_envs, int max_humans, int max_static, const 
   const size_t EN = (size_t)n_envs * max_humans, ES = (size_t)n_envs * (max_static ? max_static : 1);
   int rc = EBC_OK;
 #define A_(field, cnt) if (rc == EBC_OK) rc = dev_alloc(h, &s.field, (cnt))
-  A_(n_humans, n_envs); A_(px, EN); A_(py, EN); A_(vx, EN); A_(vy, EN); A_(gx, EN); A_(gy, EN);
+  A_(n_humans, n_envs); A_(px, EN); A_(py, EN); A_(px_n, EN); A_(py_n, EN); A_(vx, EN); A_(vy, EN); A_(gx, EN); A_(gy, EN);
   A_(radius, EN); A_(v_pref, EN); A_(type, EN); A_(n_static, n_envs); A_(spx, ES); A_(spy, ES);
   A_(sradius, ES); A_(robot, (size_t)n_envs * 9); A_(robot_n, (size_t)n_envs * 9); A_(time, n_envs); A_(arrival, EN);
   A_(tile, EN * 2);

@@ -187,6 +187,16 @@ def report(np, name, rows, base):
         last = np.argsort(done_)[-6:]
         print("   the 6 that stored last (start, loads ready, mailboxes full, stored): " + " ".join(
             "(%.1f %.1f %.1f %.1f)" % (us(r0[q]), ready[q], woke[q], done_[q]) for q in last))
+    if name == "ROWS" and rows[:, 7].any():  # marks 0 (rows_loaded put), 1 (velocities in), 2 (rows stored)
+        c0 = rows[:, 2].astype(np.int64)
+        mk = rows[:, 5:8].astype(np.int64)
+        mhz = cyc / np.maximum(life, 1e-9)
+        at = lambda q: us(r0) + (mk[:, q] - c0) / mhz
+        put, vel, stored = at(0), at(1), at(2)
+        pct = lambda v: "%.1f / %.1f / %.1f" % (np.percentile(v, 10), np.percentile(v, 50), np.percentile(v, 90))
+        print("   on the launch's time axis, p10 / p50 / p90 us: rows_loaded put %s, velocities in %s, rows stored %s" % (
+            pct(put), pct(vel), pct(stored)))
+        print("   velocities in -> rows stored: %s us; last rows stored %.1f us" % (pct(stored - vel), stored.max()))
     if name == "ORCA" and rows[:, 5].any():
         c0 = rows[:, 2].astype(np.int64)
         marks = rows[:, 5:10].astype(np.int64) - c0[:, None]
