@@ -14,8 +14,8 @@
 //             from 0 and is stored ONCE into the chunk's partial.  A state that is not live is skipped by selection.
 //   dx        cadrl_dx: a thread owns (state, input k); the chain over the layer's units runs ascending from 0; W[k][.]
 //             are adjacent floats of the image, read 16 bytes at a time, the deltas 16-byte LDS reads.
-// The partials [chunks][packed floats] are then added by cadrl_grad_reduce: one thread per weight, chunks ascending, in
-// float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
+// The partials [chunks][packed floats] are then added by grad_reduce (ebc_grad_common.h): one thread per weight, chunks
+// ascending, in float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
 //
 // LDS, in floats: X0, SX [16][K0 padded]; A1, A2, A3 and D1, D2, D3 [16][units padded] (the deltas double as the scan's
 // activations); V [16 R]; 16 outputs, 16 seeds and four small int arrays.  48 KB at the reference widths with one row per
@@ -25,7 +25,7 @@
 
 #include <hip/hip_runtime.h>
 
-#include "ebc_cadrl_grad_rule.h"
+#include "ebc_grad_common.h"
 
 #define EBC_CADRL_GRAD_WAVES 4
 
@@ -261,35 +261,6 @@ __global__ __launch_bounds__(64 * EBC_CADRL_GRAD_WAVES) void cadrl_grad_kernel(c
   cadrl_dx(P + D.at[1], D.K[1], D.O[1], D.Op[1], L.Dl[1], D.Op[1], L.A[0], D.Op[0], L.Dl[0], D.Op[0], nc, L.LIVE, true);
   __syncthreads();
   cadrl_dw(part + D.at[0], D.K[0], D.O[0], D.Op[0], L.Dl[0], D.Op[0], L.X0, K0p, nc, L.LIVE);
-}
-
-// grad[i] = the float64 sum of the chunks' partials, chunks ascending, rounded once; several launches of the main kernel
-// (each with its own run of chunks) continue the float64 sums in acc64
-__global__ __launch_bounds__(256) void cadrl_grad_reduce(const float *__restrict__ partial, const double *__restrict__ loss_part,
-                                                         const long long *__restrict__ count_part, int chunks, size_t PF, int first,
-                                                         int last, double *acc64, float *grad, double *loss_sum, long long *count) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < PF) {
-    double s = first ? 0.0 : acc64[i];
-    for (int c = 0; c < chunks; ++c) s = s + (double)partial[(size_t)c * PF + i];
-    if (last) grad[i] = ebc_cadrl::canon((float)s);
-    else acc64[i] = s;
-  }
-  if (i == 0) {
-    double l = first ? 0.0 : acc64[PF];
-    long long n = first ? 0 : reinterpret_cast<long long *>(acc64)[PF + 1];
-    for (int c = 0; c < chunks; ++c) {
-      l = l + loss_part[c];
-      n += count_part[c];
-    }
-    if (last) {
-      *loss_sum = ebc_cadrl::canon(l);
-      *count = n;
-    } else {
-      acc64[PF] = l;
-      reinterpret_cast<long long *>(acc64)[PF + 1] = n;
-    }
-  }
 }
 
 }  // namespace ebc

@@ -36,7 +36,8 @@
 // What is shared and what is written twice.  The kernel compiles the scalar steps of this header (chain, grad_relu,
 // grad_relu_back, grad_diff, grad_loss, grad_value, grad_live, canon, min_rows, first_min_row, grad_dims, pad4).  The LOOPS
 // around them exist twice: serially here (grad_unit, grad_forward_row, grad_linear, grad_backward_state, grad_batch: the
-// host build) and in parallel in ebc_cadrl_grad.h (cadrl_layer, cadrl_dw, cadrl_dx, the chunk's loss, cadrl_grad_reduce).
+// host build) and in parallel in ebc_cadrl_grad.h (cadrl_layer, cadrl_dw, cadrl_dx, the chunk's loss) and ebc_grad_common.h
+// (grad_reduce).
 // Editing a loop here does not change the kernel: the two are held together by the byte comparison of
 // tests/test_cadrl_train_gpu.py alone, and a change of order must be made in both.
 //

@@ -29,6 +29,12 @@ hipError_t raise_dynamic_lds(Kernel *kernel, int device, size_t lds, size_t (&ra
   return err;
 }
 
+// a stream that is being captured into a HIP graph: the entries that allocate or copy outside the graph refuse it
+inline bool capturing(void *stream) {
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing((hipStream_t)stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
+}
+
 }  // namespace ebc_host
 
 #define HIP_TRY(x)                                                                                    \

@@ -4,8 +4,8 @@
 //
 // A workgroup of eight waves owns one chunk of EBC_LSTM_GRAD_CHUNK consecutive states; a state's R row slots lie side by
 // side (slot q = state * R + step; the slots at or past a state's n hold zeros in X and enter no sum).
-//   layer     lstmg_layer: a thread owns (a tile of 4 slots, unit u); the weights W[k][u] come from the packed image in
-//             global memory (L2; adjacent lanes read adjacent floats), the inputs are LDS broadcasts.
+//   layer     grad_layer (ebc_grad_common.h, as grad_dw and grad_dx): a thread owns (a tile of 4 slots, unit u); the weights
+//             W[k][u] come from the packed image in global memory (L2; adjacent lanes read adjacent floats), the inputs are LDS broadcasts.
 //   step      the recurrence, a step at a time for all states of the chunk that still have one.  Gates: a thread owns (gate
 //             row q, a pair of states) and walks the rule's chain over xi[t] and then h[t-1], w_ih[k][q] and w_hh[k][q]
 //             read once for the pair (adjacent lanes, adjacent floats).  Cell: a thread owns (state, unit).  What a step
@@ -13,13 +13,13 @@
 //             This is not the forward kernel's sequence-per-lane layout (ebc_lstm.h): a chunk has four sequences.
 //   back      per step from the last: a thread owns (state, unit) for the rule's cell_back (the gates become their deltas),
 //             then (state, unit k) for dh[k], the chain over all 4 H gate rows of w_hh[k][.] (contiguous in the image).
-//   dW, db    lstmg_dw / lstmg_cell_dw: a thread owns entries (k, u) of a layer; its chain runs over the chunk's live states
+//   dW, db    grad_dw / the cell's loop: a thread owns entries (k, u) of a layer; its chain runs over the chunk's live states
 //             ascending and a state's steps ascending from 0 and is stored ONCE into the chunk's partial.
-//   dx        lstmg_dx: a thread owns (slot, input k); the chain over the layer's units runs ascending from 0.  The result
+//   dx        grad_dx: a thread owns (slot, input k); the chain over the layer's units runs ascending from 0.  The result
 //             OVERWRITES the ReLU output it is masked by (mlp1's xi: the cell's input it is the gradient of): that activation
 //             was the input of this layer's dW, which has finished (a barrier lies between), and nothing else reads it.
-// The partials [chunks][packed floats] are then added by lstm_grad_reduce: one thread per weight, chunks ascending, in
-// float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
+// The partials [chunks][packed floats] are then added by grad_reduce (ebc_grad_common.h): one thread per weight, chunks
+// ascending, in float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
 //
 // LDS, in floats (lstm_grad_lds_floats): per slot X [T padded], with mlp1 A1, A2, A3, XI [units padded], the step's record
 // [4 H + 3 H padded]; per state the joint vector J, M1, M2, M3, dh, dc, the output, the seed, the loss and two ints; one
@@ -38,6 +38,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ebc_grad_common.h"
 #include "ebc_lstm_grad_rule.h"
 
 #define EBC_LSTM_GRAD_WAVES 8
@@ -112,95 +113,6 @@ __device__ __forceinline__ LstmGradLds lstm_grad_lds(float *p, const ebc_lstmg::
 
 constexpr int kLstmGradNT = 64 * EBC_LSTM_GRAD_WAVES;
 
-// out[q][u] for the slots q < nslots and every unit u of a layer W[k][Op] | bias[Op] on in[q][0 .. K): grad_unit's chain,
-// ReLU when asked
-template <bool RELU>
-__device__ __forceinline__ void lstmg_layer(const float *__restrict__ W, int K, int O, int Op, const float *in, int is, float *out, int os,
-                                            int nslots) {
-  constexpr int TR = 4;
-  const int tiles = (nslots + TR - 1) / TR;
-  for (int idx = threadIdx.x; idx < tiles * O; idx += kLstmGradNT) {
-    const int tile = idx / O, u = idx - tile * O, q0 = tile * TR;
-    const float *xr[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) xr[t] = in + (size_t)(q0 + t < nslots ? q0 + t : nslots - 1) * is;  // past the end: the last one, not stored
-    float acc[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) acc[t] = 0.0f;
-    for (int k = 0; k < K; ++k) {
-      const float w = W[(size_t)k * Op + u];
-#pragma unroll
-      for (int t = 0; t < TR; ++t) acc[t] = ebc_lstmg::chain(xr[t][k], w, acc[t]);
-    }
-    const float b = W[(size_t)K * Op + u];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) {
-      if (q0 + t >= nslots) continue;
-      const float y = acc[t] + b;
-      out[(size_t)(q0 + t) * os + u] = RELU ? ebc_lstmg::grad_relu(y) : y;
-    }
-  }
-}
-
-// a layer's dW and db into G (the layer's place in the chunk's partial, (K + 1) * Op floats) over the chunk's live states
-// s < nc ascending and, with per_row, their steps r < N[s] ascending: delta at delta + q * ds, the input at x + q * xs (q the
-// slot, or the state without per_row).  Pad entries get 0.  cont (a later pass of the chunk): the chain goes on from what
-// this thread stored into G in the pass before, not from 0.
-__device__ __forceinline__ void lstmg_dw(float *__restrict__ G, int K, int O, int Op, const float *delta, int ds, const float *x, int xs, int R,
-                                         int nc, const int *N, const int *live, bool per_row, bool cont) {
-  const int total = (K + 1) * Op;
-  for (int idx = threadIdx.x; idx < total; idx += kLstmGradNT) {
-    const int k = idx / Op, u = idx - k * Op;
-    float acc = 0.0f;
-    if (u < O) {
-      if (cont) acc = G[idx];
-      for (int s = 0; s < nc; ++s) {
-        if (!live[s]) continue;
-        const int n = per_row ? N[s] : 1, q0 = per_row ? s * R : s;
-        if (k < K) {
-          for (int r = 0; r < n; ++r) acc = ebc_lstmg::chain(delta[(q0 + r) * ds + u], x[(q0 + r) * xs + k], acc);
-        } else {
-          for (int r = 0; r < n; ++r) acc = acc + delta[(q0 + r) * ds + u];
-        }
-      }
-    }
-    G[idx] = acc;
-  }
-}
-
-// the chain over a layer's units u ascending of w[u] * d[u] from 0; vec: both are 16-byte aligned
-__device__ __forceinline__ float lstmg_dot(const float *__restrict__ w, const float *d, int O, bool vec) {
-  float acc = 0.0f;
-  int u = 0;
-  if (vec) {
-    for (; u + 4 <= O; u += 4) {
-      const float4 a = *reinterpret_cast<const float4 *>(w + u), b = *reinterpret_cast<const float4 *>(d + u);
-      acc = ebc_lstmg::chain(a.x, b.x, acc);
-      acc = ebc_lstmg::chain(a.y, b.y, acc);
-      acc = ebc_lstmg::chain(a.z, b.z, acc);
-      acc = ebc_lstmg::chain(a.w, b.w, acc);
-    }
-  }
-  for (; u < O; ++u) acc = ebc_lstmg::chain(w[u], d[u], acc);
-  return acc;
-}
-
-// act[q][k] = (RELU: relu_back(act[q][k], dx) else dx), dx the chain over the layer's units of W[k][u] * delta[q][u], for
-// the inputs k0 <= k < k1 (stored at act[q][k - k0]) and the live slots (per_row: q = s * R + r, r < N[s]; else q = s)
-template <bool RELU>
-__device__ __forceinline__ void lstmg_dx(const float *__restrict__ W, int k0, int k1, int O, int Op, const float *delta, int ds, float *act, int as,
-                                         int R, int nc, const int *N, const int *live, bool per_row, bool vec) {
-  const int nq = per_row ? nc * R : nc;
-  for (int idx = threadIdx.x; idx < nq * (k1 - k0); idx += kLstmGradNT) {
-    const int kk = idx / nq, q = idx - kk * nq, k = k0 + kk;
-    const int s = per_row ? q / R : q;
-    if (!live[s] || (per_row && q - s * R >= N[s])) continue;
-    const float dx = lstmg_dot(W + (size_t)k * Op, delta + (size_t)q * ds, O, vec);
-    float *o = act + (size_t)q * as + kk;
-    *o = RELU ? ebc_lstmg::grad_relu_back(*o, dx) : dx;
-  }
-}
-
 // PASSES false: the whole chunk at once.  true: a.SP states at a time (see "Passes" above).
 template <bool PASSES>
 __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__restrict__ P, const LstmGradLaunch a) {
@@ -229,26 +141,21 @@ __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__r
     const int nq = nc * R;
 
     // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
-    if (tid < SP) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
     if (tid < Hp) L.ZERO[tid] = 0.0f;
-    __syncthreads();
-    for (int i = tid; i < nq * T; i += NT) {
-      const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
-      L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
-    }
+    grad_load_rows<NT>(a, L, c0, nc, SP, T);
     int nmax = 0;
     for (int s = 0; s < nc; ++s) nmax = L.N[s] > nmax ? L.N[s] : nmax;
     __syncthreads();
 
     // ---- forward: mlp1
     if (D.two) {
-      lstmg_layer<true>(AT(L_M1A), T, D.O[L_M1A], O0, L.X, Tp, L.A1, O0, nq);
+      grad_layer<NT, true>(AT(L_M1A), T, 0, D.O[L_M1A], O0, L.X, Tp, nullptr, 0, R, L.A1, O0, nq);
       __syncthreads();
-      lstmg_layer<true>(AT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A1, O0, L.A2, O1, nq);
+      grad_layer<NT, true>(AT(L_M1B), D.K[L_M1B], 0, D.O[L_M1B], O1, L.A1, O0, nullptr, 0, R, L.A2, O1, nq);
       __syncthreads();
-      lstmg_layer<true>(AT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A2, O1, L.A3, O2, nq);
+      grad_layer<NT, true>(AT(L_M1C), D.K[L_M1C], 0, D.O[L_M1C], O2, L.A2, O1, nullptr, 0, R, L.A3, O2, nq);
       __syncthreads();
-      lstmg_layer<false>(AT(L_M1D), D.K[L_M1D], I, xis, L.A3, O2, L.XI, xis, nq);
+      grad_layer<NT, false>(AT(L_M1D), D.K[L_M1D], 0, I, xis, L.A3, O2, nullptr, 0, R, L.XI, xis, nq);
       __syncthreads();
     }
 
@@ -294,57 +201,33 @@ __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__r
     }
     __syncthreads();
     // ---- mlp
-    lstmg_layer<true>(AT(L_MA), S + H, D.O[L_MA], O4, L.J, Jp, L.M1, O4, nc);
+    grad_layer<NT, true>(AT(L_MA), S + H, 0, D.O[L_MA], O4, L.J, Jp, nullptr, 0, R, L.M1, O4, nc);
     __syncthreads();
-    lstmg_layer<true>(AT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M1, O4, L.M2, O5, nc);
+    grad_layer<NT, true>(AT(L_MB), D.K[L_MB], 0, D.O[L_MB], O5, L.M1, O4, nullptr, 0, R, L.M2, O5, nc);
     __syncthreads();
-    lstmg_layer<true>(AT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M2, O5, L.M3, O6, nc);
+    grad_layer<NT, true>(AT(L_MC), D.K[L_MC], 0, D.O[L_MC], O6, L.M2, O5, nullptr, 0, R, L.M3, O6, nc);
     __syncthreads();
-    lstmg_layer<false>(AT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.M3, O6, L.OUT, 1, nc);
+    grad_layer<NT, false>(AT(L_MD), D.K[L_MD], 0, 1, D.Op[L_MD], L.M3, O6, nullptr, 0, R, L.OUT, 1, nc);
     __syncthreads();
 
     // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
-    if (tid < SP) L.LIVE[tid] = 0;
-    if (tid < nc) {
-      const long long b = c0 + tid;
-      const float val = grad_value(L.OUT[tid], L.N[tid]);
-      if (a.value) a.value[b] = val;
-      const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
-      L.LIVE[tid] = live ? 1 : 0;
-      if (live) {
-        const float d = grad_diff(val, a.target[b]);
-        L.LOSS[tid] = grad_loss(d);
-        L.SEED[tid] = a.grad_scale * d;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double loss = cont ? a.loss_part[blockIdx.x] : 0.0;
-      long long count = cont ? a.count_part[blockIdx.x] : 0;
-      for (int s = 0; s < nc; ++s) {
-        if (!L.LIVE[s]) continue;
-        loss = loss + L.LOSS[s];
-        count += 1;
-      }
-      a.loss_part[blockIdx.x] = loss;
-      a.count_part[blockIdx.x] = count;
-    }
+    grad_seed(a, L, c0, nc, SP, cont);
 
     // ---- backward: mlp
-    lstmg_dw(GAT(L_MD), D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_MD), D.K[L_MD], 0, 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dx<true>(AT(L_MD), 0, D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, false);
+    grad_dx<NT, true>(AT(L_MD), 0, D.K[L_MD], 1, D.Op[L_MD], L.SEED, 1, L.M3, O6, R, nc, L.N, L.LIVE, false, false);
     __syncthreads();
-    lstmg_dw(GAT(L_MC), D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_MC), D.K[L_MC], 0, D.O[L_MC], O6, L.M3, O6, L.M2, O5, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dx<true>(AT(L_MC), 0, D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, true);
+    grad_dx<NT, true>(AT(L_MC), 0, D.K[L_MC], D.O[L_MC], O6, L.M3, O6, L.M2, O5, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    lstmg_dw(GAT(L_MB), D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_MB), D.K[L_MB], 0, D.O[L_MB], O5, L.M2, O5, L.M1, O4, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    lstmg_dx<true>(AT(L_MB), 0, D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, true);
+    grad_dx<NT, true>(AT(L_MB), 0, D.K[L_MB], D.O[L_MB], O5, L.M2, O5, L.M1, O4, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    lstmg_dw(GAT(L_MA), S + H, D.O[L_MA], O4, L.M1, O4, L.J, Jp, R, nc, L.N, L.LIVE, false, cont);
-    lstmg_dx<false>(AT(L_MA), S, S + H, D.O[L_MA], O4, L.M1, O4, L.DH, Hp, R, nc, L.N, L.LIVE, false, true);  // dh of the last step
+    grad_dw<NT>(GAT(L_MA), S + H, 0, D.O[L_MA], O4, L.M1, O4, L.J, Jp, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    grad_dx<NT, false>(AT(L_MA), S, S + H, D.O[L_MA], O4, L.M1, O4, L.DH, Hp, R, nc, L.N, L.LIVE, false, true);  // dh of the last step
     for (int i = tid; i < nc * H; i += NT) L.DC[(i / H) * Hp + (i % H)] = 0.0f;
     __syncthreads();
 
@@ -363,7 +246,7 @@ __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__r
       for (int idx = tid; idx < nc * H; idx += NT) {
         const int k = idx / nc, s = idx - k * nc;
         if (!L.LIVE[s] || t >= L.N[s]) continue;
-        L.DH[s * Hp + k] = lstmg_dot(Whh + (size_t)k * H4, L.REC + (size_t)(s * R + t) * RS, H4, true);
+        L.DH[s * Hp + k] = grad_dot(Whh + (size_t)k * H4, L.REC + (size_t)(s * R + t) * RS, H4, true);
       }
       __syncthreads();
     }
@@ -389,55 +272,26 @@ __global__ __launch_bounds__(kLstmGradNT) void lstm_grad_kernel(const float *__r
     if (D.two) {
       // ---- mlp1: xi becomes its delta (the cell's dW above has read it)
       __syncthreads();
-      lstmg_dx<false>(Wih, 0, I, H4, H4, L.REC, RS, L.XI, xis, R, nc, L.N, L.LIVE, true, true);
+      grad_dx<NT, false>(Wih, 0, I, H4, H4, L.REC, RS, L.XI, xis, R, nc, L.N, L.LIVE, true, true);
       __syncthreads();
-      lstmg_dw(GAT(L_M1D), D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, cont);
+      grad_dw<NT>(GAT(L_M1D), D.K[L_M1D], 0, I, xis, L.XI, xis, L.A3, O2, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
       __syncthreads();
-      lstmg_dx<true>(AT(L_M1D), 0, D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, true);
+      grad_dx<NT, true>(AT(L_M1D), 0, D.K[L_M1D], I, xis, L.XI, xis, L.A3, O2, R, nc, L.N, L.LIVE, true, true);
       __syncthreads();
-      lstmg_dw(GAT(L_M1C), D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, cont);
+      grad_dw<NT>(GAT(L_M1C), D.K[L_M1C], 0, D.O[L_M1C], O2, L.A3, O2, L.A2, O1, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
       __syncthreads();
-      lstmg_dx<true>(AT(L_M1C), 0, D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, true);
+      grad_dx<NT, true>(AT(L_M1C), 0, D.K[L_M1C], D.O[L_M1C], O2, L.A3, O2, L.A2, O1, R, nc, L.N, L.LIVE, true, true);
       __syncthreads();
-      lstmg_dw(GAT(L_M1B), D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, cont);
+      grad_dw<NT>(GAT(L_M1B), D.K[L_M1B], 0, D.O[L_M1B], O1, L.A2, O1, L.A1, O0, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
       __syncthreads();
-      lstmg_dx<true>(AT(L_M1B), 0, D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
+      grad_dx<NT, true>(AT(L_M1B), 0, D.K[L_M1B], D.O[L_M1B], O1, L.A2, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
       __syncthreads();
-      lstmg_dw(GAT(L_M1A), T, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, R, nc, L.N, L.LIVE, true, cont);
+      grad_dw<NT>(GAT(L_M1A), T, 0, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
     }
     if (PASSES) __syncthreads();  // the next pass's forward overwrites what this pass's dW reads
   } while (PASSES && (at += SP) < chunk_n);
 #undef AT
 #undef GAT
-}
-
-// grad[i] = the float64 sum of the chunks' partials, chunks ascending, rounded once; several launches of the main kernel
-// (each with its own run of chunks) continue the float64 sums in acc64
-__global__ __launch_bounds__(256) void lstm_grad_reduce(const float *__restrict__ partial, const double *__restrict__ loss_part,
-                                                        const long long *__restrict__ count_part, int chunks, size_t PF, int first,
-                                                        int last, double *acc64, float *grad, double *loss_sum, long long *count) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < PF) {
-    double s = first ? 0.0 : acc64[i];
-    for (int c = 0; c < chunks; ++c) s = s + (double)partial[(size_t)c * PF + i];
-    if (last) grad[i] = ebc_lstmg::canon((float)s);
-    else acc64[i] = s;
-  }
-  if (i == 0) {
-    double l = first ? 0.0 : acc64[PF];
-    long long n = first ? 0 : reinterpret_cast<long long *>(acc64)[PF + 1];
-    for (int c = 0; c < chunks; ++c) {
-      l = l + loss_part[c];
-      n += count_part[c];
-    }
-    if (last) {
-      *loss_sum = ebc_lstmg::canon(l);
-      *count = n;
-    } else {
-      acc64[PF] = l;
-      reinterpret_cast<long long *>(acc64)[PF + 1] = n;
-    }
-  }
 }
 
 }  // namespace ebc

@@ -12,8 +12,8 @@
 //             ascending and CONTINUES the chunk's partial in global memory: the same thread owns the same entries in
 //             every group, reads what it wrote itself and stores it back.  A row of an env with w_e = 0 is skipped by a
 //             (workgroup-uniform) selection, never multiplied by 0.
-// The partials [chunks][packed_floats] are then added by sail_grad_reduce: one thread per weight, chunks ascending, in
-// float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
+// The partials [chunks][packed_floats] are then added by grad_reduce<false> (ebc_grad_common.h): one thread per weight, chunks
+// ascending, in float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
 //
 // LDS, in floats (rows = G * N, KX = max(4 N, 64)): X [rows][KX]; A1, A2, CAT, EMB, P1, FP, Q1 [rows][64] the layers'
 // outputs; D0, D1 [rows][64] the deltas' ping-pong; per row the frame [4], logit, score, dscore, dlogit and the live flag;
@@ -24,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "ebc_sail.h"
+#include "ebc_grad_common.h"
 #include "ebc_sail_grad_rule.h"
 
 #define EBC_SAIL_GRAD_WAVES 8
@@ -369,35 +370,6 @@ __global__ __launch_bounds__(64 * EBC_SAIL_GRAD_WAVES) void sail_grad_kernel(con
   if (threadIdx.x == 0) {
     a.loss_part[blockIdx.x] = *loss;
     a.count_part[blockIdx.x] = *count;
-  }
-}
-
-// grad[i] = the float64 sum of the chunks' partials, chunks ascending, rounded once; several launches of the main kernel
-// (each with its own run of chunks) continue the float64 sums in acc64
-__global__ __launch_bounds__(256) void sail_grad_reduce(const float *__restrict__ partial, const double *__restrict__ loss_part,
-                                                        const long long *__restrict__ count_part, int chunks, size_t PF, int first,
-                                                        int last, double *acc64, float *grad, double *loss_sum, long long *count) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < PF) {
-    double s = first ? 0.0 : acc64[i];
-    for (int c = 0; c < chunks; ++c) s = s + (double)partial[(size_t)c * PF + i];
-    if (last) grad[i] = (float)s;
-    else acc64[i] = s;
-  }
-  if (i == 0) {
-    double l = first ? 0.0 : acc64[PF];
-    long long n = first ? 0 : reinterpret_cast<long long *>(acc64)[PF + 1];
-    for (int c = 0; c < chunks; ++c) {
-      l = l + loss_part[c];
-      n += count_part[c];
-    }
-    if (last) {
-      *loss_sum = l;
-      *count = n;
-    } else {
-      acc64[PF] = l;
-      reinterpret_cast<long long *>(acc64)[PF + 1] = n;
-    }
   }
 }
 

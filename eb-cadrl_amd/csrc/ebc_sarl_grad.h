@@ -4,17 +4,17 @@
 //
 // A workgroup of eight waves owns one chunk of EBC_SARL_GRAD_CHUNK consecutive states; a state's R row slots lie side by
 // side (slot q = state * R + row; the slots at or past a state's n hold zeros in X and enter no sum).
-//   layer     sarl_layer: a thread owns (a tile of 4 slots, unit u); the weights W[k][u] come from the packed image in
-//             global memory (L2; adjacent lanes read adjacent floats), the inputs are LDS broadcasts.  Attention's layer 0
+//   layer     grad_layer (ebc_grad_common.h, as grad_dw and grad_dx): a thread owns (a tile of 4 slots, unit u); the weights
+//             W[k][u] come from the packed image in global memory (L2; adjacent lanes read adjacent floats), the inputs are LDS broadcasts.  Attention's layer 0
 //             reads its second half (the mean) per state.
 //   glue      the mean, the softmax (a thread per state, rows ascending), the weighted sum: the rule's chains as written.
-//   dW, db    sarl_dw: a thread owns entries (k, u) of a layer; its chain runs over the chunk's live states ascending and
+//   dW, db    grad_dw: a thread owns entries (k, u) of a layer; its chain runs over the chunk's live states ascending and
 //             a state's rows ascending from 0 and is stored ONCE into the chunk's partial.
-//   dx        sarl_dx: a thread owns (slot, input k); the chain over the layer's units runs ascending from 0.  The result
+//   dx        grad_dx: a thread owns (slot, input k); the chain over the layer's units runs ascending from 0.  The result
 //             OVERWRITES the ReLU output it is masked by: that activation was the input of this layer's dW, which has
 //             finished (a barrier lies between), and nothing else reads it.
-// The partials [chunks][packed floats] are then added by sarl_grad_reduce: one thread per weight, chunks ascending, in
-// float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
+// The partials [chunks][packed floats] are then added by grad_reduce (ebc_grad_common.h): one thread per weight, chunks
+// ascending, in float64, rounded once.  No atomics, no polling: which workgroup runs a chunk, and when, cannot reach a sum.
 //
 // LDS, in floats (sarl_grad_lds_floats): per slot X [T padded], A1, H1, B1, FT, C1, C2 [units padded], the score (later its
 // delta) and the weight; per state the mean G (later the mean's delta), the joint vector J, its delta DWF, M1, M2, M3,
@@ -31,6 +31,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "ebc_grad_common.h"
 #include "ebc_sarl_grad_rule.h"
 
 #define EBC_SARL_GRAD_WAVES 8
@@ -105,106 +106,10 @@ __device__ __forceinline__ SarlGradLds sarl_grad_lds(float *p, const ebc_sarl::G
 
 constexpr int kSarlNT = 64 * EBC_SARL_GRAD_WAVES;
 
-// out[q][u] for the slots q < nslots and every unit u of a layer W[k][Op] | bias[Op] with K1 + K2 inputs: the first K1 from
-// in[q][.], the other K2 (attention's layer 0: the mean) from in2[q / R][.]; grad_unit's chain, ReLU when asked
-template <bool RELU>
-__device__ __forceinline__ void sarl_layer(const float *__restrict__ W, int K1, int K2, int O, int Op, const float *in, int is, const float *in2,
-                                           int i2s, int R, float *out, int os, int nslots) {
-  constexpr int TR = 4;
-  const int tiles = (nslots + TR - 1) / TR;
-  for (int idx = threadIdx.x; idx < tiles * O; idx += kSarlNT) {
-    const int tile = idx / O, u = idx - tile * O, q0 = tile * TR;
-    const float *xr[TR], *x2[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) {
-      const int q = q0 + t < nslots ? q0 + t : nslots - 1;  // slots past the end: the last one, not stored
-      xr[t] = in + (size_t)q * is;
-      x2[t] = K2 ? in2 + (size_t)(q / R) * i2s : in;
-    }
-    float acc[TR];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) acc[t] = 0.0f;
-    for (int k = 0; k < K1; ++k) {
-      const float w = W[(size_t)k * Op + u];
-#pragma unroll
-      for (int t = 0; t < TR; ++t) acc[t] = ebc_sarl::chain(xr[t][k], w, acc[t]);
-    }
-    for (int k = 0; k < K2; ++k) {
-      const float w = W[(size_t)(K1 + k) * Op + u];
-#pragma unroll
-      for (int t = 0; t < TR; ++t) acc[t] = ebc_sarl::chain(x2[t][k], w, acc[t]);
-    }
-    const float b = W[(size_t)(K1 + K2) * Op + u];
-#pragma unroll
-    for (int t = 0; t < TR; ++t) {
-      if (q0 + t >= nslots) continue;
-      const float y = acc[t] + b;
-      out[(size_t)(q0 + t) * os + u] = RELU ? ebc_sarl::grad_relu(y) : y;
-    }
-  }
-}
-
-// a layer's dW and db into G (the layer's place in the chunk's partial, (K1 + K2 + 1) * Op floats) over the chunk's live
-// states s < nc ascending and, with per_row, their rows r < N[s] ascending: delta at delta + q * ds, the input at x + q * xs
-// (q the slot, or the state without per_row), inputs K1 .. of the state's x2 + s * x2s.  Pad entries get 0.  cont (a later
-// pass of the chunk): the chain goes on from what this thread stored into G in the pass before, not from 0.
-__device__ __forceinline__ void sarl_dw(float *__restrict__ G, int K1, int K2, int O, int Op, const float *delta, int ds, const float *x, int xs,
-                                        const float *x2, int x2s, int R, int nc, const int *N, const int *live, bool per_row, bool cont) {
-  const int K = K1 + K2, total = (K + 1) * Op;
-  for (int idx = threadIdx.x; idx < total; idx += kSarlNT) {
-    const int k = idx / Op, u = idx - k * Op;
-    float acc = 0.0f;
-    if (u < O) {
-      if (cont) acc = G[idx];
-      for (int s = 0; s < nc; ++s) {
-        if (!live[s]) continue;
-        const int n = per_row ? N[s] : 1, q0 = per_row ? s * R : s;
-        if (k < K1) {
-          for (int r = 0; r < n; ++r) acc = ebc_sarl::chain(delta[(q0 + r) * ds + u], x[(q0 + r) * xs + k], acc);
-        } else if (k < K) {
-          const float xv = x2[s * x2s + (k - K1)];
-          for (int r = 0; r < n; ++r) acc = ebc_sarl::chain(delta[(q0 + r) * ds + u], xv, acc);
-        } else {
-          for (int r = 0; r < n; ++r) acc = acc + delta[(q0 + r) * ds + u];
-        }
-      }
-    }
-    G[idx] = acc;
-  }
-}
-
-// the chain over a layer's units u ascending of w[u] * d[u] from 0; vec: both are 16-byte aligned
-__device__ __forceinline__ float sarl_dot(const float *__restrict__ w, const float *d, int O, bool vec) {
-  float acc = 0.0f;
-  int u = 0;
-  if (vec) {
-    for (; u + 4 <= O; u += 4) {
-      const float4 a = *reinterpret_cast<const float4 *>(w + u), b = *reinterpret_cast<const float4 *>(d + u);
-      acc = ebc_sarl::chain(a.x, b.x, acc);
-      acc = ebc_sarl::chain(a.y, b.y, acc);
-      acc = ebc_sarl::chain(a.z, b.z, acc);
-      acc = ebc_sarl::chain(a.w, b.w, acc);
-    }
-  }
-  for (; u < O; ++u) acc = ebc_sarl::chain(w[u], d[u], acc);
-  return acc;
-}
-
-// act[q][k] = (RELU: relu_back(act[q][k], dx) else dx), dx the chain over the layer's units of W[k][u] * delta[q][u], for
-// the inputs k0 <= k < k1 (stored at act[q][k - k0]) and the live slots (per_row: q = s * R + r, r < N[s]; else q = s)
-template <bool RELU>
-__device__ __forceinline__ void sarl_dx(const float *__restrict__ W, int k0, int k1, int O, int Op, const float *delta, int ds, float *act, int as,
-                                        int R, int nc, const int *N, const int *live, bool per_row, bool vec) {
-  const int nq = per_row ? nc * R : nc;
-  for (int idx = threadIdx.x; idx < nq * (k1 - k0); idx += kSarlNT) {
-    const int kk = idx / nq, q = idx - kk * nq, k = k0 + kk;
-    const int s = per_row ? q / R : q;
-    if (!live[s] || (per_row && q - s * R >= N[s])) continue;
-    const float dx = sarl_dot(W + (size_t)k * Op, delta + (size_t)q * ds, O, vec);
-    float *o = act + (size_t)q * as + kk;
-    *o = RELU ? ebc_sarl::grad_relu_back(*o, dx) : dx;
-  }
-}
+// instantiated here, ahead of the two kernels, so that the unit's code object lays its kernels out as it did when the
+// reduction was this header's own: behind them it cost the default call 0.3 % at B = 4096 (profiles/grad_refactor.txt)
+template __global__ void grad_reduce<true>(const float *__restrict__, const double *__restrict__, const long long *__restrict__, int, size_t, int, int,
+                                           double *, float *, double *, long long *);
 
 // PASSES false: the whole chunk at once.  true: a.SP states at a time (see "Passes" above).
 template <bool PASSES>
@@ -234,20 +139,15 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
     const int nq = nc * R;
 
     // ---- the states' row counts; the rows (zeros in the slots a state does not have: those are never read from memory)
-    if (tid < SP) L.N[tid] = tid < nc ? clamp_rows(a.n_valid ? a.n_valid[c0 + tid] : (long long)R, R) : 0;
-    __syncthreads();
-    for (int i = tid; i < nq * T; i += NT) {
-      const int q = i / T, k = i - q * T, s = q / R, r = q - s * R;
-      L.X[q * Tp + k] = r < L.N[s] ? a.rows[((size_t)(c0 + s) * R + r) * T + k] : 0.0f;
-    }
+    grad_load_rows<NT>(a, L, c0, nc, SP, T);
     __syncthreads();
 
     // ---- forward: mlp1, mlp2
-    sarl_layer<true>(AT(L_M1A), T, 0, D.O[L_M1A], O0, L.X, Tp, nullptr, 0, R, L.A1, O0, nq);
+    grad_layer<NT, true>(AT(L_M1A), T, 0, D.O[L_M1A], O0, L.X, Tp, nullptr, 0, R, L.A1, O0, nq);
     __syncthreads();
-    sarl_layer<true>(AT(L_M1B), D.K[L_M1B], 0, H, O1, L.A1, O0, nullptr, 0, R, L.H1, O1, nq);
+    grad_layer<NT, true>(AT(L_M1B), D.K[L_M1B], 0, H, O1, L.A1, O0, nullptr, 0, R, L.H1, O1, nq);
     __syncthreads();
-    sarl_layer<true>(AT(L_M2A), H, 0, D.O[L_M2A], O2, L.H1, O1, nullptr, 0, R, L.B1, O2, nq);
+    grad_layer<NT, true>(AT(L_M2A), H, 0, D.O[L_M2A], O2, L.H1, O1, nullptr, 0, R, L.B1, O2, nq);
     if (D.global)
       for (int i = tid; i < nc * H; i += NT) {
         const int s = i / H, k = i - s * H, n = L.N[s];
@@ -257,13 +157,13 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
         L.G[s * O1 + k] = over_rows(acc, n);
       }
     __syncthreads();
-    sarl_layer<false>(AT(L_M2B), D.K[L_M2B], 0, F, O3, L.B1, O2, nullptr, 0, R, L.FT, O3, nq);
+    grad_layer<NT, false>(AT(L_M2B), D.K[L_M2B], 0, F, O3, L.B1, O2, nullptr, 0, R, L.FT, O3, nq);
     // ---- attention
-    sarl_layer<true>(AT(L_ATA), H, KG, D.O[L_ATA], O4, L.H1, O1, L.G, O1, R, L.C1, O4, nq);
+    grad_layer<NT, true>(AT(L_ATA), H, KG, D.O[L_ATA], O4, L.H1, O1, L.G, O1, R, L.C1, O4, nq);
     __syncthreads();
-    sarl_layer<true>(AT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C1, O4, nullptr, 0, R, L.C2, O5, nq);
+    grad_layer<NT, true>(AT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C1, O4, nullptr, 0, R, L.C2, O5, nq);
     __syncthreads();
-    sarl_layer<false>(AT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.C2, O5, nullptr, 0, R, L.SC, 1, nq);
+    grad_layer<NT, false>(AT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.C2, O5, nullptr, 0, R, L.SC, 1, nq);
     __syncthreads();
     if (tid < nc) {
       const int n = L.N[tid], q0 = tid * R;
@@ -292,58 +192,34 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
     }
     __syncthreads();
     // ---- mlp3
-    sarl_layer<true>(AT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.J, Jp, nullptr, 0, 1, L.M1, O7, nc);
+    grad_layer<NT, true>(AT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.J, Jp, nullptr, 0, 1, L.M1, O7, nc);
     __syncthreads();
-    sarl_layer<true>(AT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M1, O7, nullptr, 0, 1, L.M2, O8, nc);
+    grad_layer<NT, true>(AT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M1, O7, nullptr, 0, 1, L.M2, O8, nc);
     __syncthreads();
-    sarl_layer<true>(AT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M2, O8, nullptr, 0, 1, L.M3, O9, nc);
+    grad_layer<NT, true>(AT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M2, O8, nullptr, 0, 1, L.M3, O9, nc);
     __syncthreads();
-    sarl_layer<false>(AT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.M3, O9, nullptr, 0, 1, L.OUT, 1, nc);
+    grad_layer<NT, false>(AT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.M3, O9, nullptr, 0, 1, L.OUT, 1, nc);
     __syncthreads();
 
     // ---- the values and the seeds, a thread per state; the chunk's loss in state order: thread 0's
-    if (tid < SP) L.LIVE[tid] = 0;
-    if (tid < nc) {
-      const long long b = c0 + tid;
-      const float val = grad_value(L.OUT[tid], L.N[tid]);
-      if (a.value) a.value[b] = val;
-      const bool live = grad_live(!a.mask || a.mask[b] != 0, L.N[tid]);
-      L.LIVE[tid] = live ? 1 : 0;
-      if (live) {
-        const float d = grad_diff(val, a.target[b]);
-        L.LOSS[tid] = grad_loss(d);
-        L.SEED[tid] = a.grad_scale * d;
-      }
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double loss = cont ? a.loss_part[blockIdx.x] : 0.0;
-      long long count = cont ? a.count_part[blockIdx.x] : 0;
-      for (int s = 0; s < nc; ++s) {
-        if (!L.LIVE[s]) continue;
-        loss = loss + L.LOSS[s];
-        count += 1;
-      }
-      a.loss_part[blockIdx.x] = loss;
-      a.count_part[blockIdx.x] = count;
-    }
+    grad_seed(a, L, c0, nc, SP, cont);
 
     // ---- backward: mlp3
-    sarl_dw(GAT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_M3D), D.K[L_M3D], 0, 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_M3D), 0, D.K[L_M3D], 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, R, nc, L.N, L.LIVE, false, false);
+    grad_dx<NT, true>(AT(L_M3D), 0, D.K[L_M3D], 1, D.Op[L_M3D], L.SEED, 1, L.M3, O9, R, nc, L.N, L.LIVE, false, false);
     __syncthreads();
-    sarl_dw(GAT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M3, O9, L.M2, O8, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_M3C), D.K[L_M3C], 0, D.O[L_M3C], O9, L.M3, O9, L.M2, O8, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_M3C), 0, D.K[L_M3C], D.O[L_M3C], O9, L.M3, O9, L.M2, O8, R, nc, L.N, L.LIVE, false, true);
+    grad_dx<NT, true>(AT(L_M3C), 0, D.K[L_M3C], D.O[L_M3C], O9, L.M3, O9, L.M2, O8, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    sarl_dw(GAT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M2, O8, L.M1, O7, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_M3B), D.K[L_M3B], 0, D.O[L_M3B], O8, L.M2, O8, L.M1, O7, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_M3B), 0, D.K[L_M3B], D.O[L_M3B], O8, L.M2, O8, L.M1, O7, R, nc, L.N, L.LIVE, false, true);
+    grad_dx<NT, true>(AT(L_M3B), 0, D.K[L_M3B], D.O[L_M3B], O8, L.M2, O8, L.M1, O7, R, nc, L.N, L.LIVE, false, true);
     __syncthreads();
-    sarl_dw(GAT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.M1, O7, L.J, Jp, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
+    grad_dw<NT>(GAT(L_M3A), S + F, 0, D.O[L_M3A], O7, L.M1, O7, L.J, Jp, nullptr, 0, R, nc, L.N, L.LIVE, false, cont);
     __syncthreads();
-    sarl_dx<false>(AT(L_M3A), S, S + F, D.O[L_M3A], O7, L.M1, O7, L.DWF, O3, R, nc, L.N, L.LIVE, false, true);  // dwf; J keeps wf
+    grad_dx<NT, false>(AT(L_M3A), S, S + F, D.O[L_M3A], O7, L.M1, O7, L.DWF, O3, R, nc, L.N, L.LIVE, false, true);  // dwf; J keeps wf
     __syncthreads();
 
     // ---- the weighted sum and the softmax
@@ -369,18 +245,18 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
     __syncthreads();
 
     // ---- mlp2's last layer and attention's last layer
-    sarl_dw(GAT(L_M2B), D.K[L_M2B], 0, F, O3, L.FT, O3, L.B1, O2, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
-    sarl_dw(GAT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_M2B), D.K[L_M2B], 0, F, O3, L.FT, O3, L.B1, O2, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_ATC), D.K[L_ATC], 0, 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_M2B), 0, D.K[L_M2B], F, O3, L.FT, O3, L.B1, O2, R, nc, L.N, L.LIVE, true, true);
-    sarl_dx<true>(AT(L_ATC), 0, D.K[L_ATC], 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, R, nc, L.N, L.LIVE, true, false);
+    grad_dx<NT, true>(AT(L_M2B), 0, D.K[L_M2B], F, O3, L.FT, O3, L.B1, O2, R, nc, L.N, L.LIVE, true, true);
+    grad_dx<NT, true>(AT(L_ATC), 0, D.K[L_ATC], 1, D.Op[L_ATC], L.SC, 1, L.C2, O5, R, nc, L.N, L.LIVE, true, false);
     __syncthreads();
-    sarl_dw(GAT(L_M2A), H, 0, D.O[L_M2A], O2, L.B1, O2, L.H1, O1, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
-    sarl_dw(GAT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C2, O5, L.C1, O4, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_M2A), H, 0, D.O[L_M2A], O2, L.B1, O2, L.H1, O1, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_ATB), D.K[L_ATB], 0, D.O[L_ATB], O5, L.C2, O5, L.C1, O4, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_ATB), 0, D.K[L_ATB], D.O[L_ATB], O5, L.C2, O5, L.C1, O4, R, nc, L.N, L.LIVE, true, true);
+    grad_dx<NT, true>(AT(L_ATB), 0, D.K[L_ATB], D.O[L_ATB], O5, L.C2, O5, L.C1, O4, R, nc, L.N, L.LIVE, true, true);
     __syncthreads();
-    sarl_dw(GAT(L_ATA), H, KG, D.O[L_ATA], O4, L.C1, O4, L.H1, O1, L.G, O1, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_ATA), H, KG, D.O[L_ATA], O4, L.C1, O4, L.H1, O1, L.G, O1, R, nc, L.N, L.LIVE, true, cont);
     __syncthreads();
 
     // ---- h1: the mean's delta (into G), then mlp2's layer 0 + attention's layer 0 + the mean
@@ -389,7 +265,7 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
         const int k = i / nc, s = i - k * nc, n = L.N[s];
         if (!L.LIVE[s]) continue;
         float dg = 0.0f;
-        for (int r = 0; r < n; ++r) dg = dg + sarl_dot(AT(L_ATA) + (size_t)(H + k) * O4, L.C1 + (size_t)(s * R + r) * O4, D.O[L_ATA], true);
+        for (int r = 0; r < n; ++r) dg = dg + grad_dot(AT(L_ATA) + (size_t)(H + k) * O4, L.C1 + (size_t)(s * R + r) * O4, D.O[L_ATA], true);
         L.G[s * O1 + k] = over_rows(dg, n);
       }
       __syncthreads();
@@ -397,52 +273,23 @@ __global__ __launch_bounds__(kSarlNT) void sarl_grad_kernel(const float *__restr
     for (int i = tid; i < nq * H; i += NT) {
       const int k = i / nq, q = i - k * nq, s = q / R;
       if (!L.LIVE[s] || q - s * R >= L.N[s]) continue;
-      const float d2 = sarl_dot(AT(L_M2A) + (size_t)k * O2, L.B1 + (size_t)q * O2, D.O[L_M2A], true);
-      const float d4 = sarl_dot(AT(L_ATA) + (size_t)k * O4, L.C1 + (size_t)q * O4, D.O[L_ATA], true);
+      const float d2 = grad_dot(AT(L_M2A) + (size_t)k * O2, L.B1 + (size_t)q * O2, D.O[L_M2A], true);
+      const float d4 = grad_dot(AT(L_ATA) + (size_t)k * O4, L.C1 + (size_t)q * O4, D.O[L_ATA], true);
       float *o = L.H1 + (size_t)q * O1 + k;
       *o = h1_back(*o, d2, d4, D.global ? L.G[s * O1 + k] : 0.0f, D.global);
     }
     __syncthreads();
 
     // ---- mlp1
-    sarl_dw(GAT(L_M1B), D.K[L_M1B], 0, H, O1, L.H1, O1, L.A1, O0, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_M1B), D.K[L_M1B], 0, H, O1, L.H1, O1, L.A1, O0, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
     __syncthreads();
-    sarl_dx<true>(AT(L_M1B), 0, D.K[L_M1B], H, O1, L.H1, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
+    grad_dx<NT, true>(AT(L_M1B), 0, D.K[L_M1B], H, O1, L.H1, O1, L.A1, O0, R, nc, L.N, L.LIVE, true, true);
     __syncthreads();
-    sarl_dw(GAT(L_M1A), T, 0, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
+    grad_dw<NT>(GAT(L_M1A), T, 0, D.O[L_M1A], O0, L.A1, O0, L.X, Tp, nullptr, 0, R, nc, L.N, L.LIVE, true, cont);
     if (PASSES) __syncthreads();  // the next pass's forward overwrites what this dW reads
   } while (PASSES && (at += SP) < chunk_n);
 #undef AT
 #undef GAT
-}
-
-// grad[i] = the float64 sum of the chunks' partials, chunks ascending, rounded once; several launches of the main kernel
-// (each with its own run of chunks) continue the float64 sums in acc64
-__global__ __launch_bounds__(256) void sarl_grad_reduce(const float *__restrict__ partial, const double *__restrict__ loss_part,
-                                                        const long long *__restrict__ count_part, int chunks, size_t PF, int first,
-                                                        int last, double *acc64, float *grad, double *loss_sum, long long *count) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < PF) {
-    double s = first ? 0.0 : acc64[i];
-    for (int c = 0; c < chunks; ++c) s = s + (double)partial[(size_t)c * PF + i];
-    if (last) grad[i] = ebc_sarl::canon((float)s);
-    else acc64[i] = s;
-  }
-  if (i == 0) {
-    double l = first ? 0.0 : acc64[PF];
-    long long n = first ? 0 : reinterpret_cast<long long *>(acc64)[PF + 1];
-    for (int c = 0; c < chunks; ++c) {
-      l = l + loss_part[c];
-      n += count_part[c];
-    }
-    if (last) {
-      *loss_sum = ebc_sarl::canon(l);
-      *count = n;
-    } else {
-      acc64[PF] = l;
-      reinterpret_cast<long long *>(acc64)[PF + 1] = n;
-    }
-  }
 }
 
 }  // namespace ebc

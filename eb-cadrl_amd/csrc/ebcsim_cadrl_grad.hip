@@ -7,7 +7,7 @@
 #include <vector>
 
 #include "ebc_cadrl_grad.h"
-#include "ebc_host.h"
+#include "ebc_grad_host.h"
 
 namespace {
 
@@ -15,18 +15,9 @@ using ebc_host::fail;
 
 constexpr int kMaxChunksPerLaunch = 1024;  // 1024 chunks of partials (114 MB at the reference widths) before the float64 sums take over
 
-struct CadrlNet {
-  int device = 0;
+struct CadrlNet : ebc_host::GradNet {
   ebc_cadrl::GradDims D;
-  float *P = nullptr;        // the packed image
-  void *scratch = nullptr;   // float64 sums | chunk losses | chunk counts | chunk partials
-  size_t scratch_bytes = 0;
 };
-
-bool capturing(void *stream) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing((hipStream_t)stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-}
 
 }  // namespace
 
@@ -52,49 +43,21 @@ extern "C" int ebc_cadrl_net_create(const EbcCadrlNetWeights *weights, int devic
   n->D = ebc_cadrl::grad_dims(weights->widths);
   std::vector<float> image(n->D.floats);
   ebc_cadrl::grad_pack(n->D, weights->weight, weights->bias, image.data());
-  hipError_t err = hipMalloc(&n->P, image.size() * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpy(n->P, image.data(), image.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err != hipSuccess) {
-    if (n->P) (void)hipFree(n->P);
-    delete n;
-    return fail(EBC_ERR_DEVICE, std::string("ebc_cadrl_net_create: ") + hipGetErrorString(err));
-  }
-  *net_out = n;
-  return EBC_OK;
+  return ebc_host::grad_net_upload(n, image, "ebc_cadrl_net_create", net_out);
 }
 
-extern "C" int ebc_cadrl_net_destroy(void *net) {
-  if (!net) return EBC_OK;
-  CadrlNet *n = static_cast<CadrlNet *>(net);
-  (void)hipSetDevice(n->device);
-  if (n->scratch) (void)hipFree(n->scratch);
-  if (n->P) (void)hipFree(n->P);
-  delete n;
-  return EBC_OK;
-}
+extern "C" int ebc_cadrl_net_destroy(void *net) { return ebc_host::grad_net_destroy(static_cast<CadrlNet *>(net)); }
 
 extern "C" int ebc_cadrl_net_packed_floats(void *net, int64_t *floats_out) {
-  if (!net || !floats_out) return fail(EBC_ERR_INVALID, "ebc_cadrl_net_packed_floats: null argument");
-  *floats_out = (int64_t)static_cast<CadrlNet *>(net)->D.floats;
-  return EBC_OK;
+  return ebc_host::grad_net_packed_floats(static_cast<CadrlNet *>(net), floats_out, "ebc_cadrl_net_packed_floats");
 }
 
 extern "C" int ebc_cadrl_net_get_packed(void *net, void *stream, float *dst_dev) {
-  if (!net || !dst_dev) return fail(EBC_ERR_INVALID, "ebc_cadrl_net_get_packed: null argument");
-  if (capturing(stream)) return fail(EBC_ERR_UNSUPPORTED, "ebc_cadrl_net_get_packed: the stream is being captured into a HIP graph");
-  CadrlNet *n = static_cast<CadrlNet *>(net);
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipMemcpyAsync(dst_dev, n->P, (size_t)n->D.floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return EBC_OK;
+  return ebc_host::grad_net_copy_packed(static_cast<CadrlNet *>(net), stream, dst_dev, nullptr, "ebc_cadrl_net_get_packed");
 }
 
 extern "C" int ebc_cadrl_net_set_packed(void *net, void *stream, const float *src_dev) {
-  if (!net || !src_dev) return fail(EBC_ERR_INVALID, "ebc_cadrl_net_set_packed: null argument");
-  if (capturing(stream)) return fail(EBC_ERR_UNSUPPORTED, "ebc_cadrl_net_set_packed: the stream is being captured into a HIP graph");
-  CadrlNet *n = static_cast<CadrlNet *>(net);
-  HIP_TRY(hipSetDevice(n->device));
-  HIP_TRY(hipMemcpyAsync(n->P, src_dev, (size_t)n->D.floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return EBC_OK;
+  return ebc_host::grad_net_copy_packed(static_cast<CadrlNet *>(net), stream, nullptr, src_dev, "ebc_cadrl_net_set_packed");
 }
 
 extern "C" int ebc_cadrl_grad(void *net, void *stream, const EbcCadrlGradArgs *args) {
@@ -108,61 +71,29 @@ extern "C" int ebc_cadrl_grad(void *net, void *stream, const EbcCadrlGradArgs *a
     return fail(EBC_ERR_INVALID, "ebc_cadrl_grad: rows are " + std::to_string(args->T) + " wide, the network takes " + std::to_string(D.K[0]));
   if (args->R < 1) return fail(EBC_ERR_UNSUPPORTED, "ebc_cadrl_grad: R < 1 row slots per state (" + std::to_string(args->R) + ")");
   if (args->R > EBC_CADRL_MAX_ROWS) return fail(EBC_ERR_UNSUPPORTED, "ebc_cadrl_grad: R > 128 row slots per state (" + std::to_string(args->R) + ")");
-  if (capturing(stream))
+  if (ebc_host::capturing(stream))
     return fail(EBC_ERR_UNSUPPORTED, "ebc_cadrl_grad: the stream is being captured into a HIP graph; the gradient must be launched, not replayed");
   HIP_TRY(hipSetDevice(n->device));
   const hipStream_t st = (hipStream_t)stream;
-  const size_t PF = D.floats;
-  const int B = args->B;
-  const long long chunks = ((long long)B + EBC_CADRL_GRAD_CHUNK - 1) / EBC_CADRL_GRAD_CHUNK;
-  const int per = chunks < kMaxChunksPerLaunch ? (int)(chunks > 0 ? chunks : 1) : kMaxChunksPerLaunch;
-  // scratch: float64 sums [PF + 2] | loss_part [per] | count_part [per] | partial [per][PF]
-  const size_t acc_bytes = (PF + 2) * sizeof(double), part_at = acc_bytes + (size_t)per * 16;
-  const size_t need = part_at + (size_t)per * PF * sizeof(float);
-  if (need > n->scratch_bytes) {  // grows on demand; growing waits for the device (work that reads the old scratch may be in flight)
-    HIP_TRY(hipDeviceSynchronize());
-    if (n->scratch) HIP_TRY(hipFree(n->scratch));
-    n->scratch = nullptr;
-    n->scratch_bytes = 0;
-    HIP_TRY(hipMalloc(&n->scratch, need));
-    n->scratch_bytes = need;
-  }
-  double *acc64 = static_cast<double *>(n->scratch);
-  double *loss_part = reinterpret_cast<double *>(static_cast<char *>(n->scratch) + acc_bytes);
-  long long *count_part = reinterpret_cast<long long *>(loss_part + per);
-  float *partial = reinterpret_cast<float *>(static_cast<char *>(n->scratch) + part_at);
-
   const size_t lds = ebc::cadrl_grad_lds_floats(D, args->R) * sizeof(float);  // <= 115 KB
   static size_t raised_dev[64] = {0};
   HIP_TRY(ebc_host::raise_dynamic_lds(ebc::cadrl_grad_kernel, n->device, lds, raised_dev));
-  const unsigned reduce_blocks = (unsigned)((PF + 255) / 256);
-  long long done = 0;
-  do {
-    const int now = chunks - done < per ? (int)(chunks - done) : per;
-    if (now > 0) {
-      ebc::CadrlGradLaunch a;
-      a.rows = args->rows;
-      a.n_valid = reinterpret_cast<const long long *>(args->n_valid);
-      a.target = args->target;
-      a.mask = args->sample_mask;
-      a.value = args->value;
-      a.min_row = args->min_row;
-      a.partial = partial;
-      a.loss_part = loss_part;
-      a.count_part = count_part;
-      a.grad_scale = args->grad_scale;
-      a.B = B;
-      a.R = args->R;
-      a.chunk0 = (int)done;
-      a.D = D;
-      hipLaunchKernelGGL(ebc::cadrl_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_CADRL_GRAD_WAVES), lds, st, n->P, a);
-      HIP_TRY(hipGetLastError());
-    }
-    const int first = done == 0, last = done + now >= chunks;
-    hipLaunchKernelGGL(ebc::cadrl_grad_reduce, dim3(reduce_blocks), dim3(256), 0, st, partial, loss_part, count_part, now, PF, first, last, acc64,
-                       args->grad, args->loss_sum, reinterpret_cast<long long *>(args->count));
-    HIP_TRY(hipGetLastError());
-    done += now;
-  } while (done < chunks);
-  return EBC_OK;
+  ebc::CadrlGradLaunch a;
+  a.rows = args->rows;
+  a.n_valid = reinterpret_cast<const long long *>(args->n_valid);
+  a.target = args->target;
+  a.mask = args->sample_mask;
+  a.value = args->value;
+  a.min_row = args->min_row;
+  a.grad_scale = args->grad_scale;
+  a.B = args->B;
+  a.R = args->R;
+  a.D = D;
+  const auto scratch = [n](size_t bytes, void **out) { return ebc_host::grad_net_scratch(n, bytes, out); };
+  const auto launch = [&](int chunk0, int now, float *partial, double *loss_part, long long *count_part) {
+    a.partial = partial, a.loss_part = loss_part, a.count_part = count_part, a.chunk0 = chunk0;
+    hipLaunchKernelGGL(ebc::cadrl_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_CADRL_GRAD_WAVES), lds, st, n->P, a);
+  };
+  return ebc_host::grad_launch<true>(st, D.floats, args->B, EBC_CADRL_GRAD_CHUNK, kMaxChunksPerLaunch, scratch, args->grad, args->loss_sum,
+                                     args->count, launch);
 }

@@ -3,20 +3,16 @@
 // _set_packed.  Its own translation unit: the forward's unit and the step kernels keep their code.
 #include <hip/hip_runtime.h>
 
-#include "ebc_host.h"
+#include "ebc_grad_host.h"
 #include "ebc_sail_api.h"
 #include "ebc_sail_grad.h"
 
 namespace {
 
+using ebc_host::capturing;
 using ebc_host::fail;
 
 constexpr int kMaxChunksPerLaunch = 1024;  // 1024 chunks of partials (204 MB at 5 adults) before the float64 sums take over
-
-bool capturing(void *stream) {
-  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing((hipStream_t)stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
-}
 
 }  // namespace
 
@@ -33,55 +29,28 @@ extern "C" int ebc_sail_grad(void *sail, void *stream, const EbcSailGradArgs *ar
     return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_grad: the stream is being captured into a HIP graph; the gradient must be launched, not replayed");
   HIP_TRY(hipSetDevice(v.device));
   const hipStream_t st = (hipStream_t)stream;
-  const size_t PF = ebc_sail::packed_floats(N);
-  const long long chunks = ((long long)E + EBC_SAIL_GRAD_CHUNK - 1) / EBC_SAIL_GRAD_CHUNK;
-  const int per = chunks < kMaxChunksPerLaunch ? (int)(chunks > 0 ? chunks : 1) : kMaxChunksPerLaunch;
-  // scratch: float64 sums [PF + 2] | loss_part [per] | count_part [per] | partial [per][PF]
-  const size_t acc_bytes = (PF + 2) * sizeof(double), part_at = acc_bytes + (size_t)per * 16;
-  void *scratch = nullptr;
-  if (int rc = ebc_sail_api::grad_scratch(sail, part_at + (size_t)per * PF * sizeof(float), &scratch)) return rc;
-  double *acc64 = static_cast<double *>(scratch);
-  double *loss_part = reinterpret_cast<double *>(static_cast<char *>(scratch) + acc_bytes);
-  long long *count_part = reinterpret_cast<long long *>(loss_part + per);
-  float *partial = reinterpret_cast<float *>(static_cast<char *>(scratch) + part_at);
-
   const int G = ebc_sail::grad_group_envs(N);
   const size_t lds = ebc::sail_grad_lds_floats(G, N) * sizeof(float);  // <= 110 KB
-  static size_t raised_dev[64] = {0};  // more than the 64 KB a launch gets by default; a function attribute is per device
-  if (lds > 65536 && lds > raised_dev[v.device & 63]) {
-    HIP_TRY(hipFuncSetAttribute((const void *)ebc::sail_grad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    raised_dev[v.device & 63] = lds;
-  }
-  const unsigned reduce_blocks = (unsigned)((PF + 255) / 256);
-  long long done = 0;
-  do {
-    const int now = chunks - done < per ? (int)(chunks - done) : per;
-    if (now > 0) {
-      ebc::SailGradLaunch a;
-      a.robot = args->robot;
-      a.ob = args->ob;
-      a.n_rows = reinterpret_cast<const long long *>(args->n_rows);
-      a.target = args->target;
-      a.mask = args->sample_mask;
-      a.action = args->action;
-      a.partial = partial;
-      a.loss_part = loss_part;
-      a.count_part = count_part;
-      a.grad_scale = args->grad_scale;
-      a.E = E;
-      a.R = args->R;
-      a.N = N;
-      a.chunk0 = (int)done;
-      hipLaunchKernelGGL(ebc::sail_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_SAIL_GRAD_WAVES), lds, st, v.P, a);
-      HIP_TRY(hipGetLastError());
-    }
-    const int first = done == 0, last = done + now >= chunks;
-    hipLaunchKernelGGL(ebc::sail_grad_reduce, dim3(reduce_blocks), dim3(256), 0, st, partial, loss_part, count_part, now, PF, first, last,
-                       acc64, args->grad, args->loss_sum, reinterpret_cast<long long *>(args->count));
-    HIP_TRY(hipGetLastError());
-    done += now;
-  } while (done < chunks);
-  return EBC_OK;
+  static size_t raised_dev[64] = {0};
+  HIP_TRY(ebc_host::raise_dynamic_lds(ebc::sail_grad_kernel, v.device, lds, raised_dev));
+  ebc::SailGradLaunch a;
+  a.robot = args->robot;
+  a.ob = args->ob;
+  a.n_rows = reinterpret_cast<const long long *>(args->n_rows);
+  a.target = args->target;
+  a.mask = args->sample_mask;
+  a.action = args->action;
+  a.grad_scale = args->grad_scale;
+  a.E = E;
+  a.R = args->R;
+  a.N = N;
+  const auto scratch = [sail](size_t bytes, void **out) { return ebc_sail_api::grad_scratch(sail, bytes, out); };  // the Sail object's own
+  const auto launch = [&](int chunk0, int now, float *partial, double *loss_part, long long *count_part) {
+    a.partial = partial, a.loss_part = loss_part, a.count_part = count_part, a.chunk0 = chunk0;
+    hipLaunchKernelGGL(ebc::sail_grad_kernel, dim3((unsigned)now), dim3(64 * EBC_SAIL_GRAD_WAVES), lds, st, v.P, a);
+  };
+  return ebc_host::grad_launch<false>(st, ebc_sail::packed_floats(N), E, EBC_SAIL_GRAD_CHUNK, kMaxChunksPerLaunch, scratch, args->grad,
+                                      args->loss_sum, args->count, launch);
 }
 
 extern "C" int ebc_sail_packed_floats(void *sail, int64_t *floats_out) {

@@ -10,12 +10,12 @@ writes its .grad, the optimizer steps it, ebc_lstm_net_set_packed hands the resu
 LstmValueNet.refresh_from hands it to the blocks and the scan that decide.  native=False (and every CPU device) computes
 the same loss and gradient with torch's autograd on LstmModule: the comparison path, and what the CPU tests drive.
 
-The loss is the reference's (rl/utils/trainer.py:74-100).  optimize_epoch and optimize_batch are cadrl_train's;
-run_lstm_training is the schedule of rl/train.py:99-260 with this trainer in the optimizer's place and DeviceSarlPolicy
-over LstmValueNet deciding.  It differs from run_sarl_training in what the reference itself does differently: in RL mode
-the replay holds the policy's last_state, whose rows LstmRL.predict has sorted by decreasing distance to the robot
-(lstm_rl.py:117-123, explorer.py:44), and the next state the target network values is sorted the same way; the imitation
-states stay in the env's order (explorer.py:161).
+The loss is the reference's (rl/utils/trainer.py:74-100).  optimize_epoch and optimize_batch are grad_train's, as are the
+network object's entries, the trainer around the flat tensor and the schedule's body; run_lstm_training is the schedule of
+rl/train.py:99-260 with this trainer in the optimizer's place and DeviceSarlPolicy over LstmValueNet deciding.  It differs
+from run_sarl_training in what the reference itself does differently: in RL mode the replay holds the policy's last_state,
+whose rows LstmRL.predict has sorted by decreasing distance to the robot (lstm_rl.py:117-123, explorer.py:44), and the next
+state the target network values is sorted the same way; the imitation states stay in the env's order (explorer.py:161).
 
 OM-LSTM ([lstm_rl] with_om = true) is the same trainer and schedule on rows T + W wide (13 + 4 * 4 * 3 = 61 at the
 reference's settings; the kernels take up to 64): run_lstm_training(..., om=spec) fills the replay with wide states — the
@@ -23,15 +23,15 @@ imitation window's from ebc_step_k_om in the env's order, the RL rounds' from eb
 from the rows in the sorted order as the reference's transform(state) builds them — and DeviceSarlPolicy(om=spec) decides."""
 import collections
 import ctypes as C
-import os
+import os  # noqa: F401 (a public name of this module since its first version)
 
 import torch
 
-from . import _abi
-from .cadrl_train import _finite, live_states, optimize_batch, optimize_epoch, pad4  # noqa: F401 (re-exported)
+from . import _abi, grad_train
+from .grad_train import (PASS_SIZES, PassChoice, _finite, checked_states_per_pass, live_states, optimize_batch,  # noqa: F401 (re-exported)
+                         optimize_epoch, pad4, pick_states_per_pass)
 from .lstm_rl import LstmModule, LstmValueNet
 from .sarl import DeviceSarlPolicy
-from .sarl_train import PASS_SIZES, PassChoice, checked_states_per_pass, pick_states_per_pass  # noqa: F401 (re-exported)
 
 MLP1_KEYS = ("mlp1.0", "mlp1.2", "mlp1.4", "mlp1.6")
 MLP_KEYS = ("mlp.0", "mlp.2", "mlp.4", "mlp.6")
@@ -86,10 +86,7 @@ def _views(flat, widths, self_state_dim, two):
     out, at = collections.OrderedDict(), 0
     for key, kind, k, o in _layout(widths, self_state_dim, two):
         if kind == "linear":
-            op = pad4(o)
-            out[key + ".weight"] = flat[at:at + k * op].view(k, op)[:, :o].t()
-            out[key + ".bias"] = flat[at + k * op:at + (k + 1) * op][:o]
-            at += (k + 1) * op
+            at = grad_train.linear_views(out, flat, at, key, k, o)
         else:
             h4 = 4 * o
             out[LSTM_KEYS[0]] = flat[at:at + k * h4].view(k, h4).t()
@@ -102,15 +99,8 @@ def _views(flat, widths, self_state_dim, two):
 
 def pack_state_dict(sd, out=None):
     """A state_dict of the reference's keys -> the packed image, flat float32 (into `out` when given)."""
-    widths, S, two = shape_of(sd)
-    if out is None:
-        out = torch.zeros(packed_floats(widths, S, two), dtype=torch.float32, device=sd["mlp.0.weight"].device)
-    else:
-        out.zero_()
-    with torch.no_grad():
-        for key, v in _views(out, widths, S, two).items():
-            v.copy_(sd[key])
-    return out
+    shape = shape_of(sd)
+    return grad_train.pack_into(sd, out, packed_floats(*shape), sd["mlp.0.weight"], lambda flat: _views(flat, *shape))
 
 
 def unpack_to_state_dict(flat, widths, self_state_dim=6, two=True):
@@ -144,8 +134,9 @@ def sort_rows_by_distance(rows, n_valid=None):
     return torch.gather(rows, 1, order[:, :, None].expand_as(rows))
 
 
-class LstmNet(object):
+class LstmNet(grad_train.GradNet):
     """The kernel's network object (ebc_lstm_net_*): the packed image of a state_dict in device memory."""
+    KIND, ARGS = "lstm", _abi.EbcLstmGradArgs
 
     def __init__(self, sd, device_index):
         from . import _capi
@@ -168,65 +159,17 @@ class LstmNet(object):
         self.widths, self.self_state_dim, self.two = widths, S, two
         self.joint_dim = S + widths[5]
 
-    def packed_floats(self):
-        from . import _capi
-        n = C.c_int64()
-        _capi.check(self._L.ebc_lstm_net_packed_floats(self._h, C.byref(n)))
-        return int(n.value)
-
-    def grad_max_rows(self, states_per_pass=0):
-        """The largest R ebc_lstm_grad takes for this network: a chunk's activations (states_per_pass 4, 2, 1: those of
-        that many states) fit a workgroup's LDS."""
-        from . import _capi
-        n = C.c_int()
-        if states_per_pass == 0:
-            _capi.check(self._L.ebc_lstm_net_grad_max_rows(self._h, C.byref(n)))
-        else:
-            _capi.check(self._L.ebc_lstm_net_grad_max_rows_at(self._h, int(states_per_pass), C.byref(n)))
-        return int(n.value)
-
-    def get_packed(self, out):
-        from . import _capi
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.is_cuda and out.numel() == self.packed_floats()
-        _capi.check(self._L.ebc_lstm_net_get_packed(self._h, torch.cuda.current_stream(out.device).cuda_stream, out.data_ptr()))
-        return out
-
-    def set_packed(self, flat):
-        from . import _capi
-        assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.is_cuda and flat.numel() == self.packed_floats()
-        _capi.check(self._L.ebc_lstm_net_set_packed(self._h, torch.cuda.current_stream(flat.device).cuda_stream, flat.data_ptr()))
-
     def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, joint=None, T=None,
              states_per_pass=0):
         """One ebc_lstm_grad on the current stream: rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None,
         mask [B] uint8 or None -> grad [packed floats], loss_sum 0-d float64, count 0-d int64, value [B] float32 and
         joint [B, S + H] float32 when given; every tensor contiguous on the network's device.  states_per_pass: 0 = the
         whole chunk at once; 4, 2, 1 = that many of a chunk's states at a time (more rows fit, the same bytes)."""
-        from . import _capi
-        B, R, Tr = (int(x) for x in rows.shape)
-        a = _abi.EbcLstmGradArgs()
-        a.struct_size = C.sizeof(a)
-        a.B, a.R, a.T, a.grad_scale = B, R, Tr if T is None else int(T), float(grad_scale)
-        a.states_per_pass = int(states_per_pass)
-        for name, t, dtype, numel in (("rows", rows, torch.float32, B * R * Tr), ("target", target, torch.float32, B),
-                                      ("n_valid", n_valid, torch.int64, B), ("sample_mask", mask, torch.uint8, B),
-                                      ("grad", grad, torch.float32, self.packed_floats()), ("loss_sum", loss_sum, torch.float64, 1),
-                                      ("count", count, torch.int64, 1), ("value", value, torch.float32, B),
-                                      ("joint", joint, torch.float32, B * self.joint_dim)):
-            if t is None:
-                continue
-            assert t.dtype == dtype and t.is_contiguous() and t.is_cuda and t.numel() == numel, name
-            setattr(a, name, t.data_ptr())
-        _capi.check(self._L.ebc_lstm_grad(self._h, torch.cuda.current_stream(rows.device).cuda_stream, C.addressof(a)))
-
-    def __del__(self):
-        try:
-            self._L.ebc_lstm_net_destroy(self._h)
-        except Exception:
-            pass
+        self._grad(rows, target, grad, loss_sum, count, grad_scale, n_valid, mask, value,
+                   ("joint", joint, torch.float32, int(rows.shape[0]) * self.joint_dim), T, states_per_pass)
 
 
-class LstmTrainer(object):
+class LstmTrainer(grad_train.PassTrainer):
     """module_or_state_dict: an LstmModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
     (HIP devices only; the default there) or torch autograd of LstmModule.  states_per_pass (native only; native=False
@@ -234,133 +177,33 @@ class LstmTrainer(object):
     time, which takes more rows per state (LstmNet.grad_max_rows(S)) and gives the same bytes; "auto" = per call the
     default call where the batch's R fits it, else the largest pass that holds R."""
 
+    NAME, EXTRA, OTHER_SHAPE = "LstmTrainer", "joint", "another network shape"
+
     def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, states_per_pass=None):
-        sd = module_or_state_dict.state_dict() if isinstance(module_or_state_dict, torch.nn.Module) else module_or_state_dict
-        sd = collections.OrderedDict((k, v.detach().to("cpu", torch.float32)) for k, v in sd.items())
-        self.device = torch.device(device)
+        grad_train.PassTrainer.__init__(self, module_or_state_dict, device, optimizer, lr, native, states_per_pass=states_per_pass)
+
+    def _configure(self, sd, states_per_pass):
         self.widths, self.self_state_dim, self.with_interaction_module = shape_of(sd)
         self.states_per_pass = checked_states_per_pass(states_per_pass, "LstmTrainer")
-        self.native = (self.device.type == "cuda") if native is None else bool(native)
-        if self.native and self.device.type != "cuda":
-            raise NotImplementedError("LstmTrainer(native=True) needs a HIP device: the kernel has no CPU form")
-        self.flat = pack_state_dict(sd).to(self.device).requires_grad_(True)
-        self.flat.grad = torch.zeros_like(self.flat)
-        self._optimizer_spec = optimizer
-        self.set_learning_rate(lr)
-        self.module = module_of(sd).to(self.device)  # the autograd path's
-        self.net = None
-        if self.native:
-            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.net = LstmNet(sd, idx)
-            self.passes = PassChoice(self.net, self.states_per_pass)
 
-    def grad_max_rows(self):
-        """The most rows per state the native path takes with this trainer's states_per_pass."""
-        return self.passes.max_rows()
+    _shape_of, _pack, _module_of, _new_pass_net = staticmethod(shape_of), staticmethod(pack_state_dict), staticmethod(module_of), LstmNet
 
-    def set_learning_rate(self, lr):
-        """Trainer.set_optimizer (trainer.py:24-45): a new optimizer at the stage's learning rate."""
-        spec, params = self._optimizer_spec, [self.flat]
-        if callable(spec):
-            self.optimizer = spec(params)
-        elif spec == "adam":
-            self.optimizer = torch.optim.Adam(params, lr=lr)
-        elif spec == "sgd":
-            self.optimizer = torch.optim.SGD(params, lr=lr, momentum=0.9)
-        else:
-            raise ValueError("optimizer: 'sgd', 'adam' or a callable")
+    def _shape(self):
+        return self.widths, self.self_state_dim, self.with_interaction_module
 
     def _views(self, flat):
-        return _views(flat, self.widths, self.self_state_dim, self.with_interaction_module)
+        return _views(flat, *self._shape())
 
-    # ------------------------------------------------------------------ weights
-    def state_dict(self):
-        return unpack_to_state_dict(self.flat.detach().cpu(), self.widths, self.self_state_dim, self.with_interaction_module)
+    def _forward(self, x, n_valid):
+        return self.module(x, n_valid).squeeze(1)
 
-    def device_state_dict(self):
-        """The reference's keys as views into the master copy on its device (no copy): what LstmValueNet.refresh_from reads."""
-        return self._views(self.flat.detach())
-
-    def save(self, path):
-        """The current weights as a file torch.save wrote: loads into LstmModule and the reference's ValueNetwork1 /
-        ValueNetwork2 with strict=True."""
-        torch.save(self.state_dict(), path)
-
-    def load_state_dict(self, sd):
-        if shape_of(sd) != (self.widths, self.self_state_dim, self.with_interaction_module):
-            raise ValueError("LstmTrainer.load_state_dict: another network shape")
-        with torch.no_grad():
-            pack_state_dict({k: v.to(self.device, torch.float32) for k, v in sd.items()}, out=self.flat)
-        self.push_weights()
-
-    def push_weights(self):
-        """The master copy into the kernel's network object (ebc_lstm_net_set_packed on the current stream)."""
-        if self.net is not None:
-            self.net.set_packed(self.flat.detach())
-
-    def _load_module(self):
-        with torch.no_grad():
-            params = dict(self.module.named_parameters())
-            for key, v in self._views(self.flat.detach()).items():
-                params[key].copy_(v)
-
-    # ------------------------------------------------------------------ loss and gradient
     def loss_and_grad(self, rows, target, n_valid=None, mask=None, grad_scale=None, value=None, joint=None):
         """rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None, mask [B] uint8 / bool or None, on the
         trainer's device -> (loss_sum, count) as 0-d tensors (float64, int64) there; .grad of the master copy holds
         d/dweights of grad_scale / 2 * loss_sum.  grad_scale None: 2 / count, torch's MSELoss over the live states (this
         reads the count back).  value [B] float32 / joint [B, S + H] float32, when given, receive the states' values and
         mlp's inputs (native only)."""
-        rows, target = rows.to(self.device, torch.float32).contiguous(), target.to(self.device, torch.float32).reshape(-1).contiguous()
-        B, R, T = (int(x) for x in rows.shape)
-        if T != self.widths[0]:
-            raise ValueError("LstmTrainer: rows are %d wide, the network takes %d" % (T, self.widths[0]))
-        live = None
-        if grad_scale is None:
-            live = live_states(B, R, n_valid, mask, self.device)
-            grad_scale = 2.0 / max(int(live.sum()), 1)
-        if self.native:
-            loss = torch.empty((), dtype=torch.float64, device=self.device)
-            count = torch.empty((), dtype=torch.int64, device=self.device)
-            nv = None if n_valid is None else n_valid.to(device=self.device, dtype=torch.int64).contiguous()
-            mk = None if mask is None else mask.to(device=self.device).to(torch.uint8).contiguous()
-            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, joint, states_per_pass=self.passes.of(R))
-            return loss, count
-        if value is not None or joint is not None:
-            raise NotImplementedError("LstmTrainer(native=False): `value` and `joint` are the kernel's outputs")
-        if live is None:
-            live = live_states(B, R, n_valid, mask, self.device)
-        idx = torch.nonzero(live).reshape(-1)
-        if idx.numel() == 0:
-            self.flat.grad.zero_()
-            return torch.zeros((), dtype=torch.float64, device=self.device), torch.zeros((), dtype=torch.int64, device=self.device)
-        self._load_module()
-        params = list(self.module.parameters())
-        for p in params:
-            p.requires_grad_(True)
-            p.grad = None
-        x, nv = rows[idx], None
-        if n_valid is not None:
-            # rows past a state's own are never read by the kernel; autograd multiplies their (zero) deltas with them, so
-            # a NaN there must not be an input
-            nv = n_valid.to(self.device)[idx].clamp(max=R)
-            x = torch.where((torch.arange(R, device=self.device)[None, :] < nv[:, None])[:, :, None], x, torch.zeros_like(x))
-        with torch.enable_grad():
-            out = self.module(x, nv).squeeze(1)
-            d = out - target[idx]
-            (0.5 * float(grad_scale) * (d * d).sum()).backward()
-        pack_state_dict({k: p.grad for k, p in self.module.named_parameters()}, out=self.flat.grad)
-        for p in params:
-            p.requires_grad_(False)
-            p.grad = None
-        return (d.detach().double() ** 2).sum(), torch.tensor(int(idx.numel()), dtype=torch.int64, device=self.device)
-
-    def step(self):
-        """Average the gradient over ranks (one all-reduce of the one tensor), step the optimizer, hand the weights on."""
-        from .train import allreduce_flat_
-        allreduce_flat_([self.flat])
-        self.optimizer.step()
-        self.push_weights()
+        return self._loss_and_grad(rows, target, n_valid, mask, grad_scale, value, joint)
 
 
 def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,
@@ -380,8 +223,6 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     collect_il(om=om)'s (the env's order with maps), the RL rounds' stored and next states are
     collect(om=om, sorted_rows=True)'s (one observe_wide_sorted_device after the step is both) and DeviceSarlPolicy(om=om)
     decides.  None changes no byte and no launch."""
-    import torch.distributed as dist
-    from .train import DeviceReplay, EpisodeStore, _multi_rank, all_ranks, collect, collect_il
     dev = trainer.device
     if dev.type != "cuda":
         raise NotImplementedError("run_lstm_training: the rollouts run on a HIP device")
@@ -395,66 +236,12 @@ def run_lstm_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     if trainer.native and env.R > trainer.grad_max_rows():
         raise NotImplementedError("run_lstm_training: %d rows per state, ebc_lstm_grad takes %d for this network; use native=False"
                                   % (env.R, trainer.grad_max_rows()))
-    memory = DeviceReplay(capacity, env.R, width, dev)
-    hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}
-
-    def save(name):
-        if rank == 0 and output_dir:
-            os.makedirs(output_dir, exist_ok=True)
-            trainer.save(os.path.join(output_dir, name))
-    if _multi_rank():  # every replica starts from rank 0's weights
-        with torch.no_grad():
-            dist.broadcast(trainer.flat, src=0)
-        trainer.push_weights()
-    red_dev = dev if (_multi_rank() and dist.get_backend() == "nccl") else None
-    trainer.set_learning_rate(il_learning_rate)
-    if il_steps > 0:
-        if om is None:
-            hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space)
-        else:
-            hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space, om=om)
-        if il_epochs > 0 and all_ranks(len(memory) > 0, red_dev):
-            _finite(memory.values[:len(memory)], "imitation learning: a value target in the replay memory", env)
-            hist["il_loss"] = optimize_epoch(trainer, memory, il_epochs, batch_size, generator)
-            _finite(hist["il_loss"], "imitation learning: the loss", env)
-        save("il_model.pth")
-        if log:
-            log("imitation learning: %d states of %d episodes, loss %s" % (hist["il_stored"], hist["il_episodes"], hist["il_loss"]))
-    if after_il is not None:
-        after_il(hist)
-    trainer.set_learning_rate(rl_learning_rate)
-    net = LstmValueNet(trainer.state_dict(), device=dev, self_state_dim=trainer.self_state_dim)
-    target_net = LstmValueNet(trainer.state_dict(), device=dev, self_state_dim=trainer.self_state_dim)  # explorer.update_target_model
-    policy = DeviceSarlPolicy(net, actions, gamma) if om is None else DeviceSarlPolicy(net, actions, gamma, om=om)
-    t_max = int(round(env.params.time_limit / env.params.time_step)) + 2
-    store = EpisodeStore(env.E, t_max, env.R, width, dev)
-    for it in range(int(train_iterations)):
-        eps = epsilon_start + (epsilon_end - epsilon_start) / epsilon_decay * it if it < epsilon_decay else epsilon_end
-        if om is None:
-            mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator,
-                             store=store, state_transform=sort_rows_by_distance)
-        else:
-            mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator,
-                             store=store, om=om, sorted_rows=True)
-        _finite(mean_r, "round %d: the rollout's mean reward" % it, env)
-        _finite(memory.values[:len(memory)], "round %d: a value target in the replay memory" % it, env)
-        trained = all_ranks(len(memory) > 0, red_dev)
-        loss = optimize_batch(trainer, memory, train_batches, batch_size, generator) if trained else float("nan")
-        if trained:
-            _finite(loss, "round %d: the loss" % it, env)
-        net.refresh_from(trainer)
-        if (it + 1) % target_update_interval == 0:
-            target_net.refresh_from(trainer)
-        hist["rl_loss"].append(loss)
-        hist["mean_reward"].append(mean_r)
-        hist["epsilon"].append(eps)
-        if checkpoint_interval and (it + 1) % checkpoint_interval == 0:
-            save("rl_model_%d.pth" % (it + 1))
-        if log:
-            log("iteration %d: epsilon %.3f mean reward %.4f loss %.3e" % (it, eps, mean_r, loss))
-    if train_iterations:
-        save("rl_model_%d.pth" % train_iterations)
-    hist["native_forwards"] = int(net.native_forwards)
-    hist["native_refreshes"] = int(net.native_refreshes)
-    hist["memory"] = len(memory)
-    return hist
+    # without maps the calls stay as they were: the RL rounds' states sorted here; with them the env sorts and maps (sorted_rows)
+    om_kw = {} if om is None else {"om": om}
+    collect_kw = {"state_transform": sort_rows_by_distance} if om is None else {"om": om, "sorted_rows": True}
+    return grad_train.run_value_training(
+        env, trainer, gamma, width, lambda: LstmValueNet(trainer.state_dict(), device=dev, self_state_dim=trainer.self_state_dim),
+        lambda net: DeviceSarlPolicy(net, actions, gamma, **om_kw), lambda net: net.refresh_from(trainer), om_kw, collect_kw, il_steps,
+        il_epochs, il_learning_rate, il_safety_space, rl_learning_rate, train_iterations, steps_per_iteration, train_batches, batch_size,
+        capacity, epsilon_start, epsilon_end, epsilon_decay, target_update_interval, generator, log, output_dir, checkpoint_interval, rank,
+        after_il)

@@ -9,22 +9,24 @@ result back to the kernel's network object and SarlValueNet.refresh_from hands i
 native=False (and every CPU device) computes the same loss and gradient with torch's autograd on SarlModule: the
 comparison path, and what the CPU tests drive.  ebcsim.train.DataParallelTrainer and run_training stay what they were.
 
-The loss is the reference's (rl/utils/trainer.py:74-100): the mean squared error between the network's value of a state
-and its target.  optimize_epoch and optimize_batch are cadrl_train's (they take any trainer with this interface);
-run_sarl_training is the schedule of rl/train.py:99-260 on the generic pieces of ebcsim.train with this trainer in the
-optimizer's place and DeviceSarlPolicy deciding.
+The loss is the reference's (rl/utils/trainer.py:74-100): the mean squared error between the network's value of a state and
+its target.  optimize_epoch and optimize_batch are grad_train's (they take any trainer with this interface), as are the
+network object's entries, the trainer around the flat tensor and the schedule's body; run_sarl_training is the schedule of
+rl/train.py:99-260 on the generic pieces of ebcsim.train with this trainer in the optimizer's place and DeviceSarlPolicy
+deciding.
 
 OM-SARL (om_width = W > 0, run_sarl_training(om=spec)): mlp1's first layer takes T + W inputs, the kernel's network is
 ebc_sarl_net_create_om's, the stored states are the wide ones (BatchedEnv.observe_wide_device, ebc_step_k_om) and
 DeviceSarlPolicy(om=spec) decides.  The width of the maps is not in a state_dict (only T + W is): it is given explicitly."""
 import collections
 import ctypes as C
-import os
+import os  # noqa: F401 (a public name of this module since its first version)
 
 import torch
 
-from . import _abi
-from .cadrl_train import _finite, live_states, optimize_batch, optimize_epoch, pad4  # noqa: F401 (re-exported)
+from . import _abi, grad_train
+from .grad_train import (PASS_SIZES, PassChoice, _finite, checked_states_per_pass, live_states, optimize_batch,  # noqa: F401 (re-exported)
+                         optimize_epoch, pad4, pick_states_per_pass)
 from .sarl import DeviceSarlPolicy, SarlValueNet
 from .train import SarlModule
 
@@ -33,46 +35,6 @@ LAYER_KEYS = ("mlp1.0", "mlp1.2", "mlp2.0", "mlp2.2", "attention.0", "attention.
 STACKS = (("mlp1", 2), ("mlp2", 2), ("attention", 3), ("mlp3", 4))
 MAX_IN, MAX_WIDTH = 64, 256  # csrc/ebc_sarl_grad_rule.h
 MAX_OM, MAX_WIDE = 192, 224  # the same: the widest map behind a row, the widest row with its map
-PASS_SIZES = (4, 2, 1)  # EbcSarlGradArgs.states_per_pass / EbcLstmGradArgs.states_per_pass: a chunk's states, that many at a time
-
-
-def checked_states_per_pass(value, who):
-    """A trainer's states_per_pass: None (the whole chunk at once, the kernel's default call), "auto", 1, 2 or 4."""
-    if value is None or value == "auto" or (type(value) is int and value in PASS_SIZES):
-        return value
-    raise ValueError("%s: states_per_pass is None, 'auto', 1, 2 or 4, got %r" % (who, value))
-
-
-def pick_states_per_pass(R, whole_chunk, limits):
-    """What "auto" passes to the kernel for states of R rows.  whole_chunk: the largest R of the default call
-    (grad_max_rows()); limits: {S: grad_max_rows(S)} for S in PASS_SIZES.  0 (the default call) where the whole chunk
-    fits, else the largest S whose limit holds R; past every limit 1, which the kernel then refuses by R, S and limit."""
-    if R <= whole_chunk:
-        return 0
-    for S in PASS_SIZES:
-        if R <= limits[S]:
-            return S
-    return PASS_SIZES[-1]
-
-
-class PassChoice(object):
-    """A trainer's states_per_pass over its network object (SarlNet / LstmNet): what each call passes and the most rows
-    the trainer takes.  The limits are asked of the network once."""
-
-    def __init__(self, net, setting):
-        self.setting = setting
-        self.whole_chunk = net.grad_max_rows()
-        self.limits = {S: net.grad_max_rows(S) for S in PASS_SIZES}
-
-    def of(self, R):
-        if self.setting is None:
-            return 0
-        return pick_states_per_pass(R, self.whole_chunk, self.limits) if self.setting == "auto" else self.setting
-
-    def max_rows(self):
-        if self.setting is None:
-            return self.whole_chunk
-        return max(self.whole_chunk, *self.limits.values()) if self.setting == "auto" else self.limits[self.setting]
 
 
 def _stack_keys(sd):
@@ -113,37 +75,23 @@ def packed_floats(widths, self_state_dim=6, with_global_state=True):
     return sum((k + 1) * pad4(o) for k, o in zip(layer_inputs(widths, self_state_dim, with_global_state), widths[1:]))
 
 
-def _layer_views(flat, widths, self_state_dim, with_global_state):
-    """Per layer (W view [out, in], bias view [out]) into a flat packed tensor."""
-    out, at = [], 0
-    for k, o in zip(layer_inputs(widths, self_state_dim, with_global_state), widths[1:]):
-        op = pad4(o)
-        out.append((flat[at:at + k * op].view(k, op)[:, :o].t(), flat[at + k * op:at + (k + 1) * op][:o]))
-        at += (k + 1) * op
+def _views(flat, widths, self_state_dim, with_global_state):
+    """An ordered dict of the reference's keys -> views into a flat packed tensor, in torch's shapes."""
+    out, at = collections.OrderedDict(), 0
+    for key, k, o in zip(LAYER_KEYS, layer_inputs(widths, self_state_dim, with_global_state), widths[1:]):
+        at = grad_train.linear_views(out, flat, at, key, k, o)
     return out
 
 
 def pack_state_dict(sd, out=None):
     """A state_dict of the reference's keys -> the packed image, flat float32 (into `out` when given)."""
-    widths, S, glob = shape_of(sd)
-    if out is None:
-        out = torch.zeros(packed_floats(widths, S, glob), dtype=torch.float32, device=sd["mlp1.0.weight"].device)
-    else:
-        out.zero_()
-    with torch.no_grad():
-        for key, (w, b) in zip(LAYER_KEYS, _layer_views(out, widths, S, glob)):
-            w.copy_(sd[key + ".weight"])
-            b.copy_(sd[key + ".bias"])
-    return out
+    shape = shape_of(sd)
+    return grad_train.pack_into(sd, out, packed_floats(*shape), sd["mlp1.0.weight"], lambda flat: _views(flat, *shape))
 
 
 def unpack_to_state_dict(flat, widths, self_state_dim=6, with_global_state=True):
     """The packed image -> an ordered state_dict with SarlModule's (the reference's) keys, fresh contiguous tensors."""
-    sd = collections.OrderedDict()
-    for key, (w, b) in zip(LAYER_KEYS, _layer_views(flat.detach(), widths, self_state_dim, with_global_state)):
-        sd[key + ".weight"] = w.clone().contiguous()
-        sd[key + ".bias"] = b.clone().contiguous()
-    return sd
+    return collections.OrderedDict((k, v.clone().contiguous()) for k, v in _views(flat.detach(), widths, self_state_dim, with_global_state).items())
 
 
 def module_of(sd):
@@ -154,8 +102,9 @@ def module_of(sd):
     return m
 
 
-class SarlNet(object):
+class SarlNet(grad_train.GradNet):
     """The kernel's network object (ebc_sarl_net_*): the packed image of a state_dict in device memory."""
+    KIND, ARGS = "sarl", _abi.EbcSarlGradArgs
 
     def __init__(self, sd, device_index, widths=None, self_state_dim=None, with_global_state=None, stack_layers=None, om_width=None):
         """widths / self_state_dim / with_global_state / stack_layers override what the state_dict says (the tests of the
@@ -192,65 +141,18 @@ class SarlNet(object):
         self.om_width = int(om_width or 0)
         self.widths = [w.input_dim + self.om_width] + units  # [0]: the rows ebc_sarl_grad takes
 
-    def packed_floats(self):
-        from . import _capi
-        n = C.c_int64()
-        _capi.check(self._L.ebc_sarl_net_packed_floats(self._h, C.byref(n)))
-        return int(n.value)
-
-    def grad_max_rows(self, states_per_pass=0):
-        """The largest R ebc_sarl_grad takes for this network: a chunk's activations (states_per_pass 4, 2, 1: those of
-        that many states) fit a workgroup's LDS."""
-        from . import _capi
-        n = C.c_int()
-        if states_per_pass == 0:
-            _capi.check(self._L.ebc_sarl_net_grad_max_rows(self._h, C.byref(n)))
-        else:
-            _capi.check(self._L.ebc_sarl_net_grad_max_rows_at(self._h, int(states_per_pass), C.byref(n)))
-        return int(n.value)
-
-    def get_packed(self, out):
-        from . import _capi
-        assert out.dtype == torch.float32 and out.is_contiguous() and out.is_cuda and out.numel() == self.packed_floats()
-        _capi.check(self._L.ebc_sarl_net_get_packed(self._h, torch.cuda.current_stream(out.device).cuda_stream, out.data_ptr()))
-        return out
-
-    def set_packed(self, flat):
-        from . import _capi
-        assert flat.dtype == torch.float32 and flat.is_contiguous() and flat.is_cuda and flat.numel() == self.packed_floats()
-        _capi.check(self._L.ebc_sarl_net_set_packed(self._h, torch.cuda.current_stream(flat.device).cuda_stream, flat.data_ptr()))
-
     def grad(self, rows, target, grad, loss_sum, count, grad_scale, n_valid=None, mask=None, value=None, attention=None, T=None,
              states_per_pass=0):
         """One ebc_sarl_grad on the current stream: rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None,
         mask [B] uint8 or None -> grad [packed floats], loss_sum 0-d float64, count 0-d int64, value [B] float32 and
         attention [B, R] float32 when given; every tensor contiguous on the network's device.  states_per_pass: 0 = the
         whole chunk at once; 4, 2, 1 = that many of a chunk's states at a time (more rows fit, the same bytes)."""
-        from . import _capi
-        B, R, Tr = (int(x) for x in rows.shape)
-        a = _abi.EbcSarlGradArgs()
-        a.struct_size = C.sizeof(a)
-        a.B, a.R, a.T, a.grad_scale = B, R, Tr if T is None else int(T), float(grad_scale)
-        a.states_per_pass = int(states_per_pass)
-        for name, t, dtype, numel in (("rows", rows, torch.float32, B * R * Tr), ("target", target, torch.float32, B),
-                                      ("n_valid", n_valid, torch.int64, B), ("sample_mask", mask, torch.uint8, B),
-                                      ("grad", grad, torch.float32, self.packed_floats()), ("loss_sum", loss_sum, torch.float64, 1),
-                                      ("count", count, torch.int64, 1), ("value", value, torch.float32, B),
-                                      ("attention", attention, torch.float32, B * R)):
-            if t is None:
-                continue
-            assert t.dtype == dtype and t.is_contiguous() and t.is_cuda and t.numel() == numel, name
-            setattr(a, name, t.data_ptr())
-        _capi.check(self._L.ebc_sarl_grad(self._h, torch.cuda.current_stream(rows.device).cuda_stream, C.addressof(a)))
-
-    def __del__(self):
-        try:
-            self._L.ebc_sarl_net_destroy(self._h)
-        except Exception:
-            pass
+        B, R = int(rows.shape[0]), int(rows.shape[1])
+        self._grad(rows, target, grad, loss_sum, count, grad_scale, n_valid, mask, value, ("attention", attention, torch.float32, B * R), T,
+                   states_per_pass)
 
 
-class SarlTrainer(object):
+class SarlTrainer(grad_train.PassTrainer):
     """module_or_state_dict: a SarlModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
     (HIP devices only; the default there) or torch autograd of SarlModule.  om_width: the W of OM-SARL's maps; the
@@ -259,10 +161,13 @@ class SarlTrainer(object):
     at once; 1, 2, 4 = that many states at a time, which takes more rows per state (SarlNet.grad_max_rows(S)) and gives
     the same bytes; "auto" = per call the default call where the batch's R fits it, else the largest pass that holds R."""
 
+    NAME, EXTRA, OTHER_SHAPE = "SarlTrainer", "attention", "another network shape"
+
     def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, om_width=0, states_per_pass=None):
-        sd = module_or_state_dict.state_dict() if isinstance(module_or_state_dict, torch.nn.Module) else module_or_state_dict
-        sd = collections.OrderedDict((k, v.detach().to("cpu", torch.float32)) for k, v in sd.items())
-        self.device = torch.device(device)
+        grad_train.PassTrainer.__init__(self, module_or_state_dict, device, optimizer, lr, native, om_width=om_width,
+                                        states_per_pass=states_per_pass)
+
+    def _configure(self, sd, om_width, states_per_pass):
         self.widths, self.self_state_dim, self.with_global_state = shape_of(sd)
         self.om_width = int(om_width)
         self.states_per_pass = checked_states_per_pass(states_per_pass, "SarlTrainer")
@@ -272,131 +177,26 @@ class SarlTrainer(object):
             raise ValueError("SarlTrainer: om_width %d leaves no rotated columns of mlp1.0's %d inputs" % (self.om_width, self.widths[0]))
         if self.om_width and self.widths[0] > MAX_WIDE:
             raise NotImplementedError("SarlTrainer: T + om_width = %d columns, the gradient takes up to %d" % (self.widths[0], MAX_WIDE))
-        self.native = (self.device.type == "cuda") if native is None else bool(native)
-        if self.native and self.device.type != "cuda":
-            raise NotImplementedError("SarlTrainer(native=True) needs a HIP device: the kernel has no CPU form")
-        self.flat = pack_state_dict(sd).to(self.device).requires_grad_(True)
-        self.flat.grad = torch.zeros_like(self.flat)
-        self._optimizer_spec = optimizer
-        self.set_learning_rate(lr)
-        self.module = module_of(sd).to(self.device)  # the autograd path's
-        self.net = None
-        if self.native:
-            idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
-            self.net = SarlNet(sd, idx, om_width=self.om_width or None)
-            self.passes = PassChoice(self.net, self.states_per_pass)
 
-    def grad_max_rows(self):
-        """The most rows per state the native path takes with this trainer's states_per_pass."""
-        return self.passes.max_rows()
+    _shape_of, _pack, _module_of = staticmethod(shape_of), staticmethod(pack_state_dict), staticmethod(module_of)
+    _param_key = staticmethod(SarlModule._ref_name)
 
-    def set_learning_rate(self, lr):
-        """Trainer.set_optimizer (trainer.py:24-45): a new optimizer at the stage's learning rate."""
-        spec, params = self._optimizer_spec, [self.flat]
-        if callable(spec):
-            self.optimizer = spec(params)
-        elif spec == "adam":
-            self.optimizer = torch.optim.Adam(params, lr=lr)
-        elif spec == "sgd":
-            self.optimizer = torch.optim.SGD(params, lr=lr, momentum=0.9)
-        else:
-            raise ValueError("optimizer: 'sgd', 'adam' or a callable")
+    def _shape(self):
+        return self.widths, self.self_state_dim, self.with_global_state
 
     def _views(self, flat):
-        return _layer_views(flat, self.widths, self.self_state_dim, self.with_global_state)
+        return _views(flat, *self._shape())
 
-    # ------------------------------------------------------------------ weights
-    def state_dict(self):
-        return unpack_to_state_dict(self.flat.detach().cpu(), self.widths, self.self_state_dim, self.with_global_state)
+    def _new_pass_net(self, sd, index):
+        return SarlNet(sd, index, om_width=self.om_width or None)
 
-    def device_state_dict(self):
-        """The reference's keys as views into the master copy on its device (no copy): what SarlValueNet.refresh_from reads."""
-        sd = collections.OrderedDict()
-        for key, (w, b) in zip(LAYER_KEYS, self._views(self.flat.detach())):
-            sd[key + ".weight"], sd[key + ".bias"] = w, b
-        return sd
-
-    def save(self, path):
-        """The current weights as a file torch.save wrote: loads into SarlModule and the reference's ValueNetwork with
-        strict=True."""
-        torch.save(self.state_dict(), path)
-
-    def load_state_dict(self, sd):
-        if shape_of(sd) != (self.widths, self.self_state_dim, self.with_global_state):
-            raise ValueError("SarlTrainer.load_state_dict: another network shape")
-        with torch.no_grad():
-            pack_state_dict({k: v.to(self.device, torch.float32) for k, v in sd.items()}, out=self.flat)
-        self.push_weights()
-
-    def push_weights(self):
-        """The master copy into the kernel's network object (ebc_sarl_net_set_packed on the current stream)."""
-        if self.net is not None:
-            self.net.set_packed(self.flat.detach())
-
-    def _load_module(self):
-        with torch.no_grad():
-            params = self.module.reference_state_dict()
-            for key, (w, b) in zip(LAYER_KEYS, self._views(self.flat.detach())):
-                params[key + ".weight"].copy_(w)
-                params[key + ".bias"].copy_(b)
-
-    # ------------------------------------------------------------------ loss and gradient
     def loss_and_grad(self, rows, target, n_valid=None, mask=None, grad_scale=None, value=None, attention=None):
         """rows [B, R, T] float32, target [B] float32, n_valid [B] int64 or None, mask [B] uint8 / bool or None, on the
         trainer's device -> (loss_sum, count) as 0-d tensors (float64, int64) there; .grad of the master copy holds
         d/dweights of grad_scale / 2 * loss_sum.  grad_scale None: 2 / count, torch's MSELoss over the live states (this
         reads the count back).  value [B] float32 / attention [B, R] float32, when given, receive the states' values and
         softmax weights (native only)."""
-        rows, target = rows.to(self.device, torch.float32).contiguous(), target.to(self.device, torch.float32).reshape(-1).contiguous()
-        B, R, T = (int(x) for x in rows.shape)
-        if T != self.widths[0]:
-            raise ValueError("SarlTrainer: rows are %d wide, the network takes %d" % (T, self.widths[0]))
-        live = None
-        if grad_scale is None:
-            live = live_states(B, R, n_valid, mask, self.device)
-            grad_scale = 2.0 / max(int(live.sum()), 1)
-        if self.native:
-            loss = torch.empty((), dtype=torch.float64, device=self.device)
-            count = torch.empty((), dtype=torch.int64, device=self.device)
-            nv = None if n_valid is None else n_valid.to(device=self.device, dtype=torch.int64).contiguous()
-            mk = None if mask is None else mask.to(device=self.device).to(torch.uint8).contiguous()
-            self.net.grad(rows, target, self.flat.grad, loss, count, grad_scale, nv, mk, value, attention, states_per_pass=self.passes.of(R))
-            return loss, count
-        if value is not None or attention is not None:
-            raise NotImplementedError("SarlTrainer(native=False): `value` and `attention` are the kernel's outputs")
-        if live is None:
-            live = live_states(B, R, n_valid, mask, self.device)
-        idx = torch.nonzero(live).reshape(-1)
-        if idx.numel() == 0:
-            self.flat.grad.zero_()
-            return torch.zeros((), dtype=torch.float64, device=self.device), torch.zeros((), dtype=torch.int64, device=self.device)
-        self._load_module()
-        params = list(self.module.parameters())
-        for p in params:
-            p.requires_grad_(True)
-            p.grad = None
-        x, nv = rows[idx], None
-        if n_valid is not None:
-            # rows past a state's own are never read by the kernel; autograd multiplies their (zero) weights with them, so
-            # a NaN there must not be an input
-            nv = n_valid.to(self.device)[idx].clamp(max=R)
-            x = torch.where((torch.arange(R, device=self.device)[None, :] < nv[:, None])[:, :, None], x, torch.zeros_like(x))
-        with torch.enable_grad():
-            out = self.module(x, nv)
-            d = out - target[idx]
-            (0.5 * float(grad_scale) * (d * d).sum()).backward()
-        pack_state_dict({SarlModule._ref_name(k): p.grad for k, p in self.module.named_parameters()}, out=self.flat.grad)
-        for p in params:
-            p.requires_grad_(False)
-            p.grad = None
-        return (d.detach().double() ** 2).sum(), torch.tensor(int(idx.numel()), dtype=torch.int64, device=self.device)
-
-    def step(self):
-        """Average the gradient over ranks (one all-reduce of the one tensor), step the optimizer, hand the weights on."""
-        from .train import allreduce_flat_
-        allreduce_flat_([self.flat])
-        self.optimizer.step()
-        self.push_weights()
+        return self._loss_and_grad(rows, target, n_valid, mask, grad_scale, value, attention)
 
 
 def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,
@@ -414,8 +214,6 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     om.width)), the replay and the episode store hold the wide states, collect_il and collect store them (ebc_step_k_om,
     ebc_observe_wide) and DeviceSarlPolicy(om=om) decides.
     Returns a dict of what happened."""
-    import torch.distributed as dist
-    from .train import DeviceReplay, EpisodeStore, _multi_rank, all_ranks, collect, collect_il
     dev = trainer.device
     if dev.type != "cuda":
         raise NotImplementedError("run_sarl_training: the rollouts run on a HIP device")
@@ -426,60 +224,10 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     if trainer.native and env.R > trainer.grad_max_rows():
         raise NotImplementedError("run_sarl_training: %d rows per state, ebc_sarl_grad takes %d for this network; use native=False"
                                   % (env.R, trainer.grad_max_rows()))
-    memory = DeviceReplay(capacity, env.R, env.T + W, dev)
     om_kw = {} if om is None else {"om": om}  # without maps: the calls as they were
-    hist = {"il_stored": 0, "il_episodes": 0, "il_loss": None, "rl_loss": [], "mean_reward": [], "epsilon": []}
-
-    def save(name):
-        if rank == 0 and output_dir:
-            os.makedirs(output_dir, exist_ok=True)
-            trainer.save(os.path.join(output_dir, name))
-    if _multi_rank():  # every replica starts from rank 0's weights
-        with torch.no_grad():
-            dist.broadcast(trainer.flat, src=0)
-        trainer.push_weights()
-    red_dev = dev if (_multi_rank() and dist.get_backend() == "nccl") else None
-    trainer.set_learning_rate(il_learning_rate)
-    if il_steps > 0:
-        hist["il_stored"], hist["il_episodes"] = collect_il(env, memory, il_steps, gamma, il_safety_space, **om_kw)
-        if il_epochs > 0 and all_ranks(len(memory) > 0, red_dev):
-            _finite(memory.values[:len(memory)], "imitation learning: a value target in the replay memory", env)
-            hist["il_loss"] = optimize_epoch(trainer, memory, il_epochs, batch_size, generator)
-            _finite(hist["il_loss"], "imitation learning: the loss", env)
-        save("il_model.pth")
-        if log:
-            log("imitation learning: %d states of %d episodes, loss %s" % (hist["il_stored"], hist["il_episodes"], hist["il_loss"]))
-    if after_il is not None:
-        after_il(hist)
-    trainer.set_learning_rate(rl_learning_rate)
     kw = dict(device=dev, with_global_state=trainer.with_global_state, self_state_dim=trainer.self_state_dim)
-    net = SarlValueNet(trainer.state_dict(), **kw)
-    target_net = SarlValueNet(trainer.state_dict(), **kw)  # explorer.update_target_model (train.py:195)
-    policy = DeviceSarlPolicy(net, actions, gamma, **om_kw)
-    t_max = int(round(env.params.time_limit / env.params.time_step)) + 2
-    store = EpisodeStore(env.E, t_max, env.R, env.T + W, dev)
-    for it in range(int(train_iterations)):
-        eps = epsilon_start + (epsilon_end - epsilon_start) / epsilon_decay * it if it < epsilon_decay else epsilon_end
-        mean_r = collect(env, policy, target_net, memory, steps_per_iteration, gamma, epsilon=eps, generator=generator, store=store, **om_kw)
-        _finite(mean_r, "round %d: the rollout's mean reward" % it, env)
-        _finite(memory.values[:len(memory)], "round %d: a value target in the replay memory" % it, env)
-        trained = all_ranks(len(memory) > 0, red_dev)
-        loss = optimize_batch(trainer, memory, train_batches, batch_size, generator) if trained else float("nan")
-        if trained:
-            _finite(loss, "round %d: the loss" % it, env)
-        net.refresh_from(trainer)
-        if (it + 1) % target_update_interval == 0:
-            target_net.refresh_from(trainer)
-        hist["rl_loss"].append(loss)
-        hist["mean_reward"].append(mean_r)
-        hist["epsilon"].append(eps)
-        if checkpoint_interval and (it + 1) % checkpoint_interval == 0:
-            save("rl_model_%d.pth" % (it + 1))
-        if log:
-            log("iteration %d: epsilon %.3f mean reward %.4f loss %.3e" % (it, eps, mean_r, loss))
-    if train_iterations:
-        save("rl_model_%d.pth" % train_iterations)
-    hist["native_forwards"] = int(net.native_forwards)
-    hist["native_refreshes"] = int(net.native_refreshes)
-    hist["memory"] = len(memory)
-    return hist
+    return grad_train.run_value_training(
+        env, trainer, gamma, env.T + W, lambda: SarlValueNet(trainer.state_dict(), **kw), lambda net: DeviceSarlPolicy(net, actions, gamma, **om_kw),
+        lambda net: net.refresh_from(trainer), om_kw, om_kw, il_steps, il_epochs, il_learning_rate, il_safety_space, rl_learning_rate,
+        train_iterations, steps_per_iteration, train_batches, batch_size, capacity, epsilon_start, epsilon_end, epsilon_decay,
+        target_update_interval, generator, log, output_dir, checkpoint_interval, rank, after_il)
