@@ -72,6 +72,15 @@
 #define EBC_SARL_GRAD_MAX_ROW 256    // what the host build's buffers hold of a row, wide or not
 #define EBC_SARL_GRAD_MAX_WIDTH 256  // widest hidden layer
 #define EBC_SARL_GRAD_MAX_CHUNKS 256 // chunks one launch of the kernel takes (100 MB of partials at the reference widths)
+// The layer form (ebc_sarl_grad_layers.h): the same rule layer by layer over the whole batch, activations in device memory
+#define EBC_SARL_GRAD_LAYERS_MAX_WIDTH 640    // widest hidden layer of the layer form (the reference's policy_x4: 600)
+#define EBC_SARL_GRAD_LAYERS_MAX_ROWS 128     // most row slots per state of the layer form (the product's row limit)
+#define EBC_SARL_GRAD_LAYERS_RUN_SLOTS 65536  // row slots (states * R, whole chunks) of one run of the layer form
+// What the serial loops below hold of a hidden layer, per row: the stride of their buffers.  It moves no byte of any
+// result; a host build with -DEBC_SARL_GRAD_HOST_WIDTH=640 runs the networks of the layer form.
+#ifndef EBC_SARL_GRAD_HOST_WIDTH
+#define EBC_SARL_GRAD_HOST_WIDTH 256
+#endif
 
 namespace ebc_sarl {
 
@@ -136,6 +145,19 @@ EBC_CADRL_HD int grad_dims_refused_wide(const int *widths, int self_dim, int om_
   return widths[0] + om_width > EBC_SARL_GRAD_MAX_WIDE ? 15 : 0;
 }
 
+// The layer form's limits: grad_dims_refused_wide's codes with 640 as the widest hidden layer; the rows' limits are the same.
+EBC_CADRL_HD int grad_dims_refused_layers(const int *widths, int self_dim, int om_width) {
+  if (widths[0] < 1 || widths[0] > EBC_SARL_GRAD_MAX_IN) return 1;
+  for (int l = 0; l < EBC_SARL_GRAD_LAYERS; ++l) {
+    const int o = widths[l + 1];
+    if (o < 1 || o > EBC_SARL_GRAD_LAYERS_MAX_WIDTH) return l + 2;
+    if ((l == L_ATC || l == L_M3D) && o != 1) return l + 2;
+  }
+  if (self_dim < 0 || self_dim > widths[0]) return 13;
+  if (om_width < 0 || om_width > EBC_SARL_GRAD_MAX_OM) return 14;
+  return widths[0] + om_width > EBC_SARL_GRAD_MAX_WIDE ? 15 : 0;
+}
+
 // exp(s) of a score
 EBC_CADRL_HD float score_exp(float s) {
   float sc, p;
@@ -183,13 +205,15 @@ inline void grad_linear(const float *P, float *G, const GradDims &D, int l, cons
   }
 }
 
-// what the forward of one state keeps for its backward; rows side by side, MAX_WIDTH apart
+enum { HW = EBC_SARL_GRAD_HOST_WIDTH };
+
+// what the forward of one state keeps for its backward; rows side by side, HW apart ([h1 | g]: 2 HW)
 struct StateActs {
   int n;
   std::vector<float> a1, h1, b1, ft, c1, c2, xa, s, w, g, j, m1, m2, m3;
   explicit StateActs(int R)
-      : n(0), a1((size_t)R * 256), h1((size_t)R * 256), b1((size_t)R * 256), ft((size_t)R * 256), c1((size_t)R * 256), c2((size_t)R * 256),
-        xa((size_t)R * 512), s(R), w(R), g(256), j(EBC_SARL_GRAD_MAX_ROW + 256), m1(256), m2(256), m3(256) {}
+      : n(0), a1((size_t)R * HW), h1((size_t)R * HW), b1((size_t)R * HW), ft((size_t)R * HW), c1((size_t)R * HW), c2((size_t)R * HW),
+        xa((size_t)R * 2 * HW), s(R), w(R), g(HW), j(EBC_SARL_GRAD_MAX_ROW + HW), m1(HW), m2(HW), m3(HW) {}
 };
 
 // the forward of ONE state with n >= 1 rows x[r][0 .. T) -> L10's output
@@ -197,26 +221,26 @@ inline float grad_forward_state(const float *P, const GradDims &D, const float *
   const int H = D.O[L_M1B], F = D.O[L_M2B];
   A.n = n;
   for (int r = 0; r < n; ++r) {
-    grad_layer(P, D, L_M1A, x + (size_t)r * D.T, &A.a1[(size_t)r * 256], true);
-    grad_layer(P, D, L_M1B, &A.a1[(size_t)r * 256], &A.h1[(size_t)r * 256], true);
-    grad_layer(P, D, L_M2A, &A.h1[(size_t)r * 256], &A.b1[(size_t)r * 256], true);
-    grad_layer(P, D, L_M2B, &A.b1[(size_t)r * 256], &A.ft[(size_t)r * 256], false);
+    grad_layer(P, D, L_M1A, x + (size_t)r * D.T, &A.a1[(size_t)r * HW], true);
+    grad_layer(P, D, L_M1B, &A.a1[(size_t)r * HW], &A.h1[(size_t)r * HW], true);
+    grad_layer(P, D, L_M2A, &A.h1[(size_t)r * HW], &A.b1[(size_t)r * HW], true);
+    grad_layer(P, D, L_M2B, &A.b1[(size_t)r * HW], &A.ft[(size_t)r * HW], false);
   }
   if (D.global)
     for (int k = 0; k < H; ++k) {
       float acc = 0.0f;
-      for (int r = 0; r < n; ++r) acc = acc + A.h1[(size_t)r * 256 + k];
+      for (int r = 0; r < n; ++r) acc = acc + A.h1[(size_t)r * HW + k];
       A.g[k] = over_rows(acc, n);
     }
   float sum = 0.0f;
   for (int r = 0; r < n; ++r) {
-    float *xa = &A.xa[(size_t)r * 512];
-    for (int k = 0; k < H; ++k) xa[k] = A.h1[(size_t)r * 256 + k];
+    float *xa = &A.xa[(size_t)r * 2 * HW];
+    for (int k = 0; k < H; ++k) xa[k] = A.h1[(size_t)r * HW + k];
     if (D.global)
       for (int k = 0; k < H; ++k) xa[H + k] = A.g[k];
-    grad_layer(P, D, L_ATA, xa, &A.c1[(size_t)r * 256], true);
-    grad_layer(P, D, L_ATB, &A.c1[(size_t)r * 256], &A.c2[(size_t)r * 256], true);
-    A.s[r] = grad_unit(P, D, L_ATC, 0, &A.c2[(size_t)r * 256]);
+    grad_layer(P, D, L_ATA, xa, &A.c1[(size_t)r * HW], true);
+    grad_layer(P, D, L_ATB, &A.c1[(size_t)r * HW], &A.c2[(size_t)r * HW], true);
+    A.s[r] = grad_unit(P, D, L_ATC, 0, &A.c2[(size_t)r * HW]);
     A.w[r] = score_exp(A.s[r]);
     sum = sum + A.w[r];
   }
@@ -224,7 +248,7 @@ inline float grad_forward_state(const float *P, const GradDims &D, const float *
   for (int k = 0; k < D.S; ++k) A.j[k] = x[k];
   for (int f = 0; f < F; ++f) {
     float acc = 0.0f;
-    for (int r = 0; r < n; ++r) acc = chain(A.w[r], A.ft[(size_t)r * 256 + f], acc);
+    for (int r = 0; r < n; ++r) acc = chain(A.w[r], A.ft[(size_t)r * HW + f], acc);
     A.j[D.S + f] = acc;
   }
   grad_layer(P, D, L_M3A, A.j.data(), A.m1.data(), true);
@@ -237,7 +261,7 @@ inline float grad_forward_state(const float *P, const GradDims &D, const float *
 // their deltas, as the kernel overwrites them
 inline void grad_backward_state(const float *P, float *G, const GradDims &D, const float *x, StateActs &A, float seed) {
   const int H = D.O[L_M1B], F = D.O[L_M2B], n = A.n;
-  float d[512], dj[EBC_SARL_GRAD_MAX_ROW + 256];
+  float d[2 * HW], dj[EBC_SARL_GRAD_MAX_ROW + HW];
   grad_linear(P, G, D, L_M3D, A.m3.data(), &seed, d);
   for (int k = 0; k < D.K[L_M3D]; ++k) A.m3[k] = grad_relu_back(A.m3[k], d[k]);
   grad_linear(P, G, D, L_M3C, A.m2.data(), A.m3.data(), d);
@@ -249,34 +273,34 @@ inline void grad_backward_state(const float *P, float *G, const GradDims &D, con
   // the weighted sum and the softmax
   for (int r = 0; r < n; ++r) {
     float acc = 0.0f;
-    for (int f = 0; f < F; ++f) acc = chain(dwf[f], centred(A.ft[(size_t)r * 256 + f], A.j[D.S + f]), acc);
+    for (int f = 0; f < F; ++f) acc = chain(dwf[f], centred(A.ft[(size_t)r * HW + f], A.j[D.S + f]), acc);
     A.s[r] = acc;
   }
   float m = 0.0f;
   for (int r = 0; r < n; ++r) m = chain(A.w[r], A.s[r], m);
   for (int r = 0; r < n; ++r) {
     A.s[r] = score_back(A.w[r], A.s[r], m);
-    for (int f = 0; f < F; ++f) A.ft[(size_t)r * 256 + f] = A.w[r] * dwf[f];
+    for (int f = 0; f < F; ++f) A.ft[(size_t)r * HW + f] = A.w[r] * dwf[f];
   }
   // mlp2
   for (int r = 0; r < n; ++r) {
-    float *b1 = &A.b1[(size_t)r * 256];
-    grad_linear(P, G, D, L_M2B, b1, &A.ft[(size_t)r * 256], d);
+    float *b1 = &A.b1[(size_t)r * HW];
+    grad_linear(P, G, D, L_M2B, b1, &A.ft[(size_t)r * HW], d);
     for (int k = 0; k < D.K[L_M2B]; ++k) b1[k] = grad_relu_back(b1[k], d[k]);
   }
-  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_M2A, &A.h1[(size_t)r * 256], &A.b1[(size_t)r * 256], nullptr);
+  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_M2A, &A.h1[(size_t)r * HW], &A.b1[(size_t)r * HW], nullptr);
   // attention
   for (int r = 0; r < n; ++r) {
-    float *c2 = &A.c2[(size_t)r * 256];
+    float *c2 = &A.c2[(size_t)r * HW];
     grad_linear(P, G, D, L_ATC, c2, &A.s[r], d);
     for (int k = 0; k < D.K[L_ATC]; ++k) c2[k] = grad_relu_back(c2[k], d[k]);
   }
   for (int r = 0; r < n; ++r) {
-    float *c1 = &A.c1[(size_t)r * 256];
-    grad_linear(P, G, D, L_ATB, c1, &A.c2[(size_t)r * 256], d);
+    float *c1 = &A.c1[(size_t)r * HW];
+    grad_linear(P, G, D, L_ATB, c1, &A.c2[(size_t)r * HW], d);
     for (int k = 0; k < D.K[L_ATB]; ++k) c1[k] = grad_relu_back(c1[k], d[k]);
   }
-  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_ATA, &A.xa[(size_t)r * 512], &A.c1[(size_t)r * 256], nullptr);
+  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_ATA, &A.xa[(size_t)r * 2 * HW], &A.c1[(size_t)r * HW], nullptr);
   // h1: mlp2's layer 0, attention's layer 0 and the mean
   const float *W2 = P + D.at[L_M2A], *W4 = P + D.at[L_ATA];
   const int O2 = D.O[L_M2A], Op2 = D.Op[L_M2A], O4 = D.O[L_ATA], Op4 = D.Op[L_ATA];
@@ -286,26 +310,26 @@ inline void grad_backward_state(const float *P, float *G, const GradDims &D, con
       float dg = 0.0f;
       for (int r = 0; r < n; ++r) {
         float acc = 0.0f;
-        for (int u = 0; u < O4; ++u) acc = chain(W4[(size_t)(H + k) * Op4 + u], A.c1[(size_t)r * 256 + u], acc);
+        for (int u = 0; u < O4; ++u) acc = chain(W4[(size_t)(H + k) * Op4 + u], A.c1[(size_t)r * HW + u], acc);
         dg = dg + acc;
       }
       dm[k] = over_rows(dg, n);
     }
   for (int r = 0; r < n; ++r) {  // L_M2A and L_ATA have read h1 (xa holds its copy): its delta takes its place
-    float *h1 = &A.h1[(size_t)r * 256];
+    float *h1 = &A.h1[(size_t)r * HW];
     for (int k = 0; k < H; ++k) {
       float d2 = 0.0f, d4 = 0.0f;
-      for (int u = 0; u < O2; ++u) d2 = chain(W2[(size_t)k * Op2 + u], A.b1[(size_t)r * 256 + u], d2);
-      for (int u = 0; u < O4; ++u) d4 = chain(W4[(size_t)k * Op4 + u], A.c1[(size_t)r * 256 + u], d4);
+      for (int u = 0; u < O2; ++u) d2 = chain(W2[(size_t)k * Op2 + u], A.b1[(size_t)r * HW + u], d2);
+      for (int u = 0; u < O4; ++u) d4 = chain(W4[(size_t)k * Op4 + u], A.c1[(size_t)r * HW + u], d4);
       h1[k] = h1_back(h1[k], d2, d4, dm[k], D.global);
     }
   }
   for (int r = 0; r < n; ++r) {
-    float *a1 = &A.a1[(size_t)r * 256];
-    grad_linear(P, G, D, L_M1B, a1, &A.h1[(size_t)r * 256], d);
+    float *a1 = &A.a1[(size_t)r * HW];
+    grad_linear(P, G, D, L_M1B, a1, &A.h1[(size_t)r * HW], d);
     for (int k = 0; k < D.K[L_M1B]; ++k) a1[k] = grad_relu_back(a1[k], d[k]);
   }
-  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_M1A, x + (size_t)r * D.T, &A.a1[(size_t)r * 256], nullptr);
+  for (int r = 0; r < n; ++r) grad_linear(P, G, D, L_M1A, x + (size_t)r * D.T, &A.a1[(size_t)r * HW], nullptr);
 }
 
 // The whole batch, serially: rows [B][R][T], n_valid [B] or null = R, target [B], sample_mask [B] or null -> grad

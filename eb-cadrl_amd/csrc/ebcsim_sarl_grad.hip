@@ -8,16 +8,14 @@
 
 #include "ebc_grad_host.h"
 #include "ebc_sarl_grad.h"
+#include "ebc_sarl_net.h"
 
 namespace {
 
 using ebc_host::fail;
+using ebc_host::SarlNet;  // ebc_sarl_net.h: also what ebc_sarl_net_create_layers makes (ebcsim_sarl_grad_layers.hip)
 
 constexpr int kMaxChunksPerLaunch = EBC_SARL_GRAD_MAX_CHUNKS;
-
-struct SarlNet : ebc_host::GradNet, ebc_host::GradPasses {
-  ebc_sarl::GradDims D;
-};
 
 }  // namespace
 
@@ -85,6 +83,9 @@ extern "C" int ebc_sarl_net_grad_max_rows(void *net, int *rows_out) {
 }
 
 extern "C" int ebc_sarl_net_grad_max_rows_at(void *net, int states_per_pass, int *rows_out) {
+  if (net && static_cast<SarlNet *>(net)->layers_grad && ebc_host::GradPasses::pass_index(states_per_pass) >= 0)
+    return fail(EBC_ERR_UNSUPPORTED, "ebc_sarl_net_grad_max_rows_at: states_per_pass " + std::to_string(states_per_pass) +
+                                         ": the layer form has no passes");
   return ebc_host::grad_max_rows_at(static_cast<SarlNet *>(net), states_per_pass, rows_out, "ebc_sarl_net_grad_max_rows_at");
 }
 
@@ -101,6 +102,7 @@ extern "C" int ebc_sarl_grad(void *net, void *stream, const EbcSarlGradArgs *arg
   if (!args || args->struct_size != sizeof(EbcSarlGradArgs)) return fail(EBC_ERR_INVALID, "EbcSarlGradArgs.struct_size");
   if (!args->grad || !args->loss_sum || !args->count || args->B < 0) return fail(EBC_ERR_INVALID, "ebc_sarl_grad: grad, loss_sum, count, B");
   if (args->B > 0 && (!args->rows || !args->target)) return fail(EBC_ERR_INVALID, "ebc_sarl_grad: rows, target");
+  if (static_cast<SarlNet *>(net)->layers_grad) return static_cast<SarlNet *>(net)->layers_grad(static_cast<SarlNet *>(net), stream, args);
   const int sp = args->states_per_pass;  // 0: the whole chunk at once, today's kernel
   if (int rc = ebc_host::GradPasses::check(sp, "ebc_sarl_grad")) return rc;
   SarlNet *n = static_cast<SarlNet *>(net);

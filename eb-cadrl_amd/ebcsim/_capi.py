@@ -95,6 +95,7 @@ SYMBOLS = {
     "ebc_cadrl_grad": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sarl_net_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_sarl_net_create_om": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "ebc_sarl_net_create_layers": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "ebc_sarl_net_destroy": (C.c_int, [C.c_void_p]),
     "ebc_sarl_net_packed_floats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64)]),
     "ebc_sarl_net_get_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -17,7 +17,12 @@ deciding.
 
 OM-SARL (om_width = W > 0, run_sarl_training(om=spec)): mlp1's first layer takes T + W inputs, the kernel's network is
 ebc_sarl_net_create_om's, the stored states are the wide ones (BatchedEnv.observe_wide_device, ebc_step_k_om) and
-DeviceSarlPolicy(om=spec) decides.  The width of the maps is not in a state_dict (only T + W is): it is given explicitly."""
+DeviceSarlPolicy(om=spec) decides.  The width of the maps is not in a state_dict (only T + W is): it is given explicitly.
+
+Two forms of the kernel compute the same gradient, byte for byte (SarlNet(form=...), SarlFormTrainer(grad_form=...)): the
+chunk form (ebc_sarl_net_create: one workgroup per chunk of 4 states, everything in LDS, hidden layers up to 256, R up to
+what the LDS holds) and the layer form (ebc_sarl_net_create_layers: layer by layer over the batch on the float32 matrix
+instruction, hidden layers up to 640, R up to 128).  Both read and write the same packed image."""
 import collections
 import ctypes as C
 import os  # noqa: F401 (a public name of this module since its first version)
@@ -35,6 +40,8 @@ LAYER_KEYS = ("mlp1.0", "mlp1.2", "mlp2.0", "mlp2.2", "attention.0", "attention.
 STACKS = (("mlp1", 2), ("mlp2", 2), ("attention", 3), ("mlp3", 4))
 MAX_IN, MAX_WIDTH = 64, 256  # csrc/ebc_sarl_grad_rule.h
 MAX_OM, MAX_WIDE = 192, 224  # the same: the widest map behind a row, the widest row with its map
+MAX_WIDTH_LAYERS, MAX_ROWS_LAYERS = 640, 128  # the same: the layer form's widest hidden layer and most rows per state
+GRAD_FORMS = (None, "chunk", "layers", "auto")
 
 
 def _stack_keys(sd):
@@ -106,11 +113,16 @@ class SarlNet(grad_train.GradNet):
     """The kernel's network object (ebc_sarl_net_*): the packed image of a state_dict in device memory."""
     KIND, ARGS = "sarl", _abi.EbcSarlGradArgs
 
-    def __init__(self, sd, device_index, widths=None, self_state_dim=None, with_global_state=None, stack_layers=None, om_width=None):
+    def __init__(self, sd, device_index, widths=None, self_state_dim=None, with_global_state=None, stack_layers=None, om_width=None,
+                 form="chunk"):
         """widths / self_state_dim / with_global_state / stack_layers override what the state_dict says (the tests of the
         entry's refusals).  om_width: None = ebc_sarl_net_create; an int W = ebc_sarl_net_create_om, whose rotated width
-        is mlp1.0.weight.shape[1] - W (widths[0], when given, is that rotated width)."""
+        is mlp1.0.weight.shape[1] - W (widths[0], when given, is that rotated width).  form: "chunk" (those two entries) or
+        "layers" (ebc_sarl_net_create_layers, with om_width or 0): the same packed image, hidden layers up to 640."""
         from . import _capi
+        if form not in ("chunk", "layers"):
+            raise ValueError("SarlNet: form is 'chunk' or 'layers', got %r" % (form,))
+        self.form = form
         self._L = _capi.lib()
         keys = [k for ks in _stack_keys(sd).values() for k in ks]
         host = [(sd[k + ".weight"].detach().to("cpu", torch.float32).contiguous().numpy(),
@@ -134,7 +146,9 @@ class SarlNet(grad_train.GradNet):
         for i, (a, b) in enumerate(host):
             w.weight[i], w.bias[i] = a.ctypes.data, b.ctypes.data
         self._h = C.c_void_p()
-        if om_width is None:
+        if form == "layers":
+            _capi.check(self._L.ebc_sarl_net_create_layers(C.addressof(w), int(om_width or 0), int(device_index), C.byref(self._h)))
+        elif om_width is None:
             _capi.check(self._L.ebc_sarl_net_create(C.addressof(w), int(device_index), C.byref(self._h)))
         else:
             _capi.check(self._L.ebc_sarl_net_create_om(C.addressof(w), int(om_width), int(device_index), C.byref(self._h)))
@@ -152,6 +166,84 @@ class SarlNet(grad_train.GradNet):
                    states_per_pass)
 
 
+class _NoPasses(object):
+    """PassChoice's interface over a network of the layer form: every call is the default call."""
+
+    def __init__(self, net):
+        self.setting, self.whole_chunk = None, net.grad_max_rows()
+
+    def of(self, R):
+        return 0
+
+    def max_rows(self):
+        return self.whole_chunk
+
+
+class SarlFormChoice(object):
+    """SarlFormTrainer(grad_form="auto")'s network object: the chunk form's SarlNet where ebc_sarl_net_create(_om) takes the
+    network (`chunk`, else None) and the layer form's (`layers`), made the first time a call needs it — at once when there
+    is no chunk form — from current() -> (state_dict, flat packed weights on the device).  A call goes to the chunk form
+    where it exists and the batch's R fits its default call, else to the layer form; set_packed reaches both."""
+
+    def __init__(self, sd, device_index, om_width, current):
+        from . import _capi
+        self._index, self._om, self._current = device_index, om_width or None, current
+        self.chunk = self.layers = None
+        try:
+            self.chunk = SarlNet(sd, device_index, om_width=self._om)
+            self._chunk_rows = self.chunk.grad_max_rows()
+        except _capi.EbcError as e:
+            if e.code != _abi.ERR_UNSUPPORTED:
+                raise
+            self.layers = SarlNet(sd, device_index, om_width=self._om, form="layers")
+        self.form = "chunk" if self.chunk is not None else "layers"  # of the last call (before the first: of the first network)
+
+    def form_of(self, R):
+        return "chunk" if self.chunk is not None and R <= self._chunk_rows else "layers"
+
+    def of(self, R):
+        """The network object a call on states of R rows goes to."""
+        if self.form_of(R) == "chunk":
+            return self.chunk
+        if self.layers is None:
+            sd, flat = self._current()
+            self.layers = SarlNet(sd, self._index, om_width=self._om, form="layers")
+            self.layers.set_packed(flat)  # the master copy's bytes themselves
+        return self.layers
+
+    def grad(self, rows, *args, **kw):
+        net = self.of(int(rows.shape[1]))
+        self.form = net.form
+        net.grad(rows, *args, **kw)
+
+    def packed_floats(self):
+        return (self.chunk or self.layers).packed_floats()
+
+    def grad_max_rows(self, states_per_pass=0):
+        if states_per_pass:
+            raise NotImplementedError("SarlFormChoice: grad_form 'auto' takes no states_per_pass")
+        return MAX_ROWS_LAYERS
+
+    def get_packed(self, out):
+        return (self.chunk or self.layers).get_packed(out)
+
+    def set_packed(self, flat):
+        for net in (self.chunk, self.layers):
+            if net is not None:
+                net.set_packed(flat)
+
+
+def checked_grad_form(value, states_per_pass, who):
+    """A trainer's grad_form: None or "chunk" (the chunk form, today's object), "layers" or "auto"; the last two leave no
+    room for a states_per_pass: "layers" has no passes, and "auto" is another answer to the question it answers."""
+    if value not in GRAD_FORMS:
+        raise ValueError("%s: grad_form is None, 'chunk', 'layers' or 'auto', got %r" % (who, value))
+    if value in ("layers", "auto") and states_per_pass is not None:
+        raise ValueError("%s: grad_form %r takes no states_per_pass (got %r): %s" % (
+            who, value, states_per_pass, "the layer form has no passes" if value == "layers" else "they are two answers to the same question"))
+    return value
+
+
 class SarlTrainer(grad_train.PassTrainer):
     """module_or_state_dict: a SarlModule or a state_dict of the reference's keys (the starting weights).  optimizer:
     "sgd" (momentum 0.9), "adam" (rl/utils/trainer.py:24-45) or a callable params -> torch optimizer.  native: the kernel
@@ -159,7 +251,8 @@ class SarlTrainer(grad_train.PassTrainer):
     network's mlp1.0 then takes T + W inputs, T = widths[0] - W the rotated width (1 .. 64), W <= 192, T + W <= 224.
     states_per_pass (native only; native=False ignores it): None = the kernel's default call, the whole chunk of 4 states
     at once; 1, 2, 4 = that many states at a time, which takes more rows per state (SarlNet.grad_max_rows(S)) and gives
-    the same bytes; "auto" = per call the default call where the batch's R fits it, else the largest pass that holds R."""
+    the same bytes; "auto" = per call the default call where the batch's R fits it, else the largest pass that holds R.
+    This trainer's kernel is the chunk form; SarlFormTrainer below adds the choice of the layer form."""
 
     NAME, EXTRA, OTHER_SHAPE = "SarlTrainer", "attention", "another network shape"
 
@@ -197,6 +290,39 @@ class SarlTrainer(grad_train.PassTrainer):
         reads the count back).  value [B] float32 / attention [B, R] float32, when given, receive the states' values and
         softmax weights (native only)."""
         return self._loss_and_grad(rows, target, n_valid, mask, grad_scale, value, attention)
+
+
+class SarlFormTrainer(SarlTrainer):
+    """SarlTrainer with the choice of the kernel's form: its arguments, and grad_form (native only; native=False ignores
+    it): None or "chunk" = SarlTrainer's object, the chunk form, refusals included; "layers" = the layer form (hidden layers
+    up to 640, R up to 128; states_per_pass must be None); "auto" = per call the chunk form where ebc_sarl_net_create(_om)
+    takes the network and the batch's R fits its default call, else the layer form, whose network object is made the first
+    time it is needed and follows push_weights.  The rule is about capability, not speed: the bytes are the same on both
+    forms.  "auto" with a states_per_pass is a ValueError.  (A class of its own: SarlTrainer's constructor keeps its
+    signature.)"""
+
+    def __init__(self, module_or_state_dict, device="cpu", optimizer="sgd", lr=0.01, native=None, om_width=0, states_per_pass=None,
+                 grad_form=None):
+        self.grad_form = checked_grad_form(grad_form, states_per_pass, "SarlFormTrainer")
+        SarlTrainer.__init__(self, module_or_state_dict, device, optimizer, lr, native, om_width, states_per_pass)
+
+    def _new_net(self, sd, index):
+        """None / "chunk": PassTrainer's network object.  "layers": the layer form's.  "auto": both forms behind one object
+        (SarlFormChoice), which routes every call by its R."""
+        if self.grad_form in (None, "chunk"):
+            return grad_train.PassTrainer._new_net(self, sd, index)
+        if self.grad_form == "layers":
+            net = SarlNet(sd, index, om_width=self.om_width or None, form="layers")
+        else:
+            net = SarlFormChoice(sd, index, self.om_width, lambda: (self.state_dict(), self.flat.detach()))
+        self.passes = _NoPasses(net)
+        return net
+
+    def form_of(self, R):
+        """"chunk" or "layers": the form a native call on states of R rows takes."""
+        if self.grad_form == "auto":
+            return self.net.form_of(R) if self.net is not None else ("chunk" if max(self.widths[1:]) <= MAX_WIDTH else "layers")
+        return "layers" if self.grad_form == "layers" else "chunk"
 
 
 def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,

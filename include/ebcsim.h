@@ -984,6 +984,20 @@ int ebc_sarl_net_create(const EbcSarlNetWeights *weights, int device_id, void **
  * that K; ebc_sarl_grad on such a network takes args.T == T + W and ebc_sarl_net_grad_max_rows answers for the wide row.
  * om_width = 0 is ebc_sarl_net_create: the same network, packed image and bytes. */
 int ebc_sarl_net_create_om(const EbcSarlNetWeights *weights, int om_width, int device_id, void **net_out);
+/* The LAYER form of the same gradient (csrc/ebc_sarl_grad_layers.h), for the networks the chunk form does not hold: every
+ * hidden width 1 .. 640 (the reference's policy_x2 / x3 / x4 configs: 300, 400, 600); the rows' limits are those of
+ * ebc_sarl_net_create_om (input_dim 1 .. 64, om_width 0 .. 192, T + W <= 224), refusals by name as there.  The packed image
+ * is the same, and ebc_sarl_net_packed_floats / _get_packed / _set_packed / _destroy work on the object unchanged, so a
+ * flat weight tensor passes between the two forms' networks.  ebc_sarl_grad on such a network takes the same
+ * EbcSarlGradArgs and writes the same outputs, and the SAME BYTES as the chunk form where both take the network: it runs
+ * the rule layer by layer over runs of whole chunks (at most 65 536 row slots a run) on the float32 matrix instruction,
+ * which is a k-ordered fmaf chain per output, with every activation and delta in the network's scratch in device memory
+ * (about 0.45 GB at the x2 widths, 0.9 GB at x4, for a full run); a weight's chunks are added ascending in float64 by the one
+ * wave that owns it, across runs too.  Rows at or past n ARE read here, and enter nothing.  1 <= R <= 128
+ * (ebc_sarl_net_grad_max_rows), else EBC_ERR_UNSUPPORTED with nothing written.  states_per_pass must be 0: 4, 2 and 1 are
+ * EBC_ERR_UNSUPPORTED ("the layer form has no passes"), here and in ebc_sarl_net_grad_max_rows_at; any other value is
+ * EBC_ERR_INVALID.  About 45 short launches per run. */
+int ebc_sarl_net_create_layers(const EbcSarlNetWeights *weights, int om_width, int device_id, void **net_out);
 int ebc_sarl_net_destroy(void *net);
 int ebc_sarl_net_packed_floats(void *net, int64_t *floats_out);
 int ebc_sarl_net_get_packed(void *net, void *stream, float *dst_dev);

@@ -9,7 +9,7 @@ after RL.
     python3 tools/train_sarl.py --env-config eb-cadrl_amd/configs/sarl_a5.config \
         --policy-config eb-cadrl_amd/configs/policy_plain.config --device-scenes [--envs 256] [--il-steps 200] [--il-epochs 50]
         [--iterations 200] [--steps-per-iteration 4] [--train-batches 100] [--batch-size 100] [--cases 500]
-        [--weights start.pth] [--autograd] [--out sarl_model.pth]
+        [--weights start.pth] [--autograd] [--grad-form chunk|layers|auto] [--out sarl_model.pth]
 
 The tool's defaults are a SHORT schedule, not the reference's: 200 RL rounds with epsilon decayed over 150 of them and the
 target network refreshed every 10, where run_sarl_training and the reference's train.config use 4000 and 50 for runs of
@@ -17,6 +17,10 @@ target network refreshed every 10, where run_sarl_training and the reference's t
 
 A reward, value target or loss that is not finite stops the run with an error before an optimizer step sees it; --out is
 written only by a run that ended.
+
+Wider networks ([sarl] mlp1_dims ... of the policy config above 256, eb-cadrl_amd/configs/policy_x2.config): --grad-form
+layers or auto; the chunk form (the default) refuses them.  auto takes the chunk form where it holds the network and the
+scene's rows, else the layer form; the bytes are the same.
 
 OM-SARL: a policy config with [sarl] with_om = true (eb-cadrl_amd/configs/policy_om.config) trains the network whose mlp1
 takes T + cell_num^2 * om_channel_size columns, on the wide states the device builds (ebc_observe_wide, ebc_step_k_om),
@@ -63,6 +67,9 @@ def main():
     ap.add_argument("--states-per-pass", default=None, choices=["auto", "1", "2", "4"],
                     help="the kernel runs a chunk's 4 states that many at a time, which takes more rows per state (the same bytes); "
                          "auto: the largest that holds the scene's rows.  Default: the whole chunk at once")
+    ap.add_argument("--grad-form", default=None, choices=["chunk", "layers", "auto"],
+                    help="the kernel's form: chunk (default; hidden layers up to 256), layers (up to 640, R up to 128) or auto (chunk "
+                         "where it takes the network and the rows, else layers); the same bytes")
     ap.add_argument("--out", default="sarl_model.pth")
     args = ap.parse_args()
     if not args.device_scenes:
@@ -74,7 +81,7 @@ def main():
     from ebcsim.batched import BatchedEnv
     from ebcsim.occupancy import OccupancySpec
     from ebcsim.sarl import DeviceSarlPolicy, SarlValueNet
-    from ebcsim.sarl_train import SarlTrainer, run_sarl_training
+    from ebcsim.sarl_train import SarlFormTrainer, SarlTrainer, run_sarl_training
     from ebcsim.train import SarlModule, evaluate
     cfg, pol = configparser.RawConfigParser(), configparser.RawConfigParser()
     cfg.read(args.env_config)
@@ -121,8 +128,8 @@ def main():
     if args.weights:
         start.load_state_dict(torch.load(args.weights, map_location="cpu"), strict=True)
     spp = args.states_per_pass if args.states_per_pass in (None, "auto") else int(args.states_per_pass)
-    trainer = SarlTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd,
-                          om_width=om.width if om else 0, states_per_pass=spp)
+    trainer = SarlFormTrainer(start, device="cuda:0", optimizer=args.optimizer, lr=args.il_lr, native=not args.autograd,
+                          om_width=om.width if om else 0, states_per_pass=spp, grad_form=args.grad_form)
     g = torch.Generator(device="cuda:0").manual_seed(args.seed)
     common = dict(il_learning_rate=args.il_lr, il_safety_space=args.safety_space, rl_learning_rate=args.rl_lr, steps_per_iteration=args.steps_per_iteration,
                   train_batches=args.train_batches, batch_size=args.batch_size, capacity=args.capacity, epsilon_start=args.epsilon_start,
