@@ -11,6 +11,7 @@
 #include "ebc_host.h"
 #include "ebc_value_net.h"
 #include "ebc_vn_stream_api.h"
+#include "ebc_vn_wide.h"
 
 using ebc_host::fail;
 
@@ -38,6 +39,7 @@ struct Mlp2 {
   int in_frag = 0;           // EBC_MLP_IN_FRAGMENTS: the first layer packed in accumulator k order (input = fragments)
   float *final_w = nullptr;  // optional third layer with one output
   float final_b = 0.0f;
+  void *wide = nullptr;      // ebc_mlp2_create_wide: the block runs on the single-layer kernels of ebc_vn_wide.h (its scratch)
   std::vector<void *> allocs;
 };
 
@@ -85,7 +87,7 @@ int pack_layer(Mlp2 *m, const float *W, const float *b, int out, int in, bool ac
 // W [out][in] -> transposed [in][out padded to 64], float32 as it is
 int pack_f32(Mlp2 *m, const float *W, const float *b, int out, int in, ebc::F32Layer *L) {
   const int out_pad = (out + 63) / 64 * 64;
-  if (out_pad > 64 * EBC_F32_MAXU) return fail(EBC_ERR_UNSUPPORTED, "mlp2: more than 320 units in a layer");
+  if (!m->wide && out_pad > 64 * EBC_F32_MAXU) return fail(EBC_ERR_UNSUPPORTED, "mlp2: more than 320 units in a layer");
   std::vector<float> wt((size_t)in * out_pad, 0.0f), bias((size_t)out_pad, 0.0f);
   for (int o = 0; o < out; ++o) {
     bias[o] = b[o];
@@ -164,6 +166,11 @@ int mlp2_dispatch(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu
 #endif
 }
 
+ebc_host::VnWideCall wide_call(const Mlp2 *m, hipStream_t st, const float *x, int M, int relu_out, const float *row_bias, int group_rows,
+                               float *y) {
+  return {m->device, st, m->K0, m->H, m->O, M, relu_out, x, row_bias, group_rows, m->final_w, m->final_b, y};
+}
+
 }  // namespace
 
 extern "C" {
@@ -173,10 +180,28 @@ int ebc_mlp2_create(int device_id, int K0, int H, int O, const float *w1, const 
   return ebc_mlp2_create_ex(device_id, K0, H, O, w1, b1, w2, b2, w3, b3, 0, out);
 }
 
+static int mlp2_create(int device_id, int K0, int H, int O, const float *w1, const float *b1, const float *w2, const float *b2,
+                       const float *w3, const float *b3, int flags, bool wide, void **out);
+
 int ebc_mlp2_create_ex(int device_id, int K0, int H, int O, const float *w1, const float *b1, const float *w2,
                        const float *b2, const float *w3, const float *b3, int flags, void **out) {
   if (!w1 || !b1 || !w2 || !b2 || !out) return fail(EBC_ERR_INVALID, "null argument");
   if (K0 <= 0 || H <= 0 || O <= 0 || K0 > 224 || O > 224 || H > 320) return fail(EBC_ERR_UNSUPPORTED, "mlp2 dimensions");
+  return mlp2_create(device_id, K0, H, O, w1, b1, w2, b2, w3, b3, flags, false, out);
+}
+
+int ebc_mlp2_create_wide(int device_id, int K0, int H, int O, const float *w1, const float *b1, const float *w2,
+                         const float *b2, const float *w3, const float *b3, int flags, void **out) {
+  if (!w1 || !b1 || !w2 || !b2 || !out) return fail(EBC_ERR_INVALID, "null argument");
+  if (K0 < 1 || H < 1 || O < 1 || K0 > EBC_VNW_MAX || H > EBC_VNW_MAX || O > EBC_VNW_MAX)
+    return fail(EBC_ERR_UNSUPPORTED, "wide mlp2 block: K0, H and O must each lie in 1 .. 640");
+  if (flags & EBC_MLP_IN_FRAGMENTS) return fail(EBC_ERR_UNSUPPORTED, "wide mlp2 block: EBC_MLP_IN_FRAGMENTS is not taken (rows in, rows out)");
+  if (flags) return fail(EBC_ERR_INVALID, "wide mlp2 block: unknown flags");
+  return mlp2_create(device_id, K0, H, O, w1, b1, w2, b2, w3, b3, 0, true, out);
+}
+
+static int mlp2_create(int device_id, int K0, int H, int O, const float *w1, const float *b1, const float *w2, const float *b2,
+                       const float *w3, const float *b3, int flags, bool wide, void **out) {
   int count = 0;
   if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
     return fail(EBC_ERR_DEVICE, "no HIP device: libebcsim has no CPU fallback");
@@ -185,6 +210,7 @@ int ebc_mlp2_create_ex(int device_id, int K0, int H, int O, const float *w1, con
   Mlp2 *m = new Mlp2();
   m->device = device_id; m->K0 = K0; m->H = H; m->O = O;
   m->in_frag = (flags & EBC_MLP_IN_FRAGMENTS) ? 1 : 0;
+  if (wide) m->wide = ebc_host::vn_wide_state_new();
   int rc = pack_layer(m, w1, b1, H, K0, m->in_frag != 0, &m->L1);
   if (rc == EBC_OK) rc = pack_layer(m, w2, b2, O, H, true, &m->L2);
   if (rc == EBC_OK) rc = pack_f32(m, w1, b1, H, K0, &m->F1);
@@ -199,6 +225,7 @@ int ebc_mlp2_create_ex(int device_id, int K0, int H, int O, const float *w1, con
   }
   if (rc != EBC_OK) {
     for (void *ptr : m->allocs) (void)hipFree(ptr);
+    ebc_host::vn_wide_state_free(m->wide);
     delete m;
     return rc;
   }
@@ -214,6 +241,7 @@ int ebc_mlp2_forward(void *mlp, void *stream, const float *x, int M, int relu_ou
   if (M == 0) return EBC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = (hipStream_t)stream;
+  if (m->wide) return ebc_host::vn_wide_forward(m->wide, wide_call(m, st, x, M, relu_out, row_bias, group_rows, y), m->L1, m->L2);
   const ebc::MlpExtra ex = {row_bias, group_rows, m->H, m->final_w, m->final_b, nullptr, nullptr, 0, 1};
   return mlp2_dispatch(m, st, x, M, relu_out, y, ex);
 }
@@ -256,6 +284,10 @@ int ebc_mlp2_forward_f32(void *mlp, void *stream, const float *x, int M, int rel
   if (M == 0) return EBC_OK;
   HIP_TRY(hipSetDevice(m->device));
   hipStream_t st = (hipStream_t)stream;
+  if (m->wide) {
+    const ebc::WideF32Layer f1 = {m->F1.wt, m->F1.b, m->F1.in, m->F1.out, m->F1.out_pad}, f2 = {m->F2.wt, m->F2.b, m->F2.in, m->F2.out, m->F2.out_pad};
+    return ebc_host::vn_wide_forward_f32(m->wide, wide_call(m, st, x, M, relu_out, row_bias, group_rows, y), f1, f2);
+  }
   // few rows: a workgroup per 32-row tile, its waves sharing the tile (the form a decision's re-evaluation gets); many
   // rows: four tiles per workgroup walking the hidden tiles together on weights staged in LDS.
   if (M <= EBC_F32_TILE_ROWS) {
@@ -293,6 +325,7 @@ int ebc_mlp2_forward_reduce(void *mlp, void *stream, const float *x, int M, int 
                             int group_rows, float *y, int seg_rows, const float *row_weight, double *partial) {
   Mlp2 *m = (Mlp2 *)mlp;
   if (!m || !x || !partial || M < 0) return fail(EBC_ERR_INVALID, "mlp2 forward_reduce arguments");
+  if (m->wide) return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_reduce: a wide block has no tile epilogue (no partial sums)");
   if (row_bias && group_rows <= 0) return fail(EBC_ERR_INVALID, "mlp2: group_rows");
   if (m->final_w) return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_reduce: a block with a one-output third layer has no [M][O] rows");
   if (seg_rows < 16) return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_reduce: groups of fewer than 16 rows (a tile would touch more than three)");
@@ -307,6 +340,14 @@ int ebc_mlp2_forward_ex(void *mlp, void *stream, const EbcMlpArgs *a) {
   Mlp2 *m = (Mlp2 *)mlp;
   if (!m || !a || a->struct_size != sizeof(EbcMlpArgs)) return fail(EBC_ERR_INVALID, "EbcMlpArgs.struct_size");
   if (a->M < 0 || (!a->x && !a->frag_in)) return fail(EBC_ERR_INVALID, "mlp2 forward_ex: no input");
+  if (m->wide) {  // plain rows only, which is ebc_mlp2_forward
+    if (a->frag_in || a->frag_out) return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_ex: a wide block takes and leaves rows, not fragments (frag_in / frag_out)");
+    if (a->partial || a->seg_rows || a->row_weight)
+      return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_ex: a wide block has no tile epilogue (partial / seg_rows / row_weight)");
+    if (a->flags & EBC_MLP_GENERAL_KERNEL) return fail(EBC_ERR_UNSUPPORTED, "mlp2 forward_ex: EBC_MLP_GENERAL_KERNEL on a wide block (it has one kernel)");
+    if (!a->y) return fail(EBC_ERR_INVALID, "mlp2 forward_ex: no output");
+    return ebc_mlp2_forward(mlp, stream, a->x, a->M, a->relu_out, a->row_bias, a->group_rows, a->y);
+  }
   if ((a->frag_in != nullptr) != (m->in_frag != 0))
     return fail(EBC_ERR_INVALID, "mlp2 forward_ex: fragment input needs a block created with EBC_MLP_IN_FRAGMENTS, row input one without");
   if (a->row_bias && a->group_rows <= 0) return fail(EBC_ERR_INVALID, "mlp2: group_rows");
@@ -388,6 +429,7 @@ int ebc_mlp2_destroy(void *mlp) {
   Mlp2 *m = (Mlp2 *)mlp;
   if (!m) return EBC_OK;
   for (void *ptr : m->allocs) (void)hipFree(ptr);
+  ebc_host::vn_wide_state_free(m->wide);
   delete m;
   return EBC_OK;
 }

@@ -144,6 +144,7 @@ LOCAL_MAP_MAX_DIM = 128
 
 MLP_IN_FRAGMENTS = 1
 MLP_GENERAL_KERNEL = 1
+MLP_WIDE_MAX = 640  # K0, H, O of ebc_mlp2_create_wide
 
 
 class EbcMlpArgs(C.Structure):

@@ -26,9 +26,31 @@ def _ptr(t):
 class Mlp2Block(object):
     """A two-layer block on the bf16 matrix cores with split operands (libebcsim ebc_mlp2_*)."""
 
-    def __init__(self, layers, device_index, final=None, in_fragments=False):
+    WIDE_MAX = _abi.MLP_WIDE_MAX  # K0, H, O of a wide block (ebc_mlp2_create_wide)
+    WIDE_ROWS_PER_WORKGROUP = 256  # rows a workgroup of the wide block's kernel owns (EBC_VNW_ROWS)
+
+    @staticmethod
+    def fits(K0, H, O):
+        """What ebc_mlp2_create_ex takes: inputs and outputs of up to 7 tiles, a hidden layer of up to 10."""
+        return 1 <= K0 <= 224 and 1 <= H <= 320 and 1 <= O <= 224
+
+    @staticmethod
+    def fits_wide(K0, H, O):
+        """What ebc_mlp2_create_wide takes."""
+        return all(1 <= d <= Mlp2Block.WIDE_MAX for d in (K0, H, O))
+
+    @staticmethod
+    def has_tile_epilogue(K0, O, wide=False):
+        """What ebc_mlp2_forward_reduce / _ex ask of a block whose rows leave through the tile epilogue (partial sums,
+        fragments): O a multiple of 4 and more than 1 + 1 tiles (the smallest block has no LDS tile per wave to park one);
+        a wide block has none."""
+        return not wide and O % 4 == 0 and (K0 + 31) // 32 + (O + 31) // 32 >= 3
+
+    def __init__(self, layers, device_index, final=None, in_fragments=False, wide=False):
         """layers: [(w1, b1), (w2, b2)]; final: optional (w3 [1, O], b3 [1]) third layer with one output.
-        in_fragments: the block's input is the fragment tensor another block left with `frag_out` (ebc_mlp2_forward_ex)."""
+        in_fragments: the block's input is the fragment tensor another block left with `frag_out` (ebc_mlp2_forward_ex).
+        wide: the wide block (ebc_mlp2_create_wide: K0, H, O up to 640; rows in, rows out — no fragments, no tile
+        epilogue: reduce and forward_ex with those arguments raise the library's error)."""
         (w1, b1), (w2, b2) = layers
         self._L = _capi.lib()
         self.K0, self.H, self.O = int(w1.shape[1]), int(w1.shape[0]), int(w2.shape[0])
@@ -39,14 +61,14 @@ class Mlp2Block(object):
                      final[1].detach().to("cpu", torch.float32).reshape(-1).contiguous().numpy()]
         self._h = C.c_void_p()
         self.in_fragments = bool(in_fragments)
-        # what ebc_mlp2_forward_reduce / _ex ask of a block whose rows leave through the tile epilogue (partial sums,
-        # fragments): O a multiple of 4 and more than 1 + 1 tiles (the smallest block has no LDS tile per wave to park one)
-        self.tile_epilogue = self.O % 4 == 0 and (self.K0 + 31) // 32 + (self.O + 31) // 32 >= 3
-        _capi.check(self._L.ebc_mlp2_create_ex(int(device_index), self.K0, self.H, self.O, host[0].ctypes.data,
-                                               host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data,
-                                               host[4].ctypes.data if final is not None else None,
-                                               host[5].ctypes.data if final is not None else None,
-                                               _abi.MLP_IN_FRAGMENTS if in_fragments else 0, C.byref(self._h)))
+        self.wide = bool(wide)
+        self.tile_epilogue = self.has_tile_epilogue(self.K0, self.O, wide)
+        create = self._L.ebc_mlp2_create_wide if wide else self._L.ebc_mlp2_create_ex  # (the wide entry refuses in_fragments)
+        _capi.check(create(int(device_index), self.K0, self.H, self.O, host[0].ctypes.data,
+                           host[1].ctypes.data, host[2].ctypes.data, host[3].ctypes.data,
+                           host[4].ctypes.data if final is not None else None,
+                           host[5].ctypes.data if final is not None else None,
+                           _abi.MLP_IN_FRAGMENTS if in_fragments else 0, C.byref(self._h)))
 
     @staticmethod
     def frag_buffer(M, width, device):

@@ -87,6 +87,47 @@ def select_path(net, device_type, frag_handoff, native_exact, R, T, exact, want_
     return "exact_mlp1" if T > 32 else "torch"  # rows wider than one input tile: mlp1 stays in the library
 
 
+def block_kind(K0, H, O, wide):
+    """How a two-layer stack K0 -> H -> O becomes a libebcsim block: "narrow" (ebc_mlp2_create_ex, wherever it fits that
+    entry's limits — also in a network that asks for wide blocks), "wide" (ebc_mlp2_create_wide, only when asked for)
+    or None."""
+    if Mlp2Block.fits(K0, H, O):
+        return "narrow"
+    return "wide" if wide and Mlp2Block.fits_wide(K0, H, O) else None
+
+
+def plan_blocks(mlp1, mlp2, attention, mlp3, wide):
+    """The blocks of a network from its layers' shapes alone ((out, in) per layer and stack): None when the blocks do
+    not apply, else the kinds (block_kind) of [mlp1, mlp2, attention, mlp3[:2], mlp3[2:4]] — as many of the last two as
+    exist as blocks — and of the gterm block (None: torch).  No device work."""
+    if not (len(mlp1) == 2 and len(mlp2) == 2 and len(attention) == 3 and attention[2][0] == 1):
+        return None
+    H1 = mlp1[-1][0]
+
+    def kind(st):
+        return block_kind(st[0][1], st[0][0], st[1][0], wide)
+    kinds = [kind(mlp1), kind(mlp2), block_kind(H1, attention[0][0], attention[1][0], wide)]
+    if None in kinds:
+        return None
+    if len(mlp3) >= 3 and kind(mlp3[:2]):
+        kinds.append(kind(mlp3[:2]))
+        if len(mlp3) == 4 and kind(mlp3[2:4]):
+            kinds.append(kind(mlp3[2:4]))
+    return kinds, block_kind(H1, H1, attention[0][0], wide)
+
+
+def plan_facts(plan, mlp1, mlp2, with_global_state=True):
+    """The PathFacts of a network whose blocks follow `plan` (plan_blocks; None: no blocks) — what _native_blocks reads
+    off the blocks it has built.  mlp1, mlp2: the stacks' (out, in) per layer.  No device work."""
+    if plan is None:
+        return PathFacts(with_global_state, 0, 0, 0, False, False, False, False)
+    kinds, gterm_kind = plan
+    return PathFacts(with_global_state, len(kinds), mlp1[1][0], mlp2[1][0],
+                     Mlp2Block.has_tile_epilogue(mlp1[0][1], mlp1[1][0], kinds[0] == "wide"),
+                     Mlp2Block.has_tile_epilogue(mlp2[0][1], mlp2[1][0], kinds[1] == "wide"),
+                     gterm_kind is not None, "wide" not in kinds[:3])
+
+
 def _attention_weights(scores, n_valid):
     """The reference's masked softmax (sarl.py:69-71) over the rows that exist: scores [B, R] -> weights [B, R]."""
     e = torch.exp(scores) * (scores != 0).to(scores.dtype)
@@ -128,11 +169,14 @@ def chunk_values(forward, rows, n_valid, chunk_pairs, side_streams=None):
 class SarlValueNet(object):
     """rl/policy/sarl.py:9-82 (ValueNetwork), weights from its state_dict."""
 
-    def __init__(self, state_dict, device="cpu", with_global_state=True, self_state_dim=6, dtype=torch.float32):
+    def __init__(self, state_dict, device="cpu", with_global_state=True, self_state_dim=6, dtype=torch.float32, wide=False):
         """dtype: torch.float32 reproduces the reference's values (2e-4); torch.bfloat16 runs the
         GEMMs on the bf16 matrix cores: measured on MI355X 2.3x faster per decision, but values move by
         up to 0.2 and only 63 % of the envs keep the fp32 action (positions lose their digits in bf16
-        inputs) -- an experiment, not a parity path."""
+        inputs) -- an experiment, not a parity path.
+        wide: stacks wider than the two-layer block takes (up to 640 units: the reference's policy_x3 / policy_x4)
+        become wide blocks (ebc_mlp2_create_wide) instead of sending the whole network to torch; stacks that fit the
+        narrow block stay what they are."""
         def stack(prefix):
             idx = sorted({int(k.split(".")[1]) for k in state_dict if k.startswith(prefix + ".")})
             return [(state_dict["%s.%d.weight" % (prefix, i)].to(device=device, dtype=dtype),
@@ -140,21 +184,22 @@ class SarlValueNet(object):
                     for i in idx]
         # the blocks are built on first use: (mlp1, mlp2, attention[1:], mlp3 halves) as fused two-layer blocks
         self._init(stack("mlp1"), stack("mlp2"), stack("attention"), stack("mlp3"), with_global_state, self_state_dim,
-                   torch.device(device), dtype, build_on_first_use=True)
+                   torch.device(device), dtype, build_on_first_use=True, wide=wide)
 
     @classmethod
-    def from_stacks(cls, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, native=False):
+    def from_stacks(cls, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, native=False, wide=False):
         """A float32 network on the caller's tensors ([(weight, bias), ...] per stack: a training module's parameters,
         which change under it).  Packed copies only on request: native builds the blocks from the current weights on a
         HIP device (enable_native), refresh_native() re-packs them after the weights have changed."""
         net = cls.__new__(cls)
         net._init(mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, torch.device(device), torch.float32,
-                  build_on_first_use=False)
+                  build_on_first_use=False, wide=wide)
         if native and net.device.type == "cuda":
             net.enable_native()
         return net
 
-    def _init(self, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, dtype, build_on_first_use):
+    def _init(self, mlp1, mlp2, attention, mlp3, with_global_state, self_state_dim, device, dtype, build_on_first_use, wide=False):
+        self.wide = bool(wide)
         self.mlp1, self.mlp2, self.attention, self.mlp3 = mlp1, mlp2, attention, mlp3
         self.with_global_state, self.self_state_dim = with_global_state, self_state_dim
         self.input_dim = mlp1[0][0].shape[1]
@@ -175,35 +220,38 @@ class SarlValueNet(object):
         """(layers, final) of every libebcsim block of this network, from its CURRENT tensors, or None when the blocks
         do not apply: [mlp1, mlp2, attention (h1 half of layer 0 + layer 1, layer 2 as the one-output tail),
         mlp3[:2], mlp3[2:4]] and the mean-state half of attention layer 0 as a block of its own."""
-        ok = (self.device.type == "cuda" and self.dtype == torch.float32 and len(self.mlp1) == 2
-              and len(self.mlp2) == 2 and len(self.attention) == 3 and self.with_global_state)
-        if not ok:
+        plan = self._block_kinds()
+        if plan is None:
             return None
+        kinds, gterm_kind = plan
         H = self.mlp1[-1][0].shape[0]
         # attention = layer 0 on cat([h1, g]) | layer 1 | layer 2 (one output): the h1 half of layer 0
         # and layer 1 form the block, g's half enters as a per-pair term, layer 2 is the block's tail
         att = [(self.attention[0][0][:, :H], torch.zeros_like(self.attention[0][1])), self.attention[1]]
-        stacks = (self.mlp1, self.mlp2, att)
-
-        def fits(st):  # what ebc_mlp2_create_ex takes: inputs and outputs of up to 7 tiles, a hidden layer of up to 10
-            return st[0][0].shape[1] <= 224 and st[0][0].shape[0] <= 320 and st[1][0].shape[0] <= 224
-        if not (self.attention[2][0].shape[0] == 1 and all(fits(st) for st in stacks)):
-            return None
         specs = [(self.mlp1, None), (self.mlp2, None), (att, self.attention[2])]
         # mlp3's first two layers (the joint vector's widest ones) as a fourth block; its tail
         # (the reference's 200 -> 200 -> 1) stays with torch unless it is a two-layer block too
-        if len(self.mlp3) >= 3 and fits(self.mlp3[:2]):
+        if len(kinds) > 3:
             specs.append((self.mlp3[:2], None))
-            if len(self.mlp3) == 4 and fits(self.mlp3[2:4]):
+            if len(kinds) > 4:
                 specs.append((self.mlp3[2:4], None))
         # the mean state's half of attention layer 0 (one 200 x 200 layer per PAIR) as a block too: the mean of
         # ReLU outputs is >= 0, so relu(I g) = g and [I | w0[:, H:]] is that layer in the two-layer form
         gterm = None
-        if self.attention[0][0].shape[0] <= 224:
+        if gterm_kind is not None:
             eye = torch.eye(H, dtype=torch.float32, device=self.device)
             gterm = ([(eye, torch.zeros(H, dtype=torch.float32, device=self.device)),
                       (self.attention[0][0][:, H:], self.attention[0][1])], None)
         return specs, gterm
+
+    def _block_kinds(self):
+        """plan_blocks of this network (which entry makes each block), or None when the blocks do not apply."""
+        if not (self.device.type == "cuda" and self.dtype == torch.float32 and self.with_global_state):
+            return None
+
+        def shapes(st):
+            return [tuple(w.shape) for w, _ in st]
+        return plan_blocks(shapes(self.mlp1), shapes(self.mlp2), shapes(self.attention), shapes(self.mlp3), self.wide)
 
     def _native_blocks(self):
         """The two-layer stacks of the network as libebcsim blocks (inference on a HIP device,
@@ -214,11 +262,15 @@ class SarlValueNet(object):
                 idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
                 # the shapes were checked above: a failure from here on is a HIP error and is raised, never a silent torch path
                 specs, gterm = spec
-                self._gterm_block = None if gterm is None else Mlp2Block(gterm[0], idx)
-                self._native = nat = tuple(Mlp2Block(layers, idx, final=final) for layers, final in specs)
+                kinds, gterm_kind = self._block_kinds()
+                self._gterm_block = None if gterm is None else Mlp2Block(gterm[0], idx, wide=gterm_kind == "wide")
+                self._native = nat = tuple(Mlp2Block(layers, idx, final=final, wide=kind == "wide")
+                                           for (layers, final), kind in zip(specs, kinds))
                 # the two consumers of h1 once more, taking it as the fragments mlp1 leaves (no transposition, no splitting
                 # in their input phase): mlp2 and the attention stack
-                self._native_frag = tuple(Mlp2Block(layers, idx, final=final, in_fragments=True) for layers, final in specs[1:3])
+                # (the wide block hands on rows only: the twins exist when all three stacks are narrow)
+                if "wide" not in kinds[:3]:
+                    self._native_frag = tuple(Mlp2Block(layers, idx, final=final, in_fragments=True) for layers, final in specs[1:3])
                 self._facts = PathFacts(self.with_global_state, len(nat), nat[0].O, nat[1].O, nat[0].tile_epilogue,
                                         nat[1].tile_epilogue, self._gterm_block is not None, len(self._native_frag) == 2)
             self._build_pending = False
@@ -237,7 +289,7 @@ class SarlValueNet(object):
         if self._native is None:
             return False
         specs, gterm = self._block_specs()
-        for blk, (layers, final) in zip(self._native + self._native_frag, specs + specs[1:3]):
+        for blk, (layers, final) in zip(self._native + self._native_frag, specs + (specs[1:3] if self._native_frag else [])):
             blk.update(layers, final)
         if self._gterm_block is not None:
             self._gterm_block.update(gterm[0], None)

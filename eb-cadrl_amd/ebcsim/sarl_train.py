@@ -339,7 +339,23 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
     om (an occupancy.OccupancySpec): OM-SARL.  The trainer's network takes T + om.width columns (SarlTrainer(om_width=
     om.width)), the replay and the episode store hold the wide states, collect_il and collect store them (ebc_step_k_om,
     ebc_observe_wide) and DeviceSarlPolicy(om=om) decides.
-    Returns a dict of what happened."""
+    Returns a dict of what happened.  (run_sarl_training_ex below: the same with the choice of the deciding blocks.)"""
+    return run_sarl_training_ex(env, trainer, actions, gamma, il_steps=il_steps, il_epochs=il_epochs, il_learning_rate=il_learning_rate,
+                                il_safety_space=il_safety_space, rl_learning_rate=rl_learning_rate, train_iterations=train_iterations,
+                                steps_per_iteration=steps_per_iteration, train_batches=train_batches, batch_size=batch_size,
+                                capacity=capacity, epsilon_start=epsilon_start, epsilon_end=epsilon_end, epsilon_decay=epsilon_decay,
+                                target_update_interval=target_update_interval, generator=generator, log=log, output_dir=output_dir,
+                                checkpoint_interval=checkpoint_interval, rank=rank, after_il=after_il, om=om)
+
+
+def run_sarl_training_ex(env, trainer, actions, gamma, wide_decide=False, il_steps=0, il_epochs=0, il_learning_rate=0.01, il_safety_space=0.15,
+                         rl_learning_rate=0.001, train_iterations=0, steps_per_iteration=1, train_batches=100, batch_size=100,
+                         capacity=100000, epsilon_start=0.5, epsilon_end=0.1, epsilon_decay=4000, target_update_interval=50,
+                         generator=None, log=None, output_dir=None, checkpoint_interval=0, rank=0, after_il=None, om=None):
+    """run_sarl_training (its arguments, its checks, its result) with one keyword more.  wide_decide: the deciding and
+    the target network take wide blocks for the stacks the narrow block does not hold (SarlValueNet(..., wide=True): the
+    networks the layer form of the gradient trains); False: such networks decide on torch, which is run_sarl_training.
+    (A function of its own: run_sarl_training keeps its signature.)"""
     dev = trainer.device
     if dev.type != "cuda":
         raise NotImplementedError("run_sarl_training: the rollouts run on a HIP device")
@@ -352,6 +368,8 @@ def run_sarl_training(env, trainer, actions, gamma, il_steps=0, il_epochs=0, il_
                                   % (env.R, trainer.grad_max_rows()))
     om_kw = {} if om is None else {"om": om}  # without maps: the calls as they were
     kw = dict(device=dev, with_global_state=trainer.with_global_state, self_state_dim=trainer.self_state_dim)
+    if wide_decide:
+        kw["wide"] = True
     return grad_train.run_value_training(
         env, trainer, gamma, env.T + W, lambda: SarlValueNet(trainer.state_dict(), **kw), lambda net: DeviceSarlPolicy(net, actions, gamma, **om_kw),
         lambda net: net.refresh_from(trainer), om_kw, om_kw, il_steps, il_epochs, il_learning_rate, il_safety_space, rl_learning_rate,

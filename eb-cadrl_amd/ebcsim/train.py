@@ -70,12 +70,14 @@ class SarlModule(torch.nn.Module):
             for k, v in self.named_parameters():
                 v.copy_(sd[self._ref_name(k)])
 
-    def as_value_net(self, native=False):
+    def as_value_net(self, native=False, wide=False):
         """A SarlValueNet whose tensors ARE this module's parameters (it follows every optimizer step).  native: also
         build the matrix-core blocks for inference from the current weights — the caller re-packs them with
-        net.refresh_native() after the weights have changed (run_training: once per round)."""
+        net.refresh_native() after the weights have changed (run_training: once per round).  wide: stacks of up to 640
+        units as wide blocks (SarlValueNet's keyword)."""
+        kw = {"wide": True} if wide else {}
         return SarlValueNet.from_stacks(self._stack("mlp1"), self._stack("mlp2"), self._stack("attention"), self._stack("mlp3"),
-                                        self.with_global_state, self.self_state_dim, next(self.parameters()).device, native)
+                                        self.with_global_state, self.self_state_dim, next(self.parameters()).device, native, **kw)
 
     def forward(self, rows, n_valid=None):
         net = self.as_value_net()

@@ -552,6 +552,20 @@ int ebc_mlp2_forward_reduce(void *mlp, void *stream, const float *x, int M, int 
                             int group_rows, float *y, int seg_rows, const float *row_weight, double *partial);
 int ebc_pair_weights(void *stream, const float *scores, const long long *n_valid, int B, int R, float *w);
 
+/* The WIDE two-layer block: 1 <= K0, H, O <= 640 (ebc_sarl_net_create_layers' limit: the reference's policy_x3 /
+ * policy_x4 networks), same arguments as ebc_mlp2_create_ex, same handle type.  Two launches of a single-layer
+ * split-bf16 kernel, the hidden layer making a round trip through a scratch the handle owns (one per stream, grown on
+ * demand); same arithmetic as the block above, deterministic (no atomics), not byte-equal to it.  flags: 0.
+ * On its handle work: ebc_mlp2_forward (relu_out, row_bias / group_rows, the one-output tail w3 / b3),
+ * ebc_mlp2_forward_f32 (the float32 matrix instruction: per output one float32 chain, k ascending), ebc_mlp2_update,
+ * ebc_mlp2_destroy, and ebc_mlp2_forward_ex with plain rows (x, y, row_bias), which is ebc_mlp2_forward.
+ * Refused with EBC_ERR_UNSUPPORTED, nothing written, the handle still good: EBC_MLP_IN_FRAGMENTS at creation;
+ * frag_in / frag_out, partial / seg_rows / row_weight and EBC_MLP_GENERAL_KERNEL in ebc_mlp2_forward_ex;
+ * ebc_mlp2_forward_reduce; and a forward on a stream under capture when the call would have to allocate the scratch
+ * or raise a kernel's LDS limit (run the same call once outside the capture first). */
+int ebc_mlp2_create_wide(int device_id, int K0, int H, int O, const float *w1, const float *b1, const float *w2,
+                         const float *b2, const float *w3, const float *b3, int flags, void **mlp_out);
+
 /* The argmax side of MultiHumanRL.predict for a batch (rl/policy/multi_human_rl.py:72-80), one launch:
  *   values [E][A] (float64) = reward + discount * v      (v [E][A]: the value network's float32 outputs)
  *   order  [E][A] (int32)   = each env's actions by value, best first (equal values: the lower action index first);

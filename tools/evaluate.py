@@ -61,6 +61,8 @@ def main():
     ap.add_argument("--steps-per-call", type=int, default=0, metavar="K",
                     help="--policy sail: advance in windows of K steps per ebc_step_k call (default 0: the per-step loop)")
     ap.add_argument("--one-launch", action="store_true", help="with --steps-per-call: each window as one kernel launch")
+    ap.add_argument("--wide-decide", action="store_true",
+                    help="--policy sarl: stacks wider than the two-layer block (up to 640 units: policy_x3 / policy_x4) as wide blocks instead of torch")
     args = ap.parse_args()
     if (args.steps_per_call or args.one_launch) and args.policy != "sail":
         ap.error("--steps-per-call / --one-launch go with --policy sail, the policy ebc_step_k keeps on the device")
@@ -113,7 +115,7 @@ def main():
             from ebcsim.cadrl import CadrlValueNet, DeviceCadrlPolicy
             net, make_policy = CadrlValueNet.load(weights, device="cuda:0"), DeviceCadrlPolicy
         else:
-            net = SarlValueNet.load(weights, device="cuda:0")
+            net = SarlValueNet.load(weights, device="cuda:0", **({"wide": True} if args.wide_decide else {}))
         kw = {}
         if with_om:
             kw["om"] = ebc_config.occupancy_from_config(pol, policy=args.policy)

@@ -9,7 +9,7 @@ after RL.
     python3 tools/train_sarl.py --env-config eb-cadrl_amd/configs/sarl_a5.config \
         --policy-config eb-cadrl_amd/configs/policy_plain.config --device-scenes [--envs 256] [--il-steps 200] [--il-epochs 50]
         [--iterations 200] [--steps-per-iteration 4] [--train-batches 100] [--batch-size 100] [--cases 500]
-        [--weights start.pth] [--autograd] [--grad-form chunk|layers|auto] [--out sarl_model.pth]
+        [--weights start.pth] [--autograd] [--grad-form chunk|layers|auto] [--wide-decide] [--out sarl_model.pth]
 
 The tool's defaults are a SHORT schedule, not the reference's: 200 RL rounds with epsilon decayed over 150 of them and the
 target network refreshed every 10, where run_sarl_training and the reference's train.config use 4000 and 50 for runs of
@@ -20,7 +20,9 @@ written only by a run that ended.
 
 Wider networks ([sarl] mlp1_dims ... of the policy config above 256, eb-cadrl_amd/configs/policy_x2.config): --grad-form
 layers or auto; the chunk form (the default) refuses them.  auto takes the chunk form where it holds the network and the
-scene's rows, else the layer form; the bytes are the same.
+scene's rows, else the layer form; the bytes are the same.  --wide-decide: such a network also DECIDES on the device (the
+rollouts, the value targets and the evaluations): its stacks of up to 640 units become wide blocks; without it it decides
+on torch's float32 GEMMs.
 
 OM-SARL: a policy config with [sarl] with_om = true (eb-cadrl_amd/configs/policy_om.config) trains the network whose mlp1
 takes T + cell_num^2 * om_channel_size columns, on the wide states the device builds (ebc_observe_wide, ebc_step_k_om),
@@ -70,6 +72,8 @@ def main():
     ap.add_argument("--grad-form", default=None, choices=["chunk", "layers", "auto"],
                     help="the kernel's form: chunk (default; hidden layers up to 256), layers (up to 640, R up to 128) or auto (chunk "
                          "where it takes the network and the rows, else layers); the same bytes")
+    ap.add_argument("--wide-decide", action="store_true",
+                    help="decide with wide blocks (stacks of up to 640 units) instead of torch where the network is wider than the two-layer block")
     ap.add_argument("--out", default="sarl_model.pth")
     args = ap.parse_args()
     if not args.device_scenes:
@@ -81,7 +85,7 @@ def main():
     from ebcsim.batched import BatchedEnv
     from ebcsim.occupancy import OccupancySpec
     from ebcsim.sarl import DeviceSarlPolicy, SarlValueNet
-    from ebcsim.sarl_train import SarlFormTrainer, SarlTrainer, run_sarl_training
+    from ebcsim.sarl_train import SarlFormTrainer, SarlTrainer, run_sarl_training, run_sarl_training_ex
     from ebcsim.train import SarlModule, evaluate
     cfg, pol = configparser.RawConfigParser(), configparser.RawConfigParser()
     cfg.read(args.env_config)
@@ -93,6 +97,8 @@ def main():
     with_global_state = pol.getboolean("sarl", "with_global_state", fallback=True)
     om = OccupancySpec.from_config(pol)
     om_kw = {} if om is None else {"om": om}
+    wide_kw = {"wide": True} if args.wide_decide else {}
+    wide_train_kw = {"wide_decide": True} if args.wide_decide else {}
     sc = ebc_scene.SceneConfig.from_config(cfg)
     gen, test = ebc_scene.gen_struct(sc, "train"), ebc_scene.gen_struct(sc, "test")
     S = ebc_scene.max_static_rows(sc)
@@ -105,7 +111,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
-        policy = DeviceSarlPolicy(SarlValueNet.load(path, device="cuda:0", with_global_state=with_global_state), space, gamma, **om_kw)
+        policy = DeviceSarlPolicy(SarlValueNet.load(path, device="cuda:0", with_global_state=with_global_state, **wide_kw), space, gamma, **om_kw)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
         env.close()
@@ -146,8 +152,8 @@ def main():
         mark["after_il"] = evaluate_saved(os.path.join(out_dir, "il_model.pth"), "after imitation learning")
         mark["t_rl"] = time.perf_counter()
 
-    hist = run_sarl_training(env, trainer, space, gamma, il_steps=args.il_steps, il_epochs=args.il_epochs, train_iterations=args.iterations,
-                             after_il=after_il, **om_kw, **common)
+    hist = (run_sarl_training_ex if args.wide_decide else run_sarl_training)(env, trainer, space, gamma, il_steps=args.il_steps, il_epochs=args.il_epochs, train_iterations=args.iterations,
+                             after_il=after_il, **om_kw, **wide_train_kw, **common)
     torch.cuda.synchronize()
     rl_s = time.perf_counter() - mark["t_rl"]
     print("RL: %d rounds of %d decisions per env and %d optimizer steps of batch %d in %.2f s; loss first %.3e, last %.3e; replay memory %d"
