@@ -62,6 +62,7 @@ struct DevState {
   // 8-byte word, one box per consumer, re-emptied by it: four 8-byte fabric writes per human and step
   // instead of one 16-byte one.)
   uint4 *vel;                     // [E][N] ORCA -> STATE, ROWS: {vx bits, epoch, vy bits, epoch}, one 16-byte store
+                                  //     then [E][N] linear boxes (EBC_HUMAN_BY_TYPE): the two doubles of a human on `linear`
   unsigned long long *env_done;   // [E] ENV -> STATE: epoch << 32 | 1 + done
   unsigned *rows_loaded;          // [E] ROWS -> STATE: = epoch once the pre-step state AND the robot's next state are in registers
                                   //     (STATE looks at it only before it RESTARTS an env: radius, type, static rows, n_humans, robot_n)
@@ -75,7 +76,14 @@ struct DevState {
   // uniform ORCA constants (float, as rvo2 computes them) and the magic number of h / N
   float inv_time_horizon, inv_time_step, range_sq;
   unsigned n_magic, n_shift;
+  // EBC_HUMAN_BY_TYPE (ebc_set_human_policies): bit t set = humans of type t are on the linear policy, clear = on ORCA.
+  // Read by the mixed forms only.  (It takes the four bytes the struct ended in unused: no kernel's arguments grew.)
+  unsigned human_linear;
 };
+static_assert(sizeof(DevState) % 8 == 0, "DevState: 8-byte aligned kernel argument");
+
+// EBC_HUMAN_BY_TYPE: is a human of this type on the linear policy?
+__device__ __forceinline__ bool human_on_linear(const DevState &s, int type) { return (s.human_linear >> (type & 3)) & 1u; }
 
 #ifndef EBC_SPIN_LIMIT
 #define EBC_SPIN_LIMIT (1u << 22)               // polls before a consumer gives up (~1 s)
@@ -124,7 +132,7 @@ __device__ __forceinline__ void store_tile(const EbcParams &p, const DevState &s
 
 // The preferred velocities of pool scenes [first, first + count) (in human slots), so that a
 // restart copies them instead of redoing a double sqrt and two divisions inside the step.
-__global__ __launch_bounds__(256) void pool_pref_kernel(DevState s, size_t first, size_t count) {
+static __global__ __launch_bounds__(256) void pool_pref_kernel(DevState s, size_t first, size_t count) {
   const size_t q = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (q >= count) return;
   const size_t k = first + q;
@@ -137,7 +145,7 @@ __global__ __launch_bounds__(256) void pool_pref_kernel(DevState s, size_t first
 // middle of an episode on a pool scene keeps only that slot's INDEX for its occupancy grid.  One workgroup per env
 // copies the grid into the env's own slot e — a reset slot, never a restart source once a pool is installed — and
 // points the env at it, so the grid outlives the pool it came from.
-__global__ __launch_bounds__(256) void rehome_grid_kernel(DevState s, uint64_t *grid) {
+static __global__ __launch_bounds__(256) void rehome_grid_kernel(DevState s, uint64_t *grid) {
   const int e = blockIdx.x;
   const int src = s.grid_scene[e];
   if (src == e) return;
@@ -147,7 +155,7 @@ __global__ __launch_bounds__(256) void rehome_grid_kernel(DevState s, uint64_t *
   if (threadIdx.x == 0) s.grid_scene[e] = e;
 }
 
-__global__ __launch_bounds__(256) void tile_kernel(EbcParams p, DevState s) {
+static __global__ __launch_bounds__(256) void tile_kernel(EbcParams p, DevState s) {
   const size_t k = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (k >= (size_t)s.E * s.N) return;
   store_tile(p, s, k, s.px[k], s.py[k], s.vx[k], s.vy[k], s.gx[k], s.gy[k], s.radius[k], s.v_pref[k]);
@@ -653,6 +661,13 @@ __device__ __forceinline__ void mailbox_wait_epoch(unsigned *box, bool need, uns
 template <typename W>
 __device__ __forceinline__ void mailbox_put(W *box, W v) {
   __hip_atomic_store(box, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// EBC_HUMAN_BY_TYPE: the linear box of human k, [E][N] 16-byte granules behind the words of `vel` (one allocation): the
+// two doubles of linear_policy for a human on the linear policy, written by its ORCA group before the human's word.
+__device__ __forceinline__ uint4 *linear_box(const DevState &s, size_t k) { return s.vel + (size_t)s.E * s.N + k; }
+__device__ __forceinline__ void unpack_linear(u32x4 v, double &ax, double &ay) {
+  ax = __hiloint2double((int)v.y, (int)v.x);
+  ay = __hiloint2double((int)v.w, (int)v.z);
 }
 __device__ __forceinline__ void unpack_velocity(u32x4 v, double &ax, double &ay) {
   ax = (double)__uint_as_float(v.x);  // getAgentVelocity -> Python float
@@ -1232,7 +1247,15 @@ __device__ __forceinline__ void sreg(const Tp &x) {
 }
 
 // ---- ORCA
-template <int GS>
+// MIXED (EBC_HUMAN_BY_TYPE): the group of a human on the linear policy solves no LP.  It works linear_policy out ONCE, in
+// double, from the pre-step state, and stores the two doubles in the human's linear box (linear_box); then it idles
+// through the solve like the group of a padded slot, and behind a wait for that store it posts the human's epoch-tagged
+// word with the wave's other words, zeros where the float velocity would be.  ROWS and STATE, which see from the type
+// that the human is on `linear`, read the box with a device-scope load after they have seen the word — the order
+// robot_n / robot_ready keep.  A word is still posted for EVERY human and producers still wait for nothing, so no wait
+// changes: a STATE wave that has seen all the words of its envs knows that every group that reads their tile, or a
+// human's state here, has read it.
+template <int GS, bool MIXED = false>
 __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s, const OrcaHot &hot, uint4 *vel, unsigned epoch,
                                           unsigned char *scratch, unsigned block, unsigned class_humans, int lane) {
   // `hot`, vel, epoch, class_humans (ec N): preloaded kernel arguments; the rest is asked for now, all at once
@@ -1246,6 +1269,38 @@ __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s,
   const bool h_ok = hh < span.end;  // lanes past HPW * GS idle (a span holds at most HPW humans)
   int e, i;
   split_human(hot, hh, h_ok, e, i);
+  if constexpr (MIXED) {
+    sreg(s.type); sreg(s.human_linear); sreg(s.px); sreg(s.py); sreg(s.gx); sreg(s.gy); sreg(s.v_pref);
+    // Everything either kind of group needs is asked for AT ONCE, before the type is known: the human's type and
+    // double-precision state, then its tile record, and a linear human's word leaves with the wave's other words.
+    // (Asked for one after the other — the type, then the state of a linear human, the wait for the box and its word,
+    // then the tile — a mixed step measured the same at 4096 envs and 4 % slower at 16384: profiles/human_mix.txt.)
+    const size_t k = h_ok ? hh : 0;
+    const int type = s.type[k];
+    const double lpx = s.px[k], lpy = s.py[k], lgx = s.gx[k], lgy = s.gy[k], lvpref = s.v_pref[k];
+    const OrcaTile t = orca_tile_load<GS>(hot, h_ok, e, i);
+    const bool linear = h_ok && human_on_linear(s, type);
+    const bool solve = h_ok && !linear;
+    if (linear) {
+      double ax, ay;
+      linear_policy(lpx, lpy, lgx, lgy, lvpref, ax, ay);  // pre-step state (env.py:393-405)
+      if (j == 0) {  // the store's way to memory is hidden behind the LPs of the wave's other groups
+        const u32x4 d = {(unsigned)__double2loint(ax), (unsigned)__double2hiint(ax), (unsigned)__double2loint(ay),
+                         (unsigned)__double2hiint(ay)};
+        store16_device(linear_box(s, hh), d);
+      }
+    }
+    float ox, oy;
+    bool human_ok;
+    orca_wave_compute<GS>(p, s, hot.N, t, [&] { return s.robot + (size_t)e * 9; }, solve, i, scratch, ox, oy, human_ok);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the doubles are out before a word says so
+    if (h_ok && j == 0) {
+      const bool moved = solve && human_ok;
+      const u32x4 w = {moved ? __float_as_uint(ox) : 0u, epoch, moved ? __float_as_uint(oy) : 0u, epoch};
+      store16_device(vel + hh, w);
+    }
+    return;
+  }
   float ox, oy;
   bool human_ok;
   orca_wave<GS>(p, s, hot, h_ok, e, i, scratch, ox, oy, human_ok);
@@ -1262,7 +1317,9 @@ __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s,
 // slots, so no load waits for n_humans; the ROW a slot emits is: human i < n -> i, static j < ns ->
 // n + j, and the padding rows (zeros) are shared out over the unused slots: human slot i >= n ->
 // ns + i, static slot j >= ns -> N + j.
-template <int T>
+// MIXED (EBC_HUMAN_BY_TYPE): a human on the linear policy takes the doubles of its linear box in place of the word's
+// floats (its word carries the epoch only).
+template <int T, bool MIXED = false>
 __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
                                           RoleLds &L, unsigned block, unsigned ec, unsigned epw, unsigned epoch, int lane) {
   stage_args(&L.args.p, p_in, lane);
@@ -1344,6 +1401,9 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     if (env_ok && moving) {  // Agent.step (agent.py:202-211)
       double ax, ay;
       unpack_velocity(v, ax, ay);
+      if constexpr (MIXED) {
+        if (human_on_linear(s, otype)) unpack_linear(load16_device(linear_box(s, k)), ax, ay);  // after the word was seen
+      }
       opx = opx + ax * p.time_step;
       opy = opy + ay * p.time_step;
       ovx = ax;
@@ -1355,6 +1415,9 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
 }
 
 // ---- STATE
+// MIXED (EBC_HUMAN_BY_TYPE): a human on the linear policy takes the doubles of its linear box in place of the word's
+// floats.
+template <bool MIXED = false>
 __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
                                            RoleLds &L, unsigned block, unsigned ec, bool wait_rows, unsigned epoch, int lane) {
   stage_args(&L.args.p, p_in, lane);
@@ -1446,6 +1509,9 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
   float4 *tile = s.tile + 2 * m.k;
   double ax = 0, ay = 0;
   if (m.active) unpack_velocity(v, ax, ay);
+  if constexpr (MIXED) {
+    if (m.active && human_on_linear(s, h.type)) unpack_linear(load16_device(linear_box(s, m.k)), ax, ay);  // after the word was seen
+  }
   if (io.human_action) {
     io.human_action[m.k * 2] = ax;
     io.human_action[m.k * 2 + 1] = ay;
@@ -1547,7 +1613,9 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
 #ifndef EBC_STEP_WPB
 #define EBC_STEP_WPB 1
 #endif
-template <int GS, int T>
+// MIXED = true is EBC_HUMAN_BY_TYPE's instantiation (csrc/ebcsim_mix.hip): the ORCA, ROWS and STATE roles above in their
+// mixed forms.  MIXED = false is the EBC_HUMAN_ORCA step as it was measured, not an instruction more.
+template <int GS, int T, bool MIXED = false>
 __global__ __launch_bounds__(EBC_WAVE * EBC_STEP_WPB, EBC_STEP_WAVES(GS)) void orca_step_kernel(
     // 14 dwords the wave finds in scalar registers when it starts (kernarg preload): its role and, for
     // an ORCA wave, everything up to its first vector load (the last, the humans of a class = ec N, also pads
@@ -1574,21 +1642,21 @@ __global__ __launch_bounds__(EBC_WAVE * EBC_STEP_WPB, EBC_STEP_WAVES(GS)) void o
     // -0.08 us per step (profiles/r02_early_rows_ab.txt)
     __builtin_amdgcn_s_setprio(EBC_ORCA_PRIO);
     const OrcaHot hot{hot_E, hot_N, hot_magic, hot_shift, hot_tile, hot_n_humans};
-    orca_role<GS>(p_in, s_in, hot, hot_vel, hot_epoch, lds, b, hot_class_humans, lane);
+    orca_role<GS, MIXED>(p_in, s_in, hot, hot_vel, hot_epoch, lds, b, hot_class_humans, lane);
     return;
   }
   b -= orca_blocks;
   if (b < g.rows_blocks) {
-    rows_role<T>(p_in, s_in, io_in, L, b, g.ec, g.rows_epw, g.epoch, lane);
+    rows_role<T, MIXED>(p_in, s_in, io_in, L, b, g.ec, g.rows_epw, g.epoch, lane);
     return;
   }
   b -= g.rows_blocks;
-  state_role(p_in, s_in, io_in, L, b, g.ec, g.rows_blocks != 0, g.epoch, lane);
+  state_role<MIXED>(p_in, s_in, io_in, L, b, g.ec, g.rows_blocks != 0, g.epoch, lane);
 }
 
 // SceneGenerator.generate_random_scene for n seeds, one lane per scene (ebc_scene_gen.h): `d` holds the base of
 // arrays shaped like an EbcScene's, `mt` n MT19937 states word-major (lanes of a wave touch consecutive words).
-__global__ __launch_bounds__(64) void scene_gen_kernel(EbcSceneGen c, const uint32_t *seeds, uint32_t seed0, int n, int N, int S,
+static __global__ __launch_bounds__(64) void scene_gen_kernel(EbcSceneGen c, const uint32_t *seeds, uint32_t seed0, int n, int N, int S,
                                                         int G, SceneRow d, uint32_t *mt, int *status) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r >= n) return;
@@ -1603,7 +1671,7 @@ __global__ __launch_bounds__(64) void scene_gen_kernel(EbcSceneGen c, const uint
 
 // Discounted returns of a rollout window, one thread per env walking its K steps backwards (explorer.py:159-170,
 // :82-92): see ebc_il_targets in include/ebcsim.h.
-__global__ __launch_bounds__(256) void il_targets_kernel(const double *reward, const uint8_t *done, const uint8_t *info, int K,
+static __global__ __launch_bounds__(256) void il_targets_kernel(const double *reward, const uint8_t *done, const uint8_t *info, int K,
                                                          int E, double gamma_bar, double *values, uint8_t *keep) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
@@ -1628,7 +1696,7 @@ __global__ __launch_bounds__(256) void il_targets_kernel(const double *reward, c
 // Observation rows that exist per env (humans + static obstacles as pedestrians, env.py:381-382, :457-458):
 // what the value network's per-pair kernels mask with.  Read from the device state, so it follows restarts
 // from a ragged scene pool.
-__global__ __launch_bounds__(256) void row_counts_kernel(DevState s, long long *out) {
+static __global__ __launch_bounds__(256) void row_counts_kernel(DevState s, long long *out) {
   const int e = blockIdx.x * blockDim.x + threadIdx.x;
   if (e < s.E) out[e] = (long long)s.n_humans[e] + (s.S ? s.n_static[e] : 0);
 }
@@ -1703,7 +1771,8 @@ __global__ __launch_bounds__(EBC_LA_THREADS) void lookahead_kernel(EbcParams p, 
     if (r < n) {  // a human: the current state stays for phase B1, the row moves on (Agent.step)
       const size_t k = (size_t)e * N + r;
       double ax, ay;
-      if (POLICY == EBC_HUMAN_LINEAR) {
+      // EBC_HUMAN_BY_TYPE: hact holds everybody's ORCA velocity (orca_kernel); a human on the linear policy replaces its own
+      if (POLICY == EBC_HUMAN_LINEAR || (POLICY == EBC_HUMAN_BY_TYPE && human_on_linear(s, cur.type))) {
         linear_policy(cur.px, cur.py, s.gx[k], s.gy[k], s.v_pref[k], ax, ay);
         s.hact[k * 2] = ax;  // cache for a following EBC_HUMAN_CACHED step
         s.hact[k * 2 + 1] = ay;

@@ -174,7 +174,10 @@ using RolloutArg = typename std::conditional<SAIL, RolloutIOSail, RolloutIO>::ty
 // SAIL = false is the kernel of the three robot policies as it was measured; SAIL = true (EBC_ROBOT_SAIL) is an
 // instantiation of its own, so that theirs keeps its register allocation: it adds the network's decision in P1 and
 // nothing anywhere else.
-template <int GS, bool SAIL = false>
+// MIXED = true is EBC_HUMAN_BY_TYPE's instantiation (csrc/ebcsim_mix.hip), again one of its own: the group of a human on
+// the linear policy idles through the ORCA pass, and the human's commit in P3a takes linear_policy of the pre-step state,
+// which is still in LDS there, in place of vel[].  Nothing else differs.
+template <int GS, bool SAIL = false, bool MIXED = false>
 __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutArg<SAIL> io) {
   extern __shared__ __align__(16) unsigned char ro_lds[];
   const int tid = threadIdx.x, lane = tid & (EBC_WAVE - 1), wave = tid / EBC_WAVE;
@@ -355,10 +358,12 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
       const bool h_ok = group < HPW && u < HN;  // lanes past HPW * GS idle
       const int el = h_ok ? u / N : 0;
       const int i = h_ok ? u - el * N : 0;
-      const OrcaTile t = orca_tile_load<GS>(lds_hot, h_ok, el, i);
+      bool solve = h_ok;
+      if constexpr (MIXED) solve = h_ok && !human_on_linear(s, h_type[h_ok ? u : 0]);
+      const OrcaTile t = orca_tile_load<GS>(lds_hot, solve, el, i);
       float ox, oy;
       bool human_ok;
-      orca_wave_compute<GS>(p, s, N, t, [&] { return robot + el * 9; }, h_ok, i, scratch, ox, oy, human_ok);
+      orca_wave_compute<GS>(p, s, N, t, [&] { return robot + el * 9; }, solve, i, scratch, ox, oy, human_ok);
       if (h_ok && j == 0) vel[u] = make_float2(human_ok ? ox : 0.0f, human_ok ? oy : 0.0f);
     }
     __syncthreads();
@@ -371,7 +376,10 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
       if (i >= n_h[el]) continue;
       // Agent.step (agent.py:202-211), first arrival (env.py:365-378), the float tile record (orca.py:110-140):
       // state_role's commit; the row is rows_role's
-      const double ax = (double)vel[q].x, ay = (double)vel[q].y;  // getAgentVelocity -> Python float
+      double ax = (double)vel[q].x, ay = (double)vel[q].y;  // getAgentVelocity -> Python float
+      if constexpr (MIXED) {
+        if (human_on_linear(s, h_type[q])) linear_policy(h_px[q], h_py[q], h_gx[q], h_gy[q], h_vpref[q], ax, ay);  // env.py:393-405
+      }
       const double px = h_px[q] + ax * dt, py = h_py[q] + ay * dt;
       const double rad = h_rad[q];
       if (io.obs_rotated)

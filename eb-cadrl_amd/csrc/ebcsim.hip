@@ -13,8 +13,10 @@
 
 #include "ebc_host.h"
 #include "ebc_dagger.h"
+#include "ebc_group_sizes.h"
 #include "ebc_kernels.h"
 #include "ebc_local_map_kernel.h"
+#include "ebc_mix_api.h"
 #include "ebc_om_state.h"
 #include "ebc_rollout.h"
 #include "ebc_sail_api.h"
@@ -174,30 +176,10 @@ int group_size_for(int n) {
   return 32;
 }
 
-// Development builds (make dev) instantiate ONE group size per kind of kernel: EBC_DEV_GS for the kernels
-// of the humans' ORCA, 21 for the robot's.  0 = every size of kGroupSizes.
-#ifdef EBC_DEV_GS
-constexpr int kDevHumanGs = EBC_DEV_GS, kDevRobotGs = 21;
-#else
-constexpr int kDevHumanGs = 0, kDevRobotGs = 0;
-#endif
-
-// Run-time group size -> compile-time one: calls f(std::integral_constant<int, GS>()) for GS == gs, a member of
-// kGroupSizes.  The only place that lists the instantiated sizes besides the table.
-template <int DEV_GS, typename F>
-int with_group_size(int gs, F f) {
-  if constexpr (DEV_GS != 0) {
-    if (gs != DEV_GS) return fail(EBC_ERR_UNSUPPORTED, "development build: " + std::to_string(DEV_GS) + "-lane ORCA groups only");
-    return f(std::integral_constant<int, DEV_GS>());
-  } else {
-    switch (gs) {
-#define GS_(N) case N: return f(std::integral_constant<int, N>())
-      GS_(2); GS_(3); GS_(4); GS_(5); GS_(6); GS_(7); GS_(8); GS_(9); GS_(10); GS_(12); GS_(16); GS_(21);
-#undef GS_
-      default: return f(std::integral_constant<int, 32>());
-    }
-  }
-}
+// the development builds' sizes and the run-time -> compile-time switch: ebc_group_sizes.h (shared with ebcsim_mix.hip)
+using ebc_host::kDevHumanGs;
+using ebc_host::kDevRobotGs;
+using ebc_host::with_group_size;
 
 int launch_orca(Handle *h) {
   const int blocks = orca_blocks(h);
@@ -220,6 +202,22 @@ int launch_service(Handle *h, const StepIO &io) {
   return EBC_OK;
 }
 
+// EBC_HUMAN_BY_TYPE: the mixed instantiation (ebcsim_mix.hip) with the arguments of launch_orca_step_gs
+int launch_mixed_step(Handle *h, const StepIO &io, unsigned blocks, const ebc::StepGrid &g) {
+  const void *kernel = nullptr;
+  int rc = ebc_mix_api::step_kernel(h->orca_gs, h->T, &kernel);
+  if (rc != EBC_OK) return rc;
+  unsigned env_blocks = g.env_blocks, orca_blocks = g.orca_blocks, epoch = g.epoch, class_humans = g.ec * (unsigned)h->s.N;
+  const float4 *tile = (const float4 *)h->s.tile;
+  const int *n_humans = (const int *)h->s.n_humans;
+  StepIO io_arg = io;
+  ebc::StepGrid g_arg = g;
+  void *args[] = {&env_blocks, &orca_blocks, &h->s.E, &h->s.N, &h->s.n_magic, &h->s.n_shift, &tile, &n_humans, &h->s.vel,
+                  &epoch, &class_humans, &h->p, &h->s, &io_arg, &g_arg};
+  HIP_TRY(hipLaunchKernel(kernel, dim3((blocks + EBC_STEP_WPB - 1) / EBC_STEP_WPB), dim3(EBC_WAVE * EBC_STEP_WPB), args, 0, h->stream));
+  return EBC_OK;
+}
+
 template <int GS>
 int launch_orca_step_gs(Handle *h, const StepIO &io, unsigned blocks, const ebc::StepGrid &g) {
   if (h->T == 17)
@@ -234,7 +232,7 @@ int launch_orca_step_gs(Handle *h, const StepIO &io, unsigned blocks, const ebc:
   return EBC_OK;
 }
 
-int launch_orca_step(Handle *h, const StepIO &io) {
+int launch_orca_step(Handle *h, const StepIO &io, bool mixed = false) {
   // who does what: ebc_step_grid.h (eight classes of envs, every role a multiple of 8 blocks)
   const ebc::StepGridShape shape = ebc::step_grid_shape(h->s.E, h->s.N, h->s.S, h->orca_gs, io.ob || io.obs_rotated);
   if (!shape.fits()) return fail(EBC_ERR_UNSUPPORTED, "ORCA step grid >= 2^31 workgroups");
@@ -248,8 +246,9 @@ int launch_orca_step(Handle *h, const StepIO &io) {
   if (++h->epoch == 0) h->epoch = 1;  // every mailbox word is tagged with the epoch of the launch that wrote it; 0 = never
   g.epoch = h->epoch;
   g.total = (unsigned)blocks;
-  const int rc = with_group_size<kDevHumanGs>(
-      h->orca_gs, [&](auto gs) { return launch_orca_step_gs<decltype(gs)::value>(h, io, (unsigned)blocks, g); });
+  const int rc = mixed ? launch_mixed_step(h, io, (unsigned)blocks, g)
+                       : with_group_size<kDevHumanGs>(
+                             h->orca_gs, [&](auto gs) { return launch_orca_step_gs<decltype(gs)::value>(h, io, (unsigned)blocks, g); });
   // the launch leaves the robots' next state in robot_n and the humans' next positions in px_n / py_n: that is the
   // current state from here on (every other kernel and entry point reads and writes robot, px and py)
   if (rc == EBC_OK) {
@@ -262,6 +261,7 @@ int launch_orca_step(Handle *h, const StepIO &io) {
 
 int launch_step(Handle *h, const StepIO &io, int policy) {
   if (policy == EBC_HUMAN_ORCA) return launch_orca_step(h, io);
+  if (policy == EBC_HUMAN_BY_TYPE) return launch_orca_step(h, io, true);
   if (policy == EBC_HUMAN_LINEAR) return launch_service<EBC_HUMAN_LINEAR>(h, io);
   return launch_service<EBC_HUMAN_EXTERNAL>(h, io);
 }
@@ -548,7 +548,8 @@ int ebc_create(int device_id, int n_envs, int max_humans, int max_static, const 
   A_(sradius, ES); A_(robot, (size_t)n_envs * 9); A_(robot_n, (size_t)n_envs * 9); A_(time, n_envs); A_(arrival, EN);
   A_(tile, EN * 2);
   A_(done, n_envs); A_(hact, EN * 2);
-  A_(vel, EN); A_(env_done, n_envs); A_(rows_loaded, n_envs); A_(robot_ready, n_envs); A_(fault, 1);  // zeroed: tag 0 = no launch
+  A_(vel, 2 * EN);  // the words, then the linear boxes of EBC_HUMAN_BY_TYPE (linear_box, ebc_kernels.h)
+  A_(env_done, n_envs); A_(rows_loaded, n_envs); A_(robot_ready, n_envs); A_(fault, 1);  // zeroed: tag 0 = no launch
 #undef A_
   if (rc == EBC_OK) rc = dev_alloc(h, &s.pool.cursor, n_envs);
   if (rc == EBC_OK) rc = dev_alloc(h, &s.grid_scene, n_envs);
@@ -982,7 +983,7 @@ int launch_observe_wide(Handle *h, const EbcOmSpec &spec, float *d_wide, long lo
 unsigned sail_area(const Handle *h, int chunk) { return (unsigned)(ebc::sail_lds_floats(chunk, h->sail_N) * sizeof(float)); }
 
 template <int GS>
-int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
+int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed) {
   const int N = h->s.N, S = h->s.S, E = h->s.E;
   constexpr unsigned scratch = ebc::RolloutScratch<GS>::BYTES;
   const bool sail = io.robot_policy == EBC_ROBOT_SAIL;
@@ -1022,6 +1023,14 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
     static_cast<ebc::RolloutIO &>(ios) = io;
     ios.epg = epg;
     ios.sail = ebc::RolloutSail{h->sail_P, h->sail_N, chunk};
+    if (mixed) {
+      const void *kernel = nullptr;
+      int rc = ebc_mix_api::rollout_kernel(GS, true, &kernel);
+      if (rc != EBC_OK) return rc;
+      void *args[] = {&h->p, &h->s, &ios};
+      HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)((E + epg - 1) / epg)), dim3(EBC_RO_THREADS), args, bytes(epg, chunk), h->stream));
+      return EBC_OK;
+    }
     hipLaunchKernelGGL((ebc::rollout_kernel<GS, true>), dim3((unsigned)((E + epg - 1) / epg)), dim3(EBC_RO_THREADS), bytes(epg, chunk),
                        h->stream, h->p, h->s, ios);
     HIP_TRY(hipGetLastError());
@@ -1034,14 +1043,23 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca) {
   if (lds > 48u * 1024u) return fail(EBC_ERR_UNSUPPORTED, "EBC_FLAG_ONE_LAUNCH: one env needs more than 48 KB of LDS");
   io.epg = epg;
   const unsigned blocks = (unsigned)((E + epg - 1) / epg);
+  if (mixed) {
+    const void *kernel = nullptr;
+    int rc = ebc_mix_api::rollout_kernel(GS, false, &kernel);
+    if (rc != EBC_OK) return rc;
+    void *args[] = {&h->p, &h->s, &io};
+    HIP_TRY(hipLaunchKernel(kernel, dim3(blocks), dim3(EBC_RO_THREADS), args, lds, h->stream));
+    return EBC_OK;
+  }
   hipLaunchKernelGGL((ebc::rollout_kernel<GS>), dim3(blocks), dim3(EBC_RO_THREADS), lds, h->stream, h->p, h->s, io);
   HIP_TRY(hipGetLastError());
   return EBC_OK;
 }
 
-int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca) {
+// mixed: EBC_HUMAN_BY_TYPE (the instantiations of ebcsim_mix.hip)
+int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca, bool mixed) {
   return with_group_size<kDevHumanGs>(h->orca_gs,
-                                      [&](auto gs) { return launch_rollout_gs<decltype(gs)::value>(h, io, robot_orca); });
+                                      [&](auto gs) { return launch_rollout_gs<decltype(gs)::value>(h, io, robot_orca, mixed); });
 }
 
 }  // namespace
@@ -1064,6 +1082,23 @@ int ebc_robot_orca(void *handle, double safety_space, int location, double *acti
   }
   if ((rc = launch_robot_orca(h, safety_space, d_act)) != EBC_OK) return rc;
   if (location != EBC_DEVICE) return st.finish();
+  return EBC_OK;
+}
+
+int ebc_set_human_policies(void *handle, const int32_t policy_of_type[3]) {
+  Handle *h;
+  int rc = check_handle(handle, &h);
+  if (rc) return rc;
+  if (!policy_of_type) return fail(EBC_ERR_INVALID, "ebc_set_human_policies: policy_of_type is NULL");
+  static const char *const kType[3] = {"EBC_ADULT", "EBC_BICYCLE", "EBC_CHILD"};
+  unsigned linear = 0;
+  for (int t = 0; t < 3; ++t) {
+    if (policy_of_type[t] != EBC_HUMAN_ORCA && policy_of_type[t] != EBC_HUMAN_LINEAR)
+      return fail(EBC_ERR_INVALID, std::string("ebc_set_human_policies: policy_of_type[") + kType[t] + "] = " +
+                                       std::to_string(policy_of_type[t]) + " (EBC_HUMAN_ORCA or EBC_HUMAN_LINEAR)");
+    if (policy_of_type[t] == EBC_HUMAN_LINEAR) linear |= 1u << t;
+  }
+  h->s.human_linear = linear;  // travels with every launch from now on (DevState is a kernel argument)
   return EBC_OK;
 }
 
@@ -1160,7 +1195,8 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
       return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH (the window with maps has the per-step form only)");
   }
   if (a->K < 1) return fail(EBC_ERR_INVALID, "K");
-  if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL)
+  if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL &&
+      a->human_policy != EBC_HUMAN_BY_TYPE)
     return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
   if (a->robot_policy != EBC_ROBOT_EXTERNAL && a->robot_policy != EBC_ROBOT_LINEAR && a->robot_policy != EBC_ROBOT_ORCA &&
       a->robot_policy != EBC_ROBOT_SAIL)
@@ -1208,7 +1244,7 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
     io.robot_action = a->robot_policy == EBC_ROBOT_EXTERNAL ? d_act_in : nullptr;
     io.state_rotated = d_state; io.n_rows = d_rows; io.robot_action_out = d_act_out; io.reward = d_reward;
     io.done = d_done; io.info = d_info; io.dmin = d_dmin; io.dist_to_goal = d_goal; io.obs_rotated = d_obs;
-    if ((rc = launch_rollout(h, io, a->robot_policy == EBC_ROBOT_ORCA)) != EBC_OK) return rc;
+    if ((rc = launch_rollout(h, io, a->robot_policy == EBC_ROBOT_ORCA, a->human_policy == EBC_HUMAN_BY_TYPE)) != EBC_OK) return rc;
     if (a->location != EBC_DEVICE) return st.finish();
     return EBC_OK;
   }
@@ -1295,7 +1331,8 @@ int ebc_sail_dagger_k(void *handle, const EbcSailDaggerArgs *a) {
   if (h->faulted) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k: the handle reported a mailbox fault; ebc_reset re-arms it");
   if ((rc = refuse_capture(h, "ebc_sail_dagger_k")) != EBC_OK) return rc;
   if (a->K < 1) return fail(EBC_ERR_INVALID, "K");
-  if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL)
+  if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR && a->human_policy != EBC_HUMAN_EXTERNAL &&
+      a->human_policy != EBC_HUMAN_BY_TYPE)
     return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
   if (!h->sail_P) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k: no network attached (ebc_robot_sail)");
   if ((rc = check_robot_orca(h, a->expert_safety_space)) != EBC_OK) return rc;
@@ -1347,7 +1384,7 @@ static int step_impl(Handle *h, const EbcStepArgs *a, double *local_map, const c
   if (!h->has_reset) return fail(EBC_ERR_STATE, std::string(what) + " before ebc_reset");
   if (h->faulted) return fail(EBC_ERR_STATE, std::string(what) + ": the handle reported a mailbox fault; ebc_reset re-arms it");
   if ((rc = refuse_capture(h, what)) != EBC_OK) return rc;
-  if (a->human_policy < EBC_HUMAN_EXTERNAL || a->human_policy > EBC_HUMAN_CACHED)
+  if (a->human_policy < EBC_HUMAN_EXTERNAL || a->human_policy > EBC_HUMAN_BY_TYPE)
     return fail(EBC_ERR_INVALID, "human_policy");
   if (a->robot_policy == EBC_ROBOT_LINEAR && h->p.robot_kinematics != EBC_HOLONOMIC)
     return fail(EBC_ERR_UNSUPPORTED, "the linear robot policy is holonomic (simulator/policy/linear.py:11)");
@@ -1548,7 +1585,7 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *a) {
   if (!a->actions || a->n_actions <= 0) return fail(EBC_ERR_INVALID, "actions");
   if (a->n_actions > EBC_LA_MAX_ACTIONS) return fail(EBC_ERR_UNSUPPORTED, "more than 128 actions");
   if (a->human_policy != EBC_HUMAN_ORCA && a->human_policy != EBC_HUMAN_LINEAR &&
-      a->human_policy != EBC_HUMAN_EXTERNAL && a->human_policy != EBC_HUMAN_CACHED)
+      a->human_policy != EBC_HUMAN_EXTERNAL && a->human_policy != EBC_HUMAN_CACHED && a->human_policy != EBC_HUMAN_BY_TYPE)
     return fail(EBC_ERR_INVALID, "human_policy");
   if ((a->flags & EBC_FLAG_BORDER) && !a->border) return fail(EBC_ERR_INVALID, "border is NULL");
   const DevState &s = h->s;
@@ -1572,9 +1609,11 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *a) {
     io.info = st.out(a->info, E * A); io.dmin = st.out(a->dmin, E * A * 3);
     io.next_ob = st.out(a->next_ob, E * R * 5); io.rows = st.out(a->rows_rotated, E * A * R * T);
   }
-  if (a->human_policy == EBC_HUMAN_ORCA && (rc = launch_orca(h)) != EBC_OK) return rc;  // -> hact
-  rc = a->human_policy == EBC_HUMAN_LINEAR ? launch_lookahead<EBC_HUMAN_LINEAR>(h, io)
-                                           : launch_lookahead<EBC_HUMAN_EXTERNAL>(h, io);
+  // -> hact (EBC_HUMAN_BY_TYPE: everybody's ORCA velocity; the sweep's phase A replaces those of the humans on `linear`)
+  if ((a->human_policy == EBC_HUMAN_ORCA || a->human_policy == EBC_HUMAN_BY_TYPE) && (rc = launch_orca(h)) != EBC_OK) return rc;
+  rc = a->human_policy == EBC_HUMAN_LINEAR    ? launch_lookahead<EBC_HUMAN_LINEAR>(h, io)
+       : a->human_policy == EBC_HUMAN_BY_TYPE ? launch_lookahead<EBC_HUMAN_BY_TYPE>(h, io)
+                                              : launch_lookahead<EBC_HUMAN_EXTERNAL>(h, io);
   if (rc != EBC_OK) return rc;
   if (a->location != EBC_DEVICE) return st.finish();
   return EBC_OK;

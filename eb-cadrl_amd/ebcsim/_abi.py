@@ -14,6 +14,7 @@ ADULT, BICYCLE, CHILD, ADULT_STATIC, ROBOT = 0, 1, 2, 3, 4
 HOLONOMIC, UNICYCLE = 0, 1
 HOST, DEVICE = 0, 1
 HUMAN_EXTERNAL, HUMAN_LINEAR, HUMAN_ORCA, HUMAN_CACHED = 0, 1, 2, 3
+HUMAN_BY_TYPE = 4  # every entity type on its own policy (ebc_set_human_policies)
 ROBOT_EXTERNAL, ROBOT_LINEAR, ROBOT_ORCA, ROBOT_SAIL = 0, 1, 2, 3
 FLAG_AUTO_RESET, FLAG_BORDER = 1, 2
 FLAG_ONE_LAUNCH = 4  # ebc_step_k: all K steps in one kernel launch (ORCA humans; strict, never a fall-back)

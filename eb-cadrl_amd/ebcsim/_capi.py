@@ -27,6 +27,7 @@ SYMBOLS = {
     "ebc_robot_orca": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_void_p]),
     "ebc_robot_orca_sim": (C.c_int, [C.c_void_p, C.c_int]),
     "ebc_robot_orca_sim_state": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_set_human_policies": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "ebc_step": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ebc_lookahead": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ebc_step_k": (C.c_int, [C.c_void_p, C.c_void_p]),

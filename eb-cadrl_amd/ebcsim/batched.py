@@ -211,6 +211,33 @@ class BatchedEnv:
         a = np.ascontiguousarray(act, dtype=np.float64).reshape(self.E, self.N, 2)
         _capi.check(self._L.ebc_set_human_actions(self._h, _abi.HOST, a.ctypes.data))
 
+    def set_human_policies(self, adult, bicycle, child):
+        """The policy of each entity type for human_policy=HUMAN_BY_TYPE: HUMAN_ORCA or HUMAN_LINEAR each
+        (ebc_set_human_policies; config.human_policies_from_config gives the table of an env config)."""
+        table = (C.c_int32 * 3)(int(adult), int(bicycle), int(child))
+        _capi.check(self._L.ebc_set_human_policies(self._h, table))
+        self._human_policies = (int(adult), int(bicycle), int(child))
+
+    def configure_humans(self, code, table):
+        """The humans of an env config, as config.human_policies_from_config returns them: the reference's env asks every
+        human's own policy (simulator/env.py:392-405), so from now on a call of this env that asks for HUMAN_ORCA — the
+        default of every method here and of the rollout, evaluation and training helpers of this package — runs `code`
+        instead: HUMAN_ORCA itself, HUMAN_LINEAR, or HUMAN_BY_TYPE with `table` set.  The other codes (HUMAN_EXTERNAL,
+        HUMAN_CACHED, an explicit HUMAN_LINEAR or HUMAN_BY_TYPE) are taken as given.  An env that is never configured
+        takes every code as given."""
+        if int(code) == _abi.HUMAN_BY_TYPE:
+            self.set_human_policies(*table)
+        self._configured_humans = int(code)
+
+    def _humans(self, human_policy):
+        code = int(human_policy)
+        return getattr(self, "_configured_humans", code) if code == _abi.HUMAN_ORCA else code
+
+    @property
+    def human_policies(self):
+        """(adult, bicycle, child) as last set; a fresh env holds three HUMAN_ORCA."""
+        return getattr(self, "_human_policies", (_abi.HUMAN_ORCA,) * 3)
+
     def step(self, robot_action=None, human_policy=_abi.HUMAN_ORCA,
              robot_policy=_abi.ROBOT_EXTERNAL, flags=0, border=None, outputs=None, local_map=False):
         """local_map=True: also out["local_map"] [E, dim], the map of the post-step state (ebc_step_with_map)."""
@@ -224,7 +251,7 @@ class BatchedEnv:
         args = _abi.EbcStepArgs()
         args.struct_size = C.sizeof(args)
         args.location = _abi.HOST
-        args.human_policy, args.robot_policy = int(human_policy), int(robot_policy)
+        args.human_policy, args.robot_policy = self._humans(human_policy), int(robot_policy)
         ra = b = None
         if robot_action is not None:
             ra = np.ascontiguousarray(robot_action, dtype=np.float64).reshape(E, 2)
@@ -255,7 +282,7 @@ class BatchedEnv:
         args = _abi.EbcLookaheadArgs()
         args.struct_size = C.sizeof(args)
         args.location = _abi.HOST
-        args.human_policy, args.n_actions = int(human_policy), A
+        args.human_policy, args.n_actions = self._humans(human_policy), A
         args.actions = actions.ctypes.data
         b = None
         if border is not None:
@@ -421,14 +448,14 @@ class BatchedEnv:
         ebc_step_with_map."""
         key = (tuple((k, t.data_ptr()) for k, t in outputs.items()),
                None if robot_action is None else robot_action.data_ptr(),
-               int(human_policy), int(robot_policy), int(flags))
+               self._humans(human_policy), int(robot_policy), int(flags))
         cache = self.__dict__.setdefault("_step_args", {})
         args = cache.get(key)
         if args is None:
             args = _abi.EbcStepArgs()
             args.struct_size = C.sizeof(args)
             args.location = _abi.DEVICE
-            args.human_policy, args.robot_policy = int(human_policy), int(robot_policy)
+            args.human_policy, args.robot_policy = self._humans(human_policy), int(robot_policy)
             args.flags = int(flags)
             if robot_action is not None:
                 if robot_action.dtype.itemsize != 8 or robot_action.numel() != self.E * 2:
@@ -462,7 +489,7 @@ class BatchedEnv:
         args = _abi.EbcStepKArgs()
         args.struct_size = C.sizeof(args)
         args.location, args.K = location, int(K)
-        args.human_policy, args.robot_policy, args.flags = int(human_policy), int(robot_policy), int(flags)
+        args.human_policy, args.robot_policy, args.flags = self._humans(human_policy), int(robot_policy), int(flags)
         args.robot_safety_space = float(robot_safety_space)
         args.robot_action = robot_action_ptr
         for k, v in ptr.items():
@@ -550,7 +577,7 @@ class BatchedEnv:
         shapes = self._DAGGER_SHAPES(self.E, self.R)
         args = _abi.EbcSailDaggerArgs()
         args.struct_size = C.sizeof(args)
-        args.K, args.human_policy, args.flags = int(K), int(human_policy), int(flags)
+        args.K, args.human_policy, args.flags = int(K), self._humans(human_policy), int(flags)
         args.expert_safety_space = float(safety_space)
         for k, t in outputs.items():
             if k not in shapes:
@@ -583,7 +610,7 @@ class BatchedEnv:
         args = _abi.EbcLookaheadArgs()
         args.struct_size = C.sizeof(args)
         args.location = _abi.DEVICE
-        args.human_policy, args.n_actions = int(human_policy), int(actions.shape[0])
+        args.human_policy, args.n_actions = self._humans(human_policy), int(actions.shape[0])
         args.flags = int(flags)
         if actions.dtype.itemsize != 8 or actions.dim() != 2 or actions.shape[1] != 2:
             raise ValueError("actions must be float64 [A, 2]")

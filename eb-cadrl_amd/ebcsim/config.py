@@ -70,6 +70,33 @@ def params_from_config(env_cfg, policy_cfg=None, robot_kinematics=None, policy="
     return p
 
 
+_HUMAN_POLICY_CODE = {"orca": _abi.HUMAN_ORCA, "linear": _abi.HUMAN_LINEAR}
+_HUMAN_SECTIONS = (("adults", "adult_num"), ("bicycles", "bicycle_num"), ("children", "children_num"))
+
+
+def human_policies_from_config(env_cfg):
+    """The humans' policies of an env config -> (code, table).  Every entity type carries its own `policy` key
+    (simulator/agents/agent.py:19, simulator/policy/policy_factory.py:10-14) and env.step asks every human's own policy
+    (simulator/env.py:392-405); as the reference's env does, only the sections of the types the scene has are read.
+    A uniform config returns the plain code (HUMAN_ORCA, also with no human at all, or HUMAN_LINEAR) and a table of three
+    of it; a mix of `orca` and `linear` returns HUMAN_BY_TYPE and the table for BatchedEnv.set_human_policies (adult,
+    bicycle, child; a type the scene does not have stays on ORCA).  Any other policy name is refused by name."""
+    from .scene import SceneConfig
+    sc = SceneConfig.from_config(env_cfg)
+    names = {}
+    for t, (section, count) in enumerate(_HUMAN_SECTIONS):
+        if getattr(sc, count) and env_cfg.has_section(section):
+            names[t] = env_cfg.get(section, "policy")
+    bad = sorted(set(n for n in names.values() if n not in _HUMAN_POLICY_CODE))
+    if bad:
+        raise NotImplementedError("human policies %s: each entity type takes one of orca / linear" % bad)
+    kinds = set(names.values())
+    if len(kinds) <= 1:
+        code = _HUMAN_POLICY_CODE[kinds.pop()] if kinds else _abi.HUMAN_ORCA
+        return code, (code, code, code)
+    return _abi.HUMAN_BY_TYPE, tuple(_HUMAN_POLICY_CODE[names[t]] if t in names else _abi.HUMAN_ORCA for t in range(3))
+
+
 def occupancy_from_config(policy_cfg, policy="sarl"):
     """The occupancy maps a policy config asks for: an ebcsim.occupancy.OccupancySpec for policy "sarl" with [sarl]
     with_om = true (OM-SARL, multi_human_rl.py:151-227) and for policy "om_lstm_rl" with [lstm_rl] with_om = true

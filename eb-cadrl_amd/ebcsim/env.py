@@ -15,7 +15,7 @@ from .agents import AgentType, HumanView, KIND
 from .policy import DeviceHumanPolicy
 from .state import ObservableState
 
-_POLICY_CODE = {"orca": _abi.HUMAN_ORCA, "linear": _abi.HUMAN_LINEAR}
+_POLICY_NAME = {_abi.HUMAN_ORCA: "orca", _abi.HUMAN_LINEAR: "linear"}
 
 
 class _SceneFacade(object):
@@ -84,16 +84,8 @@ class EntityBasedCollisionAvoidance(object):
         self.angular_map_min_angle = config.getfloat("map", "angle_min") * np.pi
         self.angular_map_max_angle = config.getfloat("map", "angle_max") * np.pi
         self.local_maps_angular = None
-        kinds = set()
-        for section, count in (("adults", self._scene_cfg.adult_num),
-                               ("bicycles", self._scene_cfg.bicycle_num),
-                               ("children", self._scene_cfg.children_num)):
-            if count and config.has_section(section):
-                kinds.add(config.get(section, "policy"))
-        if len(kinds) > 1 or (kinds and not kinds <= set(_POLICY_CODE)):
-            raise NotImplementedError("human policies %s: one of orca / linear for all humans" % sorted(kinds))
-        self._human_policy_name = kinds.pop() if kinds else "orca"
-        self._human_policy = _POLICY_CODE[self._human_policy_name]
+        # every entity type on its own policy (env.py:88-92); a mix is EBC_HUMAN_BY_TYPE with the table set on the backend
+        self._human_policy, self._human_table = ebc_config.human_policies_from_config(config)
 
     def set_robot(self, robot):
         self.robot = robot
@@ -114,6 +106,11 @@ class EntityBasedCollisionAvoidance(object):
             else:
                 from .batched import BatchedEnv
                 self._backend = BatchedEnv(params, 1, n_humans, n_static, device=self._device)
+            if self._human_policy == _abi.HUMAN_BY_TYPE:
+                if not hasattr(self._backend, "set_human_policies"):
+                    raise NotImplementedError("human policies %s: this backend takes one of orca / linear for all humans"
+                                              % sorted(set(_POLICY_NAME[c] for c in self._human_table)))
+                self._backend.set_human_policies(*self._human_table)
             self._params = params
             self._backend_key = key
             # the angular local map on the device when the backend has it (the CPU tests' oracle backends do not:
@@ -186,11 +183,11 @@ class EntityBasedCollisionAvoidance(object):
         sc.children_num = sum(h.type == _abi.CHILD for h in scene.humans)
         self.reset_times(phase)
 
-        marker = DeviceHumanPolicy(self._human_policy_name.upper(), self._human_policy)
+        markers = [DeviceHumanPolicy(_POLICY_NAME[c].upper(), c) for c in self._human_table]  # per entity type
         self._humans = []
         sc.adults, sc.bicycles, sc.children = [], [], []
         for h in scene.humans:
-            v = HumanView(AgentType(int(h.type)), marker)
+            v = HumanView(AgentType(int(h.type)), markers[int(h.type)])
             v.set(h.px, h.py, h.gx, h.gy, h.vx, h.vy, h.theta, h.radius, h.v_pref)
             v.time_step = self.time_step
             self._humans.append(v)
@@ -249,13 +246,13 @@ class EntityBasedCollisionAvoidance(object):
         state computes the humans' velocities and leaves them cached in the backend, every later query
         of the same state — the other 80 of MultiHumanRL.predict's loop, and the real step that follows
         — reads them (EBC_HUMAN_CACHED)."""
-        if self._human_policy != _abi.HUMAN_ORCA:
+        if self._human_policy not in (_abi.HUMAN_ORCA, _abi.HUMAN_BY_TYPE):  # a mix has ORCA humans: evaluated once too
             return self._human_policy
         if self._humans_cached:
             return _abi.HUMAN_CACHED
         self._humans_cached = True
         self.orca_evaluations += 1
-        return _abi.HUMAN_ORCA
+        return self._human_policy
 
     def lookahead_all(self, actions):
         """All candidate actions in one launch: what MultiHumanRL.predict's loop asks for

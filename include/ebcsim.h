@@ -76,7 +76,8 @@ enum {
   EBC_HUMAN_EXTERNAL = 0, /* velocities given by ebc_set_human_actions (BASELINE config 2) */
   EBC_HUMAN_LINEAR = 1,   /* simulator/policy/linear.py:17-23 */
   EBC_HUMAN_ORCA = 2,     /* simulator/policy/orca.py:85-157 (+ rvo2) */
-  EBC_HUMAN_CACHED = 3    /* re-use the velocities the last ebc_lookahead computed for the same state */
+  EBC_HUMAN_CACHED = 3,   /* re-use the velocities the last ebc_lookahead computed for the same state */
+  EBC_HUMAN_BY_TYPE = 4   /* every entity type on its own policy (ebc_set_human_policies) */
 };
 
 enum {
@@ -290,6 +291,28 @@ int ebc_generate_pool(void *handle, const EbcSceneGen *gen, uint32_t seed0, cons
 /* Humans moved by the host (BASELINE config 2): act[E][N][2]. */
 int ebc_set_human_actions(void *handle, int location, const double *act);
 
+/* EBC_HUMAN_BY_TYPE: a policy per entity type.  The reference gives [adults], [bicycles] and [children] a `policy` key
+ * each (simulator/agents/agent.py:19, simulator/policy/policy_factory.py:10-14) and env.step asks every human's own
+ * policy object for its action (simulator/env.py:392-405), so adults on ORCA among bicycles that ride straight on
+ * `linear` is a valid scene.  policy_of_type[t], t = EBC_ADULT, EBC_BICYCLE, EBC_CHILD, is EBC_HUMAN_ORCA or
+ * EBC_HUMAN_LINEAR; anything else is EBC_ERR_INVALID and ebc_last_error names the entry.  A fresh handle holds three
+ * EBC_HUMAN_ORCA; the table stays until it is set again (ebc_reset and restarts do not touch it).
+ *   The rule.  From the pre-step state a human of type t takes the velocity that policy_of_type[t] gives it:
+ * EBC_HUMAN_ORCA the velocity EBC_HUMAN_ORCA gives that human from the same state, bit for bit (its neighbours are all
+ * the others with their current velocities, humans on `linear` included, and the robot when robot_visible);
+ * EBC_HUMAN_LINEAR the one EBC_HUMAN_LINEAR gives it.  The rest of the step is the step with those velocities: every
+ * output and the state left behind are what EBC_HUMAN_EXTERNAL leaves when it is given exactly those [E][N][2] doubles.
+ * So a table of three EBC_HUMAN_ORCA is an EBC_HUMAN_ORCA step and a table of three EBC_HUMAN_LINEAR an
+ * EBC_HUMAN_LINEAR step.
+ *   Every entry that takes a human_policy takes the code: ebc_step, ebc_step_with_map, ebc_lookahead (the humans are
+ * evaluated once; a following EBC_HUMAN_CACHED step reads the mixed velocities), ebc_step_k and ebc_step_k_om with every
+ * robot policy, and ebc_sail_dagger_k.  ebc_step is ONE launch as with EBC_HUMAN_ORCA (and what is said of that launch
+ * at ebc_step holds); the groups of the humans on `linear` solve nothing.  EBC_FLAG_ONE_LAUNCH takes the code with any
+ * table, bit for bit the per-step form as for every other combination: a table of three EBC_HUMAN_LINEAR is the way to
+ * roll linear humans out in one launch (plain EBC_HUMAN_LINEAR stays refused there).
+ *   The call waits for the handle's stream: no enqueued launch sees the table change. */
+int ebc_set_human_policies(void *handle, const int32_t policy_of_type[3]);
+
 /* The observation of the CURRENT state, without stepping: what env.reset returns
  * (simulator/env.py:188-193) and what MultiHumanRL.transform builds from it
  * (rl/policy/multi_human_rl.py:128-149).  ob [E][R][5], obs_rotated [E][R][T]; either may be NULL. */
@@ -348,7 +371,7 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *args);
  *     per-step form: humans, robot, time, arrival, done, float tile, grid slot, pool cursor and the persistent
  *     simulators of ebc_robot_orca_sim hold what K per-step steps would have left, so ebc_step, ebc_lookahead,
  *     ebc_observe, ebc_get_state, ebc_local_map and a further ebc_step_k of either form continue from it.
- *   - Covers EBC_HUMAN_ORCA with each robot policy (EBC_ROBOT_EXTERNAL reading robot_action[k], EBC_ROBOT_LINEAR,
+ *   - Covers EBC_HUMAN_ORCA and EBC_HUMAN_BY_TYPE (any table, ebc_set_human_policies) with each robot policy (EBC_ROBOT_EXTERNAL reading robot_action[k], EBC_ROBOT_LINEAR,
  *     EBC_ROBOT_ORCA with or without the persistent simulator), with and without EBC_FLAG_AUTO_RESET, own-scene
  *     and installed pools, both row widths, holonomic and unicycle robots where the per-step form takes them,
  *     every output optional, host and device location.
@@ -378,7 +401,7 @@ typedef struct EbcStepKArgs {
   uint32_t struct_size;
   int32_t location;      /* of every pointer below */
   int32_t K;             /* steps, >= 1 */
-  int32_t human_policy;  /* EBC_HUMAN_ORCA, _LINEAR or _EXTERNAL (the same supplied velocities every step) */
+  int32_t human_policy;  /* EBC_HUMAN_ORCA, _LINEAR, _BY_TYPE or _EXTERNAL (the same supplied velocities every step) */
   int32_t robot_policy;  /* EBC_ROBOT_ORCA, _LINEAR, _EXTERNAL or _SAIL */
   int32_t flags;
   double robot_safety_space;  /* EBC_ROBOT_ORCA: the policy's safety_space (rl/train.py:127-129) */

@@ -106,6 +106,9 @@ def main():
         v_pref = float(batch.robot[0, 7])
     t1 = time.perf_counter()
     env.use_torch_stream()
+    # the humans' policy is the env config's ([adults] / [bicycles] / [children] policy; a mix runs EBC_HUMAN_BY_TYPE):
+    # what asks for HUMAN_ORCA below runs it
+    env.configure_humans(*ebc_config.human_policies_from_config(cfg))
     if args.policy in ("sarl", "lstm_rl", "cadrl"):
         make_policy = DeviceSarlPolicy
         if args.policy == "lstm_rl":
@@ -126,7 +129,7 @@ def main():
     elif args.policy == "sail":
         from ebcsim.sail import DeviceSailPolicy, SailNet
         policy = DeviceSailPolicy(SailNet.load(weights, device="cuda:0"))
-        # no look-ahead, so no human velocities are cached: the humans' own ORCA runs inside the step
+        # no look-ahead, so no human velocities are cached: the humans' own policy runs inside the step
         decide, hp = (lambda e: policy.decide(e)[0]), _abi.HUMAN_ORCA
     else:
         act = torch.zeros((args.cases, 2), dtype=torch.float64, device="cuda:0")

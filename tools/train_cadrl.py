@@ -72,6 +72,7 @@ def main():
     cfg.read(args.env_config)
     pol.read(args.policy_config)
     params = ebc_config.params_from_config(cfg, pol, policy="cadrl")
+    humans = ebc_config.human_policies_from_config(cfg)  # the env config's, per entity type
     gamma = args.gamma if args.gamma is not None else pol.getfloat("rl", "gamma", fallback=0.9)
     dims = [int(x) for x in pol.get("cadrl", "mlp_dims", fallback=args.mlp_dims).split(",")]
     sc = ebc_scene.SceneConfig.from_config(cfg)
@@ -86,6 +87,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
+        env.configure_humans(*humans)
         policy = DeviceCadrlPolicy(CadrlValueNet.load(path, device="cuda:0"), space, gamma)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
@@ -101,6 +103,7 @@ def main():
     E = args.envs
     env = BatchedEnv(params, E, sum(gen.count), S)
     env.use_torch_stream()
+    env.configure_humans(*humans)
     seed0 = ebc_scene.COUNTER_OFFSET["train"]
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 8 * E)

@@ -87,6 +87,7 @@ def main():
     cfg.read(args.env_config)
     pol.read(args.policy_config)
     params = ebc_config.params_from_config(cfg, pol)
+    humans = ebc_config.human_policies_from_config(cfg)  # the env config's, per entity type
     gamma = args.gamma if args.gamma is not None else pol.getfloat("rl", "gamma", fallback=0.9)
     dims = {k: [int(x) for x in pol.get("lstm_rl", k, fallback=d).split(",")] for k, d in (
         ("mlp1_dims", "150, 100, 100, 50"), ("mlp2_dims", "150, 100, 100, 1"))}
@@ -107,6 +108,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
+        env.configure_humans(*humans)
         policy = DeviceSarlPolicy(LstmValueNet.load(path, device="cuda:0"), space, gamma, **kw_om)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
@@ -122,6 +124,7 @@ def main():
     E = args.envs
     env = BatchedEnv(params, E, sum(gen.count), S)
     env.use_torch_stream()
+    env.configure_humans(*humans)
     seed0 = ebc_scene.COUNTER_OFFSET["train"]
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 8 * E)

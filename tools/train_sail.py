@@ -62,6 +62,7 @@ def main():
     cfg.read(args.env_config)
     pol.read(args.policy_config)
     params = ebc_config.params_from_config(cfg, pol, policy="sail")
+    humans = ebc_config.human_policies_from_config(cfg)  # the env config's, per entity type
     sc = ebc_scene.SceneConfig.from_config(cfg)
     gen = ebc_scene.gen_struct(sc, "train")
     N = sum(gen.count)
@@ -76,8 +77,9 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
+        env.configure_humans(*humans)
         policy = DeviceSailPolicy(SailNet.load(args.out, device="cuda:0"))
-        m = evaluate(env, lambda e: policy.decide(e)[0], args.gamma, human_policy=_abi.HUMAN_ORCA)
+        m = evaluate(env, lambda e: policy.decide(e)[0], args.gamma)
         torch.cuda.synchronize()
         env.close()
         print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
@@ -90,6 +92,7 @@ def main():
 
     env = BatchedEnv(params, E, N, 0)
     env.use_torch_stream()
+    env.configure_humans(*humans)
     seed0 = ebc_scene.COUNTER_OFFSET["train"]
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 4 * E)

@@ -91,6 +91,7 @@ def main():
     cfg.read(args.env_config)
     pol.read(args.policy_config)
     params = ebc_config.params_from_config(cfg, pol)
+    humans = ebc_config.human_policies_from_config(cfg)  # the env config's, per entity type
     gamma = args.gamma if args.gamma is not None else pol.getfloat("rl", "gamma", fallback=0.9)
     dims = {k: [int(x) for x in pol.get("sarl", k, fallback=d).split(",")] for k, d in (
         ("mlp1_dims", "150, 100"), ("mlp2_dims", "100, 50"), ("attention_dims", "100, 100, 1"), ("mlp3_dims", "150, 100, 100, 1"))}
@@ -111,6 +112,7 @@ def main():
         env.generate_reset(test, ebc_scene.COUNTER_OFFSET["test"])
         env.synchronize()
         env.use_torch_stream()
+        env.configure_humans(*humans)
         policy = DeviceSarlPolicy(SarlValueNet.load(path, device="cuda:0", with_global_state=with_global_state, **wide_kw), space, gamma, **om_kw)
         m = evaluate(env, lambda e: policy.decide(e)[0], gamma, human_policy=_abi.HUMAN_CACHED)
         torch.cuda.synchronize()
@@ -126,6 +128,7 @@ def main():
     E = args.envs
     env = BatchedEnv(params, E, sum(gen.count), S)
     env.use_torch_stream()
+    env.configure_humans(*humans)
     seed0 = ebc_scene.COUNTER_OFFSET["train"]
     env.generate_reset(gen, seed0)
     env.generate_pool(gen, seed0 + E, 8 * E)
