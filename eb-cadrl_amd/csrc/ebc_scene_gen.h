@@ -3,15 +3,18 @@
 // What the reference does on the host at every env.reset (simulator/scene/scene_generator.py:330-378):
 // seed numpy's legacy MT19937 stream with the scene's number, place the humans type by type under the
 // configured crossing rule with rejection sampling (circle_crossing :593-648, square_crossing :650-712,
-// square_crossing_old :714-761, attributes agents/agent.py:48-56), draw the static map (circles and walls,
-// :109-328), rasterise it (place_obstacles_on_map :888-922) and turn the obstacles into observation rows
+// square_crossing_old :714-761, for adults also the crowd rules mixed, mixed_20 and one_static :523-589 with
+// generate_static_adults :459-490 and generate_dynamic_adults :492-501; attributes agents/agent.py:48-56),
+// draw the static map (circles and walls, :109-328), rasterise it (place_obstacles_on_map :888-922) and turn the obstacles into observation rows
 // (create_observation_from_static_obstacles :380-422).  Here a lane owns one scene: its MT19937 state
 // lives in a strided global scratch array, every draw is numpy's legacy draw (random_sample = 53 bits of
 // two words, uniform = low + (high - low) * u, randint = masked rejection on 32-bit words, choice = randint
 // or the cumulative-probability search), every rejection test the reference's, in its order.  Seed s here
 // is therefore scene s there: all of it bit for bit except cos/sin of circle_crossing, which numpy
 // evaluates with a CPU-dependent SIMD routine (<= 1 ulp); this file's sincos_dd is correctly rounded in
-// all but ~2^-12 of the cases, so circle positions agree with a given host to <= 1 ulp (tests state it).
+// all but ~2^-12 of the cases, so cos / sin agree with a given host to <= 1 ulp (tests state it); a position is
+// circle_radius times that, and where the product crosses into the next binade (circle_radius no power of two) the
+// same difference can be 2 ulps of the position.
 //
 // The file is plain C++ with the host/device qualifier as a macro: tests/ compile it with g++ and check
 // it against ebcsim/scene.py on the CPU; the product compiles it with hipcc into scene_gen_kernel.
@@ -158,6 +161,15 @@ EBC_HD long py_round(double x) { return (long)nearbyint(x); }
 
 #define EBC_GEN_MAX_TRIES 100000  // scene_generator.py:11
 
+// Adult slots a scene of a crowd rule can take (include/ebcsim.h), 0 for every other code: the one place that says which
+// codes are crowd rules, for validate_gen and for the generator
+EBC_HD int crowd_capacity(int rule) {
+  return rule == EBC_RULE_MIXED      ? EBC_CROWD_MIXED_ADULTS
+         : rule == EBC_RULE_MIXED_20 ? EBC_CROWD_MIXED_20_ADULTS
+         : rule == EBC_RULE_ONE_STATIC ? EBC_CROWD_ONE_STATIC_ADULTS
+                                       : 0;
+}
+
 // Destination rows of one scene (row r of arrays shaped like an EbcScene's)
 struct SceneRow {
   int *n_humans;
@@ -193,14 +205,13 @@ struct SceneGenCore {
     return false;
   }
 
-  EBC_HD void place(int slot, int kind, int first, int count) {
+  EBC_HD void place(int slot, int kind, int first, int count, int rule) {
     double radius = c.radius[kind], v_pref = c.v_pref[kind];
     if (c.randomize_attributes) {  // Agent.sample_random_attributes, agent.py:48-56
       v_pref = rs.uniform(c.v_pref_min[kind], c.v_pref_max[kind]);
       radius = rs.uniform(c.radius_min[kind], c.radius_max[kind]);
     }
     double px = 0, py = 0, gx = 0, gy = 0;
-    const int rule = c.rule[kind];
     if (rule == EBC_RULE_CIRCLE_CROSSING) {  // scene_generator.py:593-648
       for (int t = 0; t < EBC_GEN_MAX_TRIES; ++t) {
         const double angle = rs.next_double() * 3.141592653589793 * 2;
@@ -249,6 +260,79 @@ struct SceneGenCore {
     o.vx[slot] = 0; o.vy[slot] = 0;
     o.radius[slot] = radius; o.v_pref[slot] = v_pref;
     o.type[slot] = (uint8_t)kind;
+  }
+
+  // ---- the crowd rules of generate_random_adult_position (:523-589): adults that stand, then adults that walk
+  // how many adults this scene has, how many of them stand (the first ones), and how many of the walking ones take
+  // the circle rule (the first ones; the rest take the square rule)
+  EBC_HD void crowd_plan(int rule, int &count, int &standing, int &on_circle) {
+    if (rule == EBC_RULE_ONE_STATIC) {  // :583-589
+      count = standing = EBC_CROWD_ONE_STATIC_ADULTS;
+      on_circle = 0;
+    } else if (rule == EBC_RULE_MIXED_20) {  // :577-582, generate_dynamic_adults :492-501
+      count = EBC_CROWD_MIXED_20_ADULTS;
+      standing = (int)rs.randint(0, EBC_CROWD_MIXED_20_ADULTS);
+      on_circle = (count - standing) / 2;
+    } else {
+      // mixed, :523-537: the sorted table is walked with the running remainder, in double as Python does
+      // standing {0: .05, 1: .2, 2: .2, 3: .3, 4: .1, 5: .15}, walking {1: .3, 2: .3, 3: .2, 4: .1, 5: .1}
+      const bool stand = rs.next_double() < 0.2;
+      double prob = rs.next_double();
+      // no key breaking leaves the reference's adult_num as it was passed in; only rounding could get there, and
+      // no seed reaches it: the largest draw, 1 - 2^-53, still breaks at the last key of either table
+      count = c.count[0] < EBC_CROWD_MIXED_ADULTS ? c.count[0] : EBC_CROWD_MIXED_ADULTS;
+      for (int k = 0; k < (stand ? 6 : 5); ++k) {
+        const double value = stand ? (k == 0 ? 0.05 : k == 3 ? 0.3 : k == 4 ? 0.1 : k == 5 ? 0.15 : 0.2)
+                                   : (k < 2 ? 0.3 : k == 2 ? 0.2 : 0.1);
+        if (prob - value <= 0) {
+          count = stand ? k : k + 1;
+          break;
+        }
+        prob -= value;
+      }
+      standing = stand ? count : 0;
+      on_circle = 2;
+    }
+  }
+
+  // a standing adult at a given place: constructed and set down, goal = position.  The reference never calls
+  // sample_random_attributes for it, so there is no attribute draw and the fixed attributes hold
+  EBC_HD void put_standing(int slot, double px, double py) {
+    o.px[slot] = px; o.py[slot] = py; o.gx[slot] = px; o.gy[slot] = py;
+    o.vx[slot] = 0; o.vy[slot] = 0;
+    o.radius[slot] = c.radius[0]; o.v_pref[slot] = c.v_pref[0];
+    o.type[slot] = (uint8_t)EBC_ADULT;
+  }
+
+  // standing adult number `count` of its rule: the fixed places of one_static and of mixed_20's first adult, or a draw
+  // into the rule's box against the robot and the adults so far
+  EBC_HD void place_standing(int slot, int first, int count, int rule) {
+    const double radius = c.radius[0];
+    double px = 0, py = 0;
+    if (rule == EBC_RULE_ONE_STATIC) {  // :583-589
+      px = count == 0 ? -2.0 : -3.0;
+      py = -8.0;
+    } else if (rule == EBC_RULE_MIXED) {  // :546-566: a 4 x 8 box, positions only
+      const double sign = rs.next_double() > 0.5 ? -1.0 : 1.0;
+      for (int t = 0; t < EBC_GEN_MAX_TRIES; ++t) {
+        px = rs.next_double() * 4.0 * 0.5 * sign;
+        py = (rs.next_double() - 0.5) * 8.0;
+        if (!clash_pos(px, py, radius, first, count, false)) break;
+      }
+    } else if (count == 0) {  // generate_static_adults(n, 6, 8), :459-490: the first one is put down
+      px = -0.5;
+      py = -2.5;
+    } else {
+      const double sign = rs.next_double() < 0.5 ? 1.0 : -1.0;  // choice([1, -1], p=[0.5, 0.5])
+      for (int t = 0; t < EBC_GEN_MAX_TRIES; ++t) {
+        px = rs.next_double() * 6.0 * 0.5 * sign;
+        py = (rs.next_double() - 0.5) * 8.0;
+        if (clash_pos(px, py, radius, first, count, false)) continue;
+        // the robot's goal, with the radius of `agent` as the loop above left it: nothing clashed, so the last adult
+        if (!(gen_hyp(px - rgx, py - rgy) < radius + o.radius[first + count - 1] + c.discomfort_dist)) break;
+      }
+    }
+    put_standing(slot, px, py);
   }
 
   EBC_HD void clear_cell(long x, long y) const { o.grid[x * 2 + (y >> 6)] |= 1ull << (y & 63); }
@@ -312,8 +396,18 @@ struct SceneGenCore {
   EBC_HD int run() {
     int slot = 0;
     for (int kind = 0; kind < 3; ++kind) {
-      const int first = slot;
-      for (int q = 0; q < c.count[kind]; ++q, ++slot) place(slot, kind, first, q);
+      const int first = slot, rule = c.rule[kind];
+      if (kind == EBC_ADULT && rule >= EBC_RULE_MIXED && rule <= EBC_RULE_ONE_STATIC) {  // crowd_capacity(rule) > 0
+        int count, standing, on_circle;
+        crowd_plan(rule, count, standing, on_circle);
+        if (count == 0) put_standing(slot++, 0.0, -10.0);  // mixed, :542-545: a standing crowd of none is one adult far off
+        for (int q = 0; q < count; ++q, ++slot) {
+          if (q < standing) place_standing(slot, first, q, rule);
+          else place(slot, kind, first, q, q - standing < on_circle ? EBC_RULE_CIRCLE_CROSSING : EBC_RULE_SQUARE_CROSSING);
+        }
+        continue;
+      }
+      for (int q = 0; q < c.count[kind]; ++q, ++slot) place(slot, kind, first, q, rule);
     }
     *o.n_humans = slot;
     for (; slot < N; ++slot) {

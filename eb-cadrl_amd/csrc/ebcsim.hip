@@ -760,9 +760,16 @@ int validate_gen(const Handle *h, const EbcSceneGen *g, int n) {
   long total = 0;
   for (int t = 0; t < 3; ++t) {
     if (g->count[t] < 0) return fail(EBC_ERR_INVALID, "EbcSceneGen.count");
-    total += g->count[t];
-    if (!g->count[t]) continue;
     const int r = g->rule[t];
+    // the crowd rules place a number of adults of their own whatever count[0] says (scene_generator.py:523-589);
+    // the generator asks the same function, so a code that is no crowd rule here places count[t] humans there
+    const int crowd = ebc::crowd_capacity(r);
+    if (crowd && t != EBC_ADULT)
+      return fail(EBC_ERR_INVALID, r == EBC_RULE_MIXED      ? "the mixed rule is defined for adults only"
+                                   : r == EBC_RULE_MIXED_20 ? "the mixed_20 rule is defined for adults only"
+                                                            : "the one_static rule is defined for adults only");
+    total += crowd ? crowd : g->count[t];
+    if (crowd || !g->count[t]) continue;
     if (r != EBC_RULE_CIRCLE_CROSSING && r != EBC_RULE_SQUARE_CROSSING && r != EBC_RULE_SQUARE_CROSSING_OLD)
       return fail(EBC_ERR_INVALID, "EbcSceneGen.rule");
     // what the reference itself cannot run (scene_generator.py:449-457 raises for children on the circle; the
@@ -811,6 +818,11 @@ int generate_batch(Handle *h, const EbcSceneGen *gen, uint32_t seed0, const uint
   if (rc == EBC_OK && seeds) rc = get(&dseeds, n);
   if (rc) return rc;
   HIP_TRY(hipMemsetAsync(status, 0, sizeof(int), h->stream));
+  if (!S) {  // one placeholder row per scene that the kernel has no reason to write: ebc_generate_scenes copies it out
+    HIP_TRY(hipMemsetAsync(d.spx, 0, nS * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(d.spy, 0, nS * sizeof(double), h->stream));
+    HIP_TRY(hipMemsetAsync(d.sradius, 0, nS * sizeof(double), h->stream));
+  }
   if (seeds) HIP_TRY(hipMemcpyAsync(dseeds, seeds, (size_t)n * sizeof(uint32_t), hipMemcpyHostToDevice, h->stream));
   hipLaunchKernelGGL(ebc::scene_gen_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, h->stream, *gen, (const uint32_t *)dseeds,
                      seed0, n, N, S, G, d, mt, status);

@@ -78,6 +78,9 @@ class EbcSceneOut(C.Structure):
 
 
 RULE_CIRCLE_CROSSING, RULE_SQUARE_CROSSING, RULE_SQUARE_CROSSING_OLD = 0, 1, 2
+RULE_MIXED, RULE_MIXED_20, RULE_ONE_STATIC = 3, 4, 5  # the crowd rules: adults only
+# adult slots a scene of a crowd rule can take, whatever adult_num says (scene_generator.py:523-589)
+CROWD_CAPACITY = {RULE_MIXED: 5, RULE_MIXED_20: 20, RULE_ONE_STATIC: 2}
 
 
 class EbcStepArgs(C.Structure):

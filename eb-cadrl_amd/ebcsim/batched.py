@@ -169,8 +169,9 @@ class BatchedEnv:
 
     def _note_generated(self, gen):
         humans = sum(gen.count)
+        # a crowd rule draws the number of adults per scene (count[0] is its capacity): ragged whatever the sizes say
         self.ragged = bool(getattr(self, "ragged", False) or humans < self.N or gen.num_walls > 0
-                           or gen.num_circles < self.S)
+                           or gen.num_circles < self.S or gen.rule[0] in _abi.CROWD_CAPACITY)
 
     def generate_scenes(self, gen, seeds, n):
         """n generated scenes copied back as a scene.SceneBatch (what generate_scene + from_scenes build on the host)."""

@@ -118,7 +118,10 @@ def max_static_rows(cfg: "SceneConfig") -> int:
 
 
 _RULES = {"circle_crossing": _abi.RULE_CIRCLE_CROSSING, "square_crossing": _abi.RULE_SQUARE_CROSSING,
-          "square_crossing_old": _abi.RULE_SQUARE_CROSSING_OLD}
+          "square_crossing_old": _abi.RULE_SQUARE_CROSSING_OLD, "mixed": _abi.RULE_MIXED,
+          "mixed_20": _abi.RULE_MIXED_20, "one_static": _abi.RULE_ONE_STATIC}
+# the crowd rules (scene_generator.py:523-589): adults only; each sets the number of adults itself
+CROWD_RULES = {name: _abi.CROWD_CAPACITY[_RULES[name]] for name in ("mixed", "mixed_20", "one_static")}
 
 
 def gen_struct(cfg: SceneConfig, phase: str = "test", multiagent_training: bool = True) -> "_abi.EbcSceneGen":
@@ -135,15 +138,21 @@ def gen_struct(cfg: SceneConfig, phase: str = "test", multiagent_training: bool 
     g.randomize_attributes = int(bool(cfg.randomize_attributes))
     for t, (spec, rule, count) in enumerate(zip((cfg.adults, cfg.bicycles, cfg.children), rules, counts)):
         n = count if many else 1
+        crowd = t == _abi.ADULT and rule in CROWD_RULES
+        if crowd:  # the rule ignores the adult_num it is passed; count[0] carries its capacity, for sizing
+            n = CROWD_RULES[rule]
         g.count[t] = n
         if n:
             if rule not in _RULES or (rule == "circle_crossing" and t == _abi.CHILD) or (
-                    rule == "square_crossing_old" and t != _abi.BICYCLE):
+                    rule == "square_crossing_old" and t != _abi.BICYCLE) or (rule in CROWD_RULES and not crowd):
                 raise ValueError("unsupported crossing rule %r for type %d" % (rule, t))
             g.rule[t] = _RULES[rule]
         for key in ("radius", "v_pref", "radius_min", "radius_max", "v_pref_min", "v_pref_max"):
             v = getattr(spec, key)
-            if v is None and n and (cfg.randomize_attributes) == key.endswith(("_min", "_max")):
+            # standing adults keep the fixed attributes even under randomize_attributes
+            needed = (cfg.randomize_attributes) == key.endswith(("_min", "_max")) or (
+                crowd and not key.endswith(("_min", "_max")))
+            if v is None and n and needed:
                 raise ValueError("[%s] %s missing" % (("adults", "bicycles", "children")[t], key))
             getattr(g, key)[t] = 0.0 if v is None else float(v)
     g.square_width, g.circle_radius = cfg.square_width, cfg.circle_radius
@@ -292,7 +301,86 @@ class _Gen:
         h.px, h.py, h.gx, h.gy = px, py, gx, gy
         return h
 
+    def _standing(self, spec, px, py):
+        """An adult that is constructed and set down: no attribute draw, goal = position."""
+        h = self._new(spec, _abi.ADULT, False)
+        h.px, h.py, h.gx, h.gy = px, py, px, py
+        return h
+
+    def _clash(self, h, px, py, others):
+        """The position test of the standing adults; also returns the `agent` the reference's loop leaves behind."""
+        agent = None
+        for agent in others:
+            if _hyp(px - agent.px, py - agent.py) < h.radius + agent.radius + self.c.discomfort_dist:
+                return True, agent
+        return False, agent
+
+    def static_adults(self, n, width, height, spec, out):  # generate_static_adults, scene_generator.py:459-490
+        c = self.c
+        robot = self._robot_h()
+        for i in range(n):
+            if i == 0:
+                out.append(self._standing(spec, -0.5, -2.5))
+                continue
+            h = self._standing(spec, None, None)
+            sign = self.rs.choice([1, -1], p=[0.5, 0.5])
+            for _ in range(MAX_TRIES):
+                px = self.rs.random_sample() * width * 0.5 * sign
+                py = (self.rs.random_sample() - 0.5) * height
+                clash, agent = self._clash(h, px, py, [robot] + out)
+                # `agent` is the loop variable as it was left: where nothing clashed, the last adult placed
+                at_goal = _hyp(px - robot.gx, py - robot.gy) < h.radius + agent.radius + c.discomfort_dist
+                if not clash and not at_goal:
+                    break
+            h.px, h.py, h.gx, h.gy = px, py, px, py
+            out.append(h)
+
+    def dynamic_adults(self, n, on_circle, spec, out):  # generate_dynamic_adults, :492-501, and mixed, :570-576
+        for i in range(n):
+            if i < on_circle:
+                out.append(self.circle_crossing(spec, _abi.ADULT, out))
+            else:
+                out.append(self.square_crossing(spec, _abi.ADULT, out))
+
+    def crowd(self, count, rule, spec):
+        """generate_random_adult_position under mixed, mixed_20 and one_static (scene_generator.py:523-589)."""
+        out = []
+        if rule == "one_static":
+            out += [self._standing(spec, -2.0, -8.0), self._standing(spec, -3.0, -8.0)]
+        elif rule == "mixed_20":
+            standing = self.rs.randint(20)
+            self.static_adults(standing, 6, 8, spec, out)
+            self.dynamic_adults(20 - standing, (20 - standing) // 2, spec, out)
+        else:
+            tables = ({0: 0.05, 1: 0.2, 2: 0.2, 3: 0.3, 4: 0.1, 5: 0.15}, {1: 0.3, 2: 0.3, 3: 0.2, 4: 0.1, 5: 0.1})
+            static = bool(self.rs.random_sample() < 0.2)
+            prob = self.rs.random_sample()
+            for key, value in sorted(tables[0 if static else 1].items()):
+                if prob - value <= 0:
+                    count = key
+                    break
+                prob -= value
+            if not static:
+                self.dynamic_adults(count, 2, spec, out)
+                return out
+            if count == 0:
+                out.append(self._standing(spec, 0.0, -10.0))
+            robot = self._robot_h()
+            for _ in range(count):
+                h = self._standing(spec, None, None)
+                sign = -1 if self.rs.random_sample() > 0.5 else 1
+                for _ in range(MAX_TRIES):
+                    px = self.rs.random_sample() * 4 * 0.5 * sign
+                    py = (self.rs.random_sample() - 0.5) * 8
+                    if not self._clash(h, px, py, [robot] + out)[0]:
+                        break
+                h.px, h.py, h.gx, h.gy = px, py, px, py
+                out.append(h)
+        return out
+
     def group(self, count, rule, spec, kind):
+        if kind == _abi.ADULT and rule in CROWD_RULES:
+            return self.crowd(count, rule, spec)
         out = []
         for _ in range(count):
             if rule == "circle_crossing":

@@ -244,8 +244,18 @@ int ebc_set_scene_pool(void *handle, const EbcScene *pool, int stride);
 enum EbcCrossingRule {
   EBC_RULE_CIRCLE_CROSSING = 0,     /* scene_generator.py:593-648 (adults, bicycles) */
   EBC_RULE_SQUARE_CROSSING = 1,     /* :650-712 */
-  EBC_RULE_SQUARE_CROSSING_OLD = 2  /* :714-761 (bicycles only) */
+  EBC_RULE_SQUARE_CROSSING_OLD = 2, /* :714-761 (bicycles only) */
+  /* The crowd rules, adults only.  Each sets the number of adults itself and ignores the adult_num it is passed
+   * (count[0] is not read, but for the unreachable case noted in ebc_scene_gen.h); a scene takes at most 5, 20 and 2
+   * adult slots, and that capacity + count[1] + count[2] must fit max_humans. */
+  EBC_RULE_MIXED = 3,               /* :523-576: 0..5 standing adults in a 4 x 8 box (p = 0.2), or 1..5 walking */
+  EBC_RULE_MIXED_20 = 4,            /* :577-582, :459-501: 20 adults, randint(20) of them standing in a 6 x 8 box */
+  EBC_RULE_ONE_STATIC = 5           /* :583-589: two standing adults at (-2, -8) and (-3, -8) */
 };
+/* adult slots a scene of each crowd rule can take */
+#define EBC_CROWD_MIXED_ADULTS 5
+#define EBC_CROWD_MIXED_20_ADULTS 20
+#define EBC_CROWD_ONE_STATIC_ADULTS 2
 #define EBC_GEN_STATIC_OVERFLOW 1 /* a generated map has more observation rows than max_static */
 
 typedef struct EbcSceneGen {
@@ -279,7 +289,10 @@ typedef struct EbcSceneOut {
  * np.random.seed(seeds[i]) (seeds NULL: seed0 + i; env.reset seeds with counter_offset[phase] + case,
  * simulator/env.py:153-169) — numpy's legacy MT19937 stream, draw for draw, so every value is the reference's bit
  * for bit, except the cos / sin of circle_crossing (<= 1 ulp: numpy's own results there depend on the CPU).
- * Shapes follow the handle (max_humans, max_static, grid width); sum(count) must fit max_humans; a map with more
+ * The position is circle_radius * cos: with a circle_radius that is no power of two, a cos between a power of two and
+ * 4 / 3 of it lands in the next binade, and its 1 ulp is then up to 2 ulps of the position (rare: 3 of 1200 test scenes).
+ * Shapes follow the handle (max_humans, max_static, grid width); sum(count) must fit max_humans (under a crowd rule
+ * the rule's capacity takes the place of count[0], and n_humans then varies from scene to scene); a map with more
  * observation rows than max_static is EBC_ERR_INVALID.
  *   ebc_generate_scenes: copy the batch out (tests, inspection).
  *   ebc_generate_reset:  env.reset of envs first..first+n-1 from it, nothing crossing PCIe but the seeds.
