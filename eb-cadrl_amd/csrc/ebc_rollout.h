@@ -8,6 +8,8 @@
 //
 //   P1   (pre-step state)
 //        all threads   state_rotated[k] rows -> LDS row buffer (they leave as 16-byte stores after the barrier)
+//        all threads   ebc_step_k_world only (rollout_kernel<GS, SAIL, MIXED, true>): the robot array and the world-frame
+//                      rows of the workgroup's envs, from LDS straight to the caller's [k] slices (world_store)
 //        all waves     EBC_ROBOT_SAIL only (rollout_kernel<GS, true>): the attached network decides for the envs of the
 //                      workgroup, a chunk of envs at a time through one LDS area (sail_group, ebc_sail.h), from the
 //                      LDS state; the action goes to act[] and a barrier ends it
@@ -171,14 +173,48 @@ struct RolloutIOSail : RolloutIO {
 template <bool SAIL>
 using RolloutArg = typename std::conditional<SAIL, RolloutIOSail, RolloutIO>::type;
 
+// ebc_step_k_world: the records of the world before every step, [K][E][9] and [K][E][R][5] doubles; either may be null
+struct RolloutWorld {
+  double *robot, *ob;
+};
+template <bool SAIL>
+struct RolloutIOWorld : RolloutArg<SAIL> {
+  RolloutWorld world;
+};
+template <bool SAIL, bool WORLD>
+using RolloutArgW = typename std::conditional<WORLD, RolloutIOWorld<SAIL>, RolloutArg<SAIL>>::type;
+
+// `cnt` doubles, value(f) for f in [0, cnt), -> dst in flat order, by THREADS threads: 16-byte stores from the first
+// 16-byte boundary of the destination on, a single double before and behind (flush_rows' shape, for doubles that are
+// computed from the LDS state instead of lying in a buffer).
+template <int THREADS, typename F>
+__device__ __forceinline__ void world_store(double *dst, int cnt, int tid, F value) {
+  int head = (int)(((size_t)dst >> 3) & 1);
+  head = head < cnt ? head : cnt;
+  if (tid < head) dst[tid] = value(tid);
+  const int body2 = (cnt - head) / 2;
+  typedef double f64x2 __attribute__((ext_vector_type(2)));
+  for (int v = tid; v < body2; v += THREADS) {
+    const int f = head + 2 * v;
+    const f64x2 w = {value(f), value(f + 1)};
+    *reinterpret_cast<f64x2 *>(dst + f) = w;
+  }
+  const int tail0 = head + 2 * body2;
+  if (tid < cnt - tail0) dst[tail0 + tid] = value(tail0 + tid);
+}
+
 // SAIL = false is the kernel of the three robot policies as it was measured; SAIL = true (EBC_ROBOT_SAIL) is an
 // instantiation of its own, so that theirs keeps its register allocation: it adds the network's decision in P1 and
 // nothing anywhere else.
 // MIXED = true is EBC_HUMAN_BY_TYPE's instantiation (csrc/ebcsim_mix.hip), again one of its own: the group of a human on
 // the linear policy idles through the ORCA pass, and the human's commit in P3a takes linear_policy of the pre-step state,
 // which is still in LDS there, in place of vel[].  Nothing else differs.
-template <int GS, bool SAIL = false, bool MIXED = false>
-__global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutArg<SAIL> io) {
+// WORLD = true is ebc_step_k_world's (csrc/ebcsim_world.hip), one more of its own for the same reason: at the top of P1
+// all threads write the robot array and the world-frame rows of the workgroup's envs from LDS, the values the SAIL
+// source struct reads there.  A workgroup's envs are consecutive, so each record of a step is one contiguous run of
+// envs * 9 and envs * R * 5 doubles.  No LDS of its own.
+template <int GS, bool SAIL = false, bool MIXED = false, bool WORLD = false>
+__global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(EbcParams p, DevState s, RolloutArgW<SAIL, WORLD> io) {
   extern __shared__ __align__(16) unsigned char ro_lds[];
   const int tid = threadIdx.x, lane = tid & (EBC_WAVE - 1), wave = tid / EBC_WAVE;
   const int N = s.N, S = s.S, R = N + S, EPG = io.epg, T = io.T, E = s.E;
@@ -267,6 +303,15 @@ __global__ __launch_bounds__(EBC_RO_THREADS, EBC_RO_OCC) void rollout_kernel(Ebc
     const size_t ke = (size_t)k * E + e0;  // first env of this workgroup in a [K][E] output
     // ================================================================ P1
     if (k > 0 && io.obs_rotated) flush_rows<EBC_RO_THREADS>(rows_obs, io.obs_rotated + (ke - E) * R * T, RN * T, tid);
+    if constexpr (WORLD) {  // ebc_get_state's robot and ebc_observe's ob of the state before step k
+      if (io.world.robot) world_store<EBC_RO_THREADS>(io.world.robot + ke * 9, envs * 9, tid, [&](int f) { return robot[f]; });
+      if (io.world.ob)
+        world_store<EBC_RO_THREADS>(io.world.ob + ke * R * 5, RN * 5, tid, [&](int f) {
+          const int el = f / (R * 5), rem = f - el * (R * 5), r = rem / 5, c = rem - r * 5;
+          const ObsRow o = obs_row(lds_rows.at(el * N, el * S), r, n_h[el], n_s[el]);
+          return c == 0 ? o.px : c == 1 ? o.py : c == 2 ? o.vx : c == 3 ? o.vy : o.radius;
+        });
+    }
     if (io.state_rotated) {  // rows of the current state in the robot's frame
       for (int q = tid; q < RN; q += EBC_RO_THREADS) {
         const int el = q / R, r = q - el * R;

@@ -20,6 +20,7 @@
 #include "ebc_om_state.h"
 #include "ebc_rollout.h"
 #include "ebc_sail_api.h"
+#include "ebc_world_api.h"
 
 namespace {
 
@@ -994,8 +995,25 @@ int launch_observe_wide(Handle *h, const EbcOmSpec &spec, float *d_wide, long lo
 // EBC_ROBOT_SAIL: the network's LDS area for `chunk` envs, in bytes
 unsigned sail_area(const Handle *h, int chunk) { return (unsigned)(ebc::sail_lds_floats(chunk, h->sail_N) * sizeof(float)); }
 
+// ebc_step_k_world: the instantiation that also writes the records (ebcsim_world.hip), with `arg` = the default
+// instantiation's argument and the record pointers behind it
+template <typename Arg>
+int launch_rollout_world(Handle *h, int gs, bool sail, bool mixed, const Arg &arg, const ebc::RolloutWorld &world, unsigned blocks,
+                         unsigned lds) {
+  ebc::RolloutIOWorld<std::is_same<Arg, ebc::RolloutIOSail>::value> iow;
+  static_cast<Arg &>(iow) = arg;
+  iow.world = world;
+  const void *kernel = nullptr;
+  int rc = ebc_world_api::rollout_kernel(gs, sail, mixed, &kernel);
+  if (rc != EBC_OK) return rc;
+  void *args[] = {&h->p, &h->s, &iow};
+  HIP_TRY(hipLaunchKernel(kernel, dim3(blocks), dim3(EBC_RO_THREADS), args, lds, h->stream));
+  return EBC_OK;
+}
+
+// world: the records of ebc_step_k_world, or nullptr (ebc_step_k)
 template <int GS>
-int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed) {
+int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed, const ebc::RolloutWorld *world) {
   const int N = h->s.N, S = h->s.S, E = h->s.E;
   constexpr unsigned scratch = ebc::RolloutScratch<GS>::BYTES;
   const bool sail = io.robot_policy == EBC_ROBOT_SAIL;
@@ -1035,6 +1053,7 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed)
     static_cast<ebc::RolloutIO &>(ios) = io;
     ios.epg = epg;
     ios.sail = ebc::RolloutSail{h->sail_P, h->sail_N, chunk};
+    if (world) return launch_rollout_world(h, GS, true, mixed, ios, *world, (unsigned)((E + epg - 1) / epg), bytes(epg, chunk));
     if (mixed) {
       const void *kernel = nullptr;
       int rc = ebc_mix_api::rollout_kernel(GS, true, &kernel);
@@ -1055,6 +1074,7 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed)
   if (lds > 48u * 1024u) return fail(EBC_ERR_UNSUPPORTED, "EBC_FLAG_ONE_LAUNCH: one env needs more than 48 KB of LDS");
   io.epg = epg;
   const unsigned blocks = (unsigned)((E + epg - 1) / epg);
+  if (world) return launch_rollout_world(h, GS, false, mixed, io, *world, blocks, lds);
   if (mixed) {
     const void *kernel = nullptr;
     int rc = ebc_mix_api::rollout_kernel(GS, false, &kernel);
@@ -1069,9 +1089,9 @@ int launch_rollout_gs(Handle *h, ebc::RolloutIO io, bool robot_orca, bool mixed)
 }
 
 // mixed: EBC_HUMAN_BY_TYPE (the instantiations of ebcsim_mix.hip)
-int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca, bool mixed) {
-  return with_group_size<kDevHumanGs>(h->orca_gs,
-                                      [&](auto gs) { return launch_rollout_gs<decltype(gs)::value>(h, io, robot_orca, mixed); });
+int launch_rollout(Handle *h, const ebc::RolloutIO &io, bool robot_orca, bool mixed, const ebc::RolloutWorld *world) {
+  return with_group_size<kDevHumanGs>(
+      h->orca_gs, [&](auto gs) { return launch_rollout_gs<decltype(gs)::value>(h, io, robot_orca, mixed, world); });
 }
 
 }  // namespace
@@ -1190,8 +1210,9 @@ static int refuse_capture(Handle *h, const char *what) {
   return EBC_OK;
 }
 
-// ebc_step_k, and with `om` (ebc_step_k_om) the wide state of every state the policy sees, enqueued before step k
-static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om, const char *what) {
+// ebc_step_k; with `om` (ebc_step_k_om) the wide state of every state the policy sees, enqueued before step k; with
+// `world` (ebc_step_k_world) the robot's FullState and the world-frame rows before step k
+static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om, const EbcStepKWorld *world, const char *what) {
   Handle *h;
   int rc = check_handle(handle, &h);
   if (rc) return rc;
@@ -1233,16 +1254,19 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
   long long *d_rows = a->n_rows;
   double *d_act_out = a->robot_action_out, *d_reward = a->reward, *d_dmin = a->dmin, *d_goal = a->dist_to_goal;
   uint8_t *d_done = a->done, *d_info = a->info;
+  double *d_wrobot = world ? world->robot : nullptr, *d_wob = world ? world->ob : nullptr;
   Stager st{h};
   if (a->location != EBC_DEVICE) {
     const size_t need = K * (pad256(E * 2 * 8) * 2 + pad256(E * 8) * 3 + pad256(E) * 2 + pad256(E * 3 * 8) +
-                             pad256(E * R * T * 4) * 2) + pad256(E * 2 * 8) + 8192;
+                             pad256(E * R * T * 4) * 2) + pad256(E * 2 * 8) + 8192 +
+                        (world ? pad256(K * E * 9 * 8) + pad256(K * E * R * 5 * 8) : 0);
     if ((rc = ensure_stage(h, need)) != EBC_OK) return rc;
     if ((rc = st.in(a->robot_policy == EBC_ROBOT_EXTERNAL ? a->robot_action : nullptr, K * E * 2, &d_act_in)) != EBC_OK) return rc;
     d_state = st.out(a->state_rotated, K * E * R * T); d_rows = st.out(a->n_rows, K * E);
     d_act_out = st.out(a->robot_action_out, K * E * 2); d_reward = st.out(a->reward, K * E);
     d_done = st.out(a->done, K * E); d_info = st.out(a->info, K * E); d_dmin = st.out(a->dmin, K * E * 3);
     d_goal = st.out(a->dist_to_goal, K * E); d_obs = st.out(a->obs_rotated, K * E * R * T);
+    d_wrobot = st.out(d_wrobot, K * E * 9); d_wob = st.out(d_wob, K * E * R * 5);
   }
   if (one_launch) {
     ebc::RolloutIO io;
@@ -1256,7 +1280,10 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
     io.robot_action = a->robot_policy == EBC_ROBOT_EXTERNAL ? d_act_in : nullptr;
     io.state_rotated = d_state; io.n_rows = d_rows; io.robot_action_out = d_act_out; io.reward = d_reward;
     io.done = d_done; io.info = d_info; io.dmin = d_dmin; io.dist_to_goal = d_goal; io.obs_rotated = d_obs;
-    if ((rc = launch_rollout(h, io, a->robot_policy == EBC_ROBOT_ORCA, a->human_policy == EBC_HUMAN_BY_TYPE)) != EBC_OK) return rc;
+    const ebc::RolloutWorld records = {d_wrobot, d_wob};
+    if ((rc = launch_rollout(h, io, a->robot_policy == EBC_ROBOT_ORCA, a->human_policy == EBC_HUMAN_BY_TYPE, world ? &records : nullptr)) !=
+        EBC_OK)
+      return rc;
     if (a->location != EBC_DEVICE) return st.finish();
     return EBC_OK;
   }
@@ -1283,7 +1310,11 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
   }
   for (size_t k = 0; k < K; ++k) {
     if (om && (rc = launch_observe_wide(h, om->spec, om->state_wide + k * E * R * (T + om_width(om->spec)), nullptr)) != EBC_OK) return rc;
-    if (d_state && (rc = launch_observe(h, nullptr, d_state + k * E * R * T)) != EBC_OK) return rc;
+    if (d_wrobot) HIP_TRY(hipMemcpyAsync(d_wrobot + k * E * 9, h->s.robot, E * 9 * 8, hipMemcpyDeviceToDevice, h->stream));
+    // one launch of observe_kernel for the rotated state and the world-frame rows, whichever are asked for
+    if ((d_state || d_wob) &&
+        (rc = launch_observe(h, d_wob ? d_wob + k * E * R * 5 : nullptr, d_state ? d_state + k * E * R * T : nullptr)) != EBC_OK)
+      return rc;
     if (d_rows) {
       hipLaunchKernelGGL(ebc::row_counts_kernel, dim3((unsigned)((E + 255) / 256)), dim3(256), 0, h->stream, h->s, d_rows + k * E);
       HIP_TRY(hipGetLastError());
@@ -1323,13 +1354,21 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
   return EBC_OK;
 }
 
-int ebc_step_k(void *handle, const EbcStepKArgs *a) { return step_k_impl(handle, a, nullptr, "ebc_step_k"); }
+int ebc_step_k(void *handle, const EbcStepKArgs *a) { return step_k_impl(handle, a, nullptr, nullptr, "ebc_step_k"); }
 
 int ebc_step_k_om(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om) {
   if (!om) return fail(EBC_ERR_INVALID, "ebc_step_k_om: om is NULL");
   if (om->struct_size != sizeof(EbcStepKOm)) return fail(EBC_ERR_INVALID, "EbcStepKOm.struct_size");
   if (om->spec.struct_size != sizeof(EbcOmSpec)) return fail(EBC_ERR_INVALID, "EbcOmSpec.struct_size");
-  return step_k_impl(handle, a, om, "ebc_step_k_om");
+  return step_k_impl(handle, a, om, nullptr, "ebc_step_k_om");
+}
+
+int ebc_step_k_world(void *handle, const EbcStepKArgs *a, const EbcStepKWorld *world) {
+  if (!world) return fail(EBC_ERR_INVALID, "ebc_step_k_world: world is NULL");
+  if (world->struct_size != sizeof(EbcStepKWorld)) return fail(EBC_ERR_INVALID, "EbcStepKWorld.struct_size");
+  if (world->reserved != 0) return fail(EBC_ERR_INVALID, "EbcStepKWorld.reserved");
+  if (!world->robot && !world->ob) return fail(EBC_ERR_INVALID, "ebc_step_k_world: robot and ob are both NULL");
+  return step_k_impl(handle, a, nullptr, world, "ebc_step_k_world");
 }
 
 // K closed-loop steps of the attached SAIL network with the ORCA robot labelling every state (csrc/ebc_dagger.h): per

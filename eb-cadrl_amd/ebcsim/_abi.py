@@ -225,6 +225,12 @@ class EbcStepKOm(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("spec", EbcOmSpec), ("state_wide", C.c_void_p)]
 
 
+class EbcStepKWorld(C.Structure):
+    """include/ebcsim.h: what ebc_step_k_world adds to ebc_step_k: the robot's FullState [K][E][9] and the world-frame rows
+    [K][E][R][5] before every step, float64 where EbcStepKArgs.location says; either may be NULL, not both."""
+    _fields_ = [("struct_size", C.c_uint32), ("reserved", C.c_int32), ("robot", C.c_void_p), ("ob", C.c_void_p)]
+
+
 def om_spec(spec):
     """An occupancy.OccupancySpec (cell_num, cell_size, channels) as the struct."""
     s = EbcOmSpec()

@@ -81,6 +81,7 @@ SYMBOLS = {
     "ebc_observe_wide": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_observe_wide_sorted": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_step_k_om": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ebc_step_k_world": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_create": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "ebc_sail_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "ebc_sail_destroy": (C.c_int, [C.c_void_p]),

@@ -484,7 +484,21 @@ class BatchedEnv:
     _STEP_K_SHAPES = staticmethod(lambda E, R, T: dict(
         state_rotated=((E, R, T), "float32"), n_rows=((E,), "int64"), robot_action_out=((E, 2), "float64"),
         reward=((E,), "float64"), done=((E,), "uint8"), info=((E,), "uint8"), dmin=((E, 3), "float64"),
-        dist_to_goal=((E,), "float64"), obs_rotated=((E, R, T), "float32")))
+        dist_to_goal=((E,), "float64"), obs_rotated=((E, R, T), "float32"),
+        world_robot=((E, 9), "float64"), world_ob=((E, R, 5), "float64")))
+    # the outputs of EbcStepKWorld (ebc_step_k_world), by their key here and their field there
+    _WORLD_KEYS = {"world_robot": "robot", "world_ob": "ob"}
+
+    def _step_k_call(self, args, ptr):
+        """ebc_step_k, or ebc_step_k_world when `ptr` (key -> address) holds a world output"""
+        if not any(k in ptr for k in self._WORLD_KEYS):
+            _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
+            return
+        w = _abi.EbcStepKWorld()
+        w.struct_size = C.sizeof(w)
+        for k, field in self._WORLD_KEYS.items():
+            setattr(w, field, ptr.get(k))
+        _capi.check(self._L.ebc_step_k_world(self._h, C.addressof(args), C.addressof(w)))
 
     def _step_k_args(self, K, location, ptr, human_policy, robot_policy, flags, robot_safety_space, robot_action_ptr):
         args = _abi.EbcStepKArgs()
@@ -494,27 +508,32 @@ class BatchedEnv:
         args.robot_safety_space = float(robot_safety_space)
         args.robot_action = robot_action_ptr
         for k, v in ptr.items():
-            setattr(args, k, v)
+            if k not in self._WORLD_KEYS:
+                setattr(args, k, v)
         return args
 
     def step_k(self, K, keys=("reward", "done", "info", "state_rotated"), robot_action=None,
                human_policy=_abi.HUMAN_ORCA, robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0):
         """K steps in one call (ebc_step_k), host buffers: returns {key: array [K, ...]}.  flags may carry
         _abi.FLAG_ONE_LAUNCH: the K steps as one kernel launch, same results bit for bit (ORCA humans only).
-        robot_policy=_abi.ROBOT_SAIL: the network attached with attach_sail decides every step."""
+        robot_policy=_abi.ROBOT_SAIL: the network attached with attach_sail decides every step.  The keys "world_robot"
+        [K, E, 9] and "world_ob" [K, E, R, 5] are the robot's FullState and the world-frame rows before every step
+        (ebc_step_k_world)."""
         shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
         out = {k: np.zeros((K,) + shapes[k][0], dtype=shapes[k][1]) for k in keys}
         ra = None
         if robot_action is not None:
             ra = np.ascontiguousarray(robot_action, dtype=np.float64).reshape(K, self.E, 2)
-        args = self._step_k_args(K, _abi.HOST, {k: v.ctypes.data for k, v in out.items()}, human_policy, robot_policy,
-                                 flags, robot_safety_space, None if ra is None else ra.ctypes.data)
-        _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
+        ptr = {k: v.ctypes.data for k, v in out.items()}
+        args = self._step_k_args(K, _abi.HOST, ptr, human_policy, robot_policy, flags, robot_safety_space,
+                                 None if ra is None else ra.ctypes.data)
+        self._step_k_call(args, ptr)
         return out
 
     def alloc_step_k_outputs(self, K, keys=("reward", "done", "info", "state_rotated"), om=None):
         """torch CUDA tensors [K, ...] for step_k_device(); the caller owns them.  The key "state_wide" (with om, an
-        occupancy.OccupancySpec) is [K, E, R, T + om.width] float32."""
+        occupancy.OccupancySpec) is [K, E, R, T + om.width] float32; "world_robot" [K, E, 9] and "world_ob" [K, E, R, 5]
+        are float64 (ebc_step_k_world)."""
         import torch
         dev = torch.device("cuda", self.device)
         shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
@@ -528,20 +547,27 @@ class BatchedEnv:
                       robot_policy=_abi.ROBOT_LINEAR, flags=0, robot_safety_space=0.0, om=None):
         """Enqueue K steps (ebc_step_k) writing into torch CUDA tensors [K, ...] (not copied); flags as step_k.  om (an
         occupancy.OccupancySpec) with the output "state_wide" [K, E, R, T + om.width]: ebc_step_k_om, which also writes the
-        wide state of the state the policy sees before every step (per-step form only)."""
+        wide state of the state the policy sees before every step (per-step form only).  The outputs "world_robot" and
+        "world_ob" make it ebc_step_k_world, in either form; not together with om (the C entries take one side struct)."""
         if (om is None) != ("state_wide" not in outputs):
             raise ValueError("om and the output state_wide go together")
+        if om is not None and any(k in outputs for k in self._WORLD_KEYS):
+            raise ValueError("world_robot / world_ob (ebc_step_k_world) and om (ebc_step_k_om) do not go together")
+        shapes = self._STEP_K_SHAPES(self.E, self.R, self.T)
+        for k in self._WORLD_KEYS:
+            if k in outputs and (tuple(outputs[k].shape[1:]) != shapes[k][0] or outputs[k].dtype.itemsize != 8):
+                raise ValueError("%s must be a float64 [K, %s] tensor" % (k, ", ".join(map(str, shapes[k][0]))))
         for k, t in outputs.items():
             if t.shape[0] != K or not t.is_contiguous():
                 raise ValueError("%s must be a contiguous [K, ...] tensor" % k)
         if robot_action is not None and (robot_action.dtype.itemsize != 8 or robot_action.numel() != K * self.E * 2
                                          or not robot_action.is_contiguous()):
             raise ValueError("robot_action must be a contiguous float64 [K, E, 2] tensor")
-        args = self._step_k_args(K, _abi.DEVICE, {k: t.data_ptr() for k, t in outputs.items() if k != "state_wide"}, human_policy,
-                                 robot_policy, flags, robot_safety_space,
+        ptr = {k: t.data_ptr() for k, t in outputs.items() if k != "state_wide"}
+        args = self._step_k_args(K, _abi.DEVICE, ptr, human_policy, robot_policy, flags, robot_safety_space,
                                  None if robot_action is None else robot_action.data_ptr())
         if om is None:
-            _capi.check(self._L.ebc_step_k(self._h, C.addressof(args)))
+            self._step_k_call(args, ptr)
             return
         wide = outputs["state_wide"]
         if wide.dtype.itemsize != 4 or wide.numel() != K * self.E * self.R * (self.T + om.width):

@@ -228,7 +228,8 @@ class DeviceSailPolicy(object):
         """K closed-loop steps in ONE call: attaches the net to `env` (BatchedEnv.attach_sail) and enqueues
         step_k_device(robot_policy=ROBOT_SAIL) writing into `outputs` (torch CUDA tensors [K, ...], e.g.
         env.alloc_step_k_outputs).  Step for step what decide() followed by step_device computes, without the host in
-        the loop; flags may carry FLAG_AUTO_RESET and FLAG_ONE_LAUNCH (the network inside the rollout kernel)."""
+        the loop; flags may carry FLAG_AUTO_RESET and FLAG_ONE_LAUNCH (the network inside the rollout kernel).  The keys
+        "world_robot" and "world_ob" in `outputs` go through as they are: the world before every step (ebc_step_k_world)."""
         if env.R < self.net.adult_num:
             raise ValueError("DeviceSailPolicy: the env has %d rows, the network takes exactly adult_num = %d" % (env.R, self.net.adult_num))
         env.attach_sail(self.net)

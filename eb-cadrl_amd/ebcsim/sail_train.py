@@ -207,11 +207,16 @@ class SailTrainer(object):
         self.push_weights()
 
 
-def collect_sail_demos(env, steps, safety_space=0.15, persistent_sim=True, human_policy=_abi.HUMAN_ORCA):
+def collect_sail_demos(env, steps, safety_space=0.15, persistent_sim=True, human_policy=_abi.HUMAN_ORCA, steps_per_call=None,
+                       one_launch=False):
     """`steps` steps of every env of a BatchedEnv (on a HIP device, auto-reset) with the robot on ORCA, the demonstrator
     of rl/train.py:124-133 as train.collect_il runs it: per step the robot's FullState, the world-frame observation rows
     and the row counts go into [K, E, ...] buffers, ebc_robot_orca gives the action (the regression target, (vx, vy)),
     and the step takes it.  Kept: the steps of episodes that ended inside the window in ReachGoal.
+    steps_per_call (an int K): the same window as ebc_step_k_world calls of at most K steps with EBC_ROBOT_ORCA, which
+    write the same six buffers (world_robot, world_ob, n_rows, robot_action_out, done, info) without the host between
+    the steps; one_launch: each call as one kernel launch (EBC_FLAG_ONE_LAUNCH; ORCA and by-type humans).  The dictionary is
+    the loop's byte for byte.  None is the loop, five calls per step.
     -> dict(robot [M, 9], ob [M, R, 5], n_rows [M], target [M, 2], steps, episodes) on the device."""
     if int(env.params.robot_kinematics) != _abi.HOLONOMIC:
         raise NotImplementedError("collect_sail_demos: holonomic robots only: the demonstrator's action is (vx, vy), which SAIL "
@@ -226,7 +231,17 @@ def collect_sail_demos(env, steps, safety_space=0.15, persistent_sim=True, human
     done = torch.empty((K, E), dtype=torch.uint8, device=dev)
     info = torch.empty((K, E), dtype=torch.uint8, device=dev)
     reward = torch.empty((E,), dtype=torch.float64, device=dev)
-    for k in range(K):
+    if one_launch and steps_per_call is None:
+        raise ValueError("collect_sail_demos: one_launch needs steps_per_call, the steps of a call")
+    if steps_per_call is not None and int(steps_per_call) < 1:
+        raise ValueError("collect_sail_demos: steps_per_call must be at least 1")
+    flags = _abi.FLAG_AUTO_RESET | (_abi.FLAG_ONE_LAUNCH if one_launch else 0)
+    for k0 in range(0, K if steps_per_call is not None else 0, int(steps_per_call or 1)):
+        k1 = min(K, k0 + int(steps_per_call))
+        env.step_k_device(dict(world_robot=robot[k0:k1], world_ob=ob[k0:k1], n_rows=n_rows[k0:k1], robot_action_out=target[k0:k1],
+                               done=done[k0:k1], info=info[k0:k1]), k1 - k0, human_policy=human_policy,
+                          robot_policy=_abi.ROBOT_ORCA, flags=flags, robot_safety_space=safety_space)
+    for k in range(K if steps_per_call is None else 0):
         env.robot_state_device(robot[k])
         env.observe_ob_device(ob[k])
         env.row_counts_device(n_rows[k])
@@ -268,9 +283,11 @@ def fit(trainer, demos, epochs, batch_size, generator=None):
     return losses
 
 
-def train_sail(env, trainer, demo_steps, epochs, batch_size, generator=None, safety_space=0.15, persistent_sim=True):
+def train_sail(env, trainer, demo_steps, epochs, batch_size, generator=None, safety_space=0.15, persistent_sim=True,
+               steps_per_call=None, one_launch=False):
     """Demonstrations from `env`, then the fit -> the per-epoch mean losses."""
-    return fit(trainer, collect_sail_demos(env, demo_steps, safety_space, persistent_sim), epochs, batch_size, generator)
+    demos = collect_sail_demos(env, demo_steps, safety_space, persistent_sim, steps_per_call=steps_per_call, one_launch=one_launch)
+    return fit(trainer, demos, epochs, batch_size, generator)
 
 
 # ---------------------------------------------------------------------- DAgger (Ross, Gordon and Bagnell 2011)
@@ -360,14 +377,16 @@ class DaggerDataset(object):
 
 
 def dagger(env, trainer, rounds, demo_steps, dagger_steps, epochs, dagger_epochs, batch_size, beta0=0.5, beta_decay=0.5,
-           capacity=1 << 20, generator=None, safety_space=0.15, on_round=None, persistent_sim=True):
+           capacity=1 << 20, generator=None, safety_space=0.15, on_round=None, persistent_sim=True, demo_steps_per_call=None,
+           demo_one_launch=False):
     """Round 0: collect_sail_demos + fit, exactly train_sail.  Round i >= 1: collect_dagger at beta0 * beta_decay^(i - 1)
     on `env` (the env trainer.net is attached to: SailTrainer.step has already handed it the new weights), append to the
     aggregate, fit on all of it for dagger_epochs.  on_round(i, info) runs after every round's fit; info holds round,
     beta, losses, samples (this round's), aggregate, episodes and, from round 1 on, the window's outcome counts.
     -> (per-round list of the per-epoch losses, the DaggerDataset).  rounds = 0 is train_sail."""
     data = DaggerDataset(capacity)
-    demos = collect_sail_demos(env, demo_steps, safety_space, persistent_sim)
+    demos = collect_sail_demos(env, demo_steps, safety_space, persistent_sim, steps_per_call=demo_steps_per_call,
+                               one_launch=demo_one_launch)  # round 0 in windows of ebc_step_k_world, when asked for
     if int(rounds) > 0:
         data.append(demos)
     losses = [fit(trainer, demos, epochs, batch_size, generator)]

@@ -638,23 +638,30 @@ class _EpisodeTally(object):
         }
 
 
-def evaluate(env, decide, gamma, max_steps=None, human_policy=_abi.HUMAN_ORCA):
+def evaluate(env, decide, gamma, max_steps=None, human_policy=_abi.HUMAN_ORCA, record=None):
     """Explorer.run_k_episodes on the `val` / `test` cases (explorer.py:33-131, :202-330), batched: one
     episode per env of a freshly reset BatchedEnv (no auto-reset; an env that has ended is ignored from
     then on).  decide(env) -> robot actions, float64 CUDA tensor [E, 2] (e.g. `lambda e:
     policy.decide(e)[0]` with human_policy=EBC_HUMAN_CACHED: the decision's sweep has already worked out
     the humans' velocities).  Returns the reference's compile_metrics() dictionary (same keys; the case
-    lists hold env indices) plus "num_episodes"."""
+    lists hold env indices) plus "num_episodes".  record (a record.EpisodeRecorder): the robot's state, the world-frame
+    rows and the row counts before every step go into its buffers."""
     tally = _EpisodeTally(env, gamma)
     steps = int(max_steps or round(tally.limit / tally.dt) + 2)
     outs = env.alloc_step_outputs(("reward", "done", "info", "dmin"))
     for t in range(steps):
+        if record is not None:
+            record.before_step(t)
         actions = decide(env)
         env.step_device(outs, robot_action=actions.contiguous(), human_policy=human_policy)
+        if record is not None:
+            record.after_steps(t, outs["done"], outs["info"])
         tally.step(t, outs["reward"], outs["done"], outs["info"], outs["dmin"])
         if t % 8 == 7 and not bool(tally.alive.any()):
             break
     env.synchronize()  # before the metrics: a broken step must not be counted
+    if record is not None:
+        record.finish(tally)
     return tally.metrics()
 
 
@@ -662,7 +669,9 @@ def evaluate_windows(env, rollout, gamma, steps_per_call, max_steps=None):
     """evaluate() for a policy that lives on the device, in windows of `steps_per_call` steps per call:
     rollout(env, K, outputs) enqueues K closed-loop steps writing reward, done, info and dmin [K, ...] (e.g.
     sail.DeviceSailPolicy.rollout).  The same first-terminal masking step by step, so the same metrics as evaluate()
-    with the per-step loop of the same policy; steps of a window past the end of every episode count for nothing."""
+    with the per-step loop of the same policy; steps of a window past the end of every episode count for nothing.
+    To record the world of every step, pass a recorder's view of the rollout: record.EpisodeRecorder.recording(rollout)
+    asks every window for world_robot, world_ob and n_rows too (ebc_step_k_world), written straight into its buffers."""
     tally = _EpisodeTally(env, gamma)
     steps = int(max_steps or round(tally.limit / tally.dt) + 2)
     K = int(steps_per_call)

@@ -761,6 +761,26 @@ typedef struct EbcStepKOm {
 } EbcStepKOm;
 int ebc_step_k_om(void *handle, const EbcStepKArgs *args, const EbcStepKOm *om);
 
+/* ebc_step_k(handle, args) in either form — every output of `args` and the state left behind are its bytes — and
+ * before step k also the world itself, what the reference keeps per step in env.states (simulator/env.py:344-351):
+ * the robot's FullState and the world-frame observation rows.  Index k is the state BEFORE step k, the convention of
+ * state_rotated[k] and n_rows[k]: robot[k] holds the bytes ebc_get_state's `robot` would give there and ob[k] those of
+ * ebc_observe's `ob` (rows past an env's own are zeros); after a terminal step under EBC_FLAG_AUTO_RESET index k + 1
+ * shows the restart scene.  The pointers live where args->location says; at least one is non-NULL.
+ *   - Per-step form: one copy of the robot array per step, and ebc_observe's kernel writing `ob` (in the launch that
+ *     writes state_rotated[k] where that is asked for too).
+ *   - EBC_FLAG_ONE_LAUNCH: the workgroup writes its envs' records from the LDS-resident state at the top of every step
+ *     (instantiations of their own, csrc/ebcsim_world.hip; the kernels of plain ebc_step_k are not touched).
+ *   - Every refusal of ebc_step_k holds; a wrong struct_size, a non-zero `reserved` or two NULL pointers are
+ *     EBC_ERR_INVALID. */
+typedef struct EbcStepKWorld {
+  uint32_t struct_size;
+  int32_t reserved;   /* 0 */
+  double *robot;      /* [K][E][9]    the robot's FullState BEFORE step k (ebc_get_state's `robot`), or NULL */
+  double *ob;         /* [K][E][R][5] world-frame rows BEFORE step k (ebc_observe's `ob`), or NULL */
+} EbcStepKWorld;
+int ebc_step_k_world(void *handle, const EbcStepKArgs *args, const EbcStepKWorld *world);
+
 /* ---- the SAIL policy (rl/policy/sail.py): one small network from the robot's state and the world-frame states of
  * exactly adult_num others straight to a continuous action, no look-ahead and no action space; one kernel per batch of
  * decisions.  The arithmetic is csrc/ebc_sail_rule.h (one definition for the kernel and for the host build

@@ -32,6 +32,10 @@ reference's metrics at the end.
                                          (the same episodes in windows of 32 steps per ebc_step_k call with the network
                                           as the robot policy on the device, EBC_ROBOT_SAIL: same metrics, no host
                                           work per step; --one-launch: each window as one kernel launch)
+    python3 tools/evaluate.py ... --record episodes.npz
+                                         (any policy, either loop: the robot's state and the world-frame rows before every
+                                          step of every case, cut at its terminal step, with length, final, the humans'
+                                          types and the case indices: what a trajectory plot of a listed case needs)
 """
 import argparse
 import configparser
@@ -61,6 +65,8 @@ def main():
     ap.add_argument("--steps-per-call", type=int, default=0, metavar="K",
                     help="--policy sail: advance in windows of K steps per ebc_step_k call (default 0: the per-step loop)")
     ap.add_argument("--one-launch", action="store_true", help="with --steps-per-call: each window as one kernel launch")
+    ap.add_argument("--record", default=None, metavar="PATH",
+                    help="save every case's world-frame trajectory (ebcsim.record.EpisodeRecorder) as one .npz")
     ap.add_argument("--wide-decide", action="store_true",
                     help="--policy sarl: stacks wider than the two-layer block (up to 640 units: policy_x3 / policy_x4) as wide blocks instead of torch")
     args = ap.parse_args()
@@ -140,15 +146,22 @@ def main():
         hp = _abi.HUMAN_ORCA
     torch.cuda.synchronize()
     t2 = time.perf_counter()
+    rec = None
+    if args.record:
+        from ebcsim.record import EpisodeRecorder
+        rec = EpisodeRecorder(env, int(round(params.time_limit / params.time_step)) + 2)  # the steps evaluate() takes at most
+        rec.case += args.first_case
     if args.steps_per_call > 0:
         from ebcsim.train import evaluate_windows
         flags = _abi.FLAG_ONE_LAUNCH if args.one_launch else 0
-        m = evaluate_windows(env, lambda e, K, outs: policy.rollout(e, K, outs, flags=flags, human_policy=hp), args.gamma,
-                             args.steps_per_call)
+        rollout = lambda e, K, outs: policy.rollout(e, K, outs, flags=flags, human_policy=hp)  # noqa: E731
+        m = evaluate_windows(env, rec.recording(rollout) if rec is not None else rollout, args.gamma, args.steps_per_call)
     else:
-        m = evaluate(env, decide, args.gamma, human_policy=hp)
+        m = evaluate(env, decide, args.gamma, human_policy=hp, record=rec)
     torch.cuda.synchronize()
     t3 = time.perf_counter()
+    if rec is not None:
+        print("recorded %d cases to %s" % (args.cases, rec.save(args.record)))
     print("TEST  has success rate: %.2f, collision rate adult / bicycle / child / obstacle: %.2f / %.2f / %.2f / %.4f, "
           "timeout: %d, nav time: %.2f, total reward: %.4f" % (
               m["success_rate"], m["collision_rate_adult"], m["collision_rate_bicycle"], m["collision_rate_child"],

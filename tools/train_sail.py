@@ -7,7 +7,11 @@ evaluation tools/evaluate.py --policy sail runs on the test cases, with the refe
     python3 tools/train_sail.py --env-config ENV_WITH_ADULT_NUM_ROWS --device-scenes [--envs 1024] [--demo-steps 120]
                                 [--epochs 50] [--batch-size 1024] [--lr 1e-3] [--cases 500] [--out sail_model.pth]
                                 [--dagger-rounds N] [--dagger-steps 60] [--dagger-epochs 10] [--beta0 0.5] [--beta-decay 0.5]
-                                [--capacity 1000000]
+                                [--capacity 1000000] [--demo-steps-per-call K [--demo-one-launch]]
+
+--demo-steps-per-call K collects the demonstrations in windows of K steps per call (ebc_step_k_world, which records the
+robot's state and the world-frame rows on the device) instead of five calls per step; --demo-one-launch runs each window
+as one kernel launch.  The demonstrations are the same bytes.
 
 --dagger-rounds N > 0 continues with N rounds of DAgger (ebcsim.sail_train.dagger): the network drives the training envs
 (mixed with the demonstrator with probability beta0 * beta_decay^(i - 1)), the demonstrator labels every state it
@@ -34,6 +38,9 @@ def main():
     ap.add_argument("--device-scenes", action="store_true", help="generate the scenes on the device (required: the only form built)")
     ap.add_argument("--envs", type=int, default=1024)
     ap.add_argument("--demo-steps", type=int, default=120)
+    ap.add_argument("--demo-steps-per-call", type=int, default=None, metavar="K",
+                    help="collect the demonstrations K steps per call (ebc_step_k_world); default: the per-step loop")
+    ap.add_argument("--demo-one-launch", action="store_true", help="each of those calls as one kernel launch")
     ap.add_argument("--epochs", type=int, default=50)
     ap.add_argument("--batch-size", type=int, default=1024)
     ap.add_argument("--lr", type=float, default=1e-3)
@@ -50,6 +57,8 @@ def main():
     ap.add_argument("--beta-decay", type=float, default=0.5, help="factor on that probability from round to round")
     ap.add_argument("--capacity", type=int, default=1000000, help="samples the aggregate keeps (the oldest leave first)")
     args = ap.parse_args()
+    if args.demo_one_launch and args.demo_steps_per_call is None:
+        ap.error("--demo-one-launch needs --demo-steps-per-call")
     if not args.device_scenes:
         ap.error("--device-scenes is required: demonstrations restart from a pool of device-generated scenes")
     import torch
@@ -116,7 +125,8 @@ def main():
         t0 = time.perf_counter()
         dagger(env, trainer, args.dagger_rounds, args.demo_steps, args.dagger_steps, args.epochs, args.dagger_epochs, args.batch_size,
                beta0=args.beta0, beta_decay=args.beta_decay, capacity=args.capacity,
-               generator=torch.Generator(device="cuda:0").manual_seed(args.seed), safety_space=args.safety_space, on_round=on_round)
+               generator=torch.Generator(device="cuda:0").manual_seed(args.seed), safety_space=args.safety_space, on_round=on_round,
+               demo_steps_per_call=args.demo_steps_per_call, demo_one_launch=args.demo_one_launch)
         torch.cuda.synchronize()
         print("%d rounds of DAgger after the behaviour cloning in %.2f s (the evaluations included)" % (args.dagger_rounds, time.perf_counter() - t0))
         env.close()
@@ -127,7 +137,8 @@ def main():
                           "rounds": per_round}))
         return
     t0 = time.perf_counter()
-    demos = collect_sail_demos(env, args.demo_steps, args.safety_space)
+    demos = collect_sail_demos(env, args.demo_steps, args.safety_space, steps_per_call=args.demo_steps_per_call,
+                               one_launch=args.demo_one_launch)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
     print("demonstrations: %d envs x %d steps, %d episodes ended, %d steps kept (ReachGoal episodes) in %.2f s"
