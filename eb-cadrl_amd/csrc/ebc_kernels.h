@@ -28,6 +28,12 @@
 #ifndef EBC_POLL_SLEEP
 #define EBC_POLL_SLEEP 2
 #endif
+// marks build (make trace TRACE_LEVEL=2): the STATE head is waited for part by part, see state_role
+#if defined(EBC_WAVE_TRACE) && EBC_WAVE_TRACE > 1
+#define EBC_HEAD_MARKS 1
+#else
+#define EBC_HEAD_MARKS 0
+#endif
 #include "ebc_orca_group.h"
 #include "ebc_scene_gen.h"
 #include "ebc_step_grid.h"
@@ -463,6 +469,44 @@ __device__ __forceinline__ void stage_args(Tp *dst_lds, const Tp &src, int lane)
   const uint32_t *from = reinterpret_cast<const uint32_t *>(&src);
   uint32_t *to = reinterpret_cast<uint32_t *>(dst_lds);
   for (int w = lane; w < (int)(sizeof(Tp) / 4); w += EBC_WAVE) to[w] = from[w];
+}
+
+// The same for the three structs of a role of the fused ORCA step, in ONE memory round trip: every load of the block
+// is issued before the first LDS store waits for one.  (stage_args struct by struct is a trip per 64 dwords — load,
+// wait, store, four times in a row for these 700 bytes: 1.4 / 1.8 / 2.1 us at the head of every ENV, ROWS and STATE
+// wave at p10 / p50 / p90)
+template <typename Tp>
+struct StagedWords {
+  static constexpr int WORDS = (int)(sizeof(Tp) / 4), TRIPS = (WORDS + EBC_WAVE - 1) / EBC_WAVE;
+  uint32_t w[TRIPS];
+};
+template <typename Tp>
+__device__ __forceinline__ StagedWords<Tp> stage_load(const Tp &src, int lane) {
+  const uint32_t *from = reinterpret_cast<const uint32_t *>(&src);
+  StagedWords<Tp> r;
+#pragma unroll
+  for (int t = 0; t < StagedWords<Tp>::TRIPS; ++t) {
+    const int q = lane + t * EBC_WAVE;
+    r.w[t] = q < StagedWords<Tp>::WORDS ? from[q] : 0u;
+  }
+  return r;
+}
+template <typename Tp>
+__device__ __forceinline__ void stage_store(Tp *dst_lds, const StagedWords<Tp> &r, int lane) {
+  uint32_t *to = reinterpret_cast<uint32_t *>(dst_lds);
+#pragma unroll
+  for (int t = 0; t < StagedWords<Tp>::TRIPS; ++t) {
+    const int q = lane + t * EBC_WAVE;
+    if (q < StagedWords<Tp>::WORDS) to[q] = r.w[t];
+  }
+}
+__device__ __forceinline__ void stage_role_args(ArgBlock *dst_lds, const EbcParams &p, const DevState &s, const StepIO &io, int lane) {
+  const StagedWords<EbcParams> wp = stage_load(p, lane);
+  const StagedWords<DevState> ws = stage_load(s, lane);
+  const StagedWords<StepIO> wio = stage_load(io, lane);
+  stage_store(&dst_lds->p, wp, lane);
+  stage_store(&dst_lds->s, ws, lane);
+  stage_store(&dst_lds->io, wio, lane);
 }
 
 struct LaneMap {
@@ -1081,9 +1125,7 @@ struct RoleLds {  // after the arguments, what the role of the wave needs
 static_assert(EBC_GRID_ENV_EPW == EBC_WAVE / EBC_ENV_LANES, "ebc_step_grid.h: envs per ENV wave");
 __device__ __forceinline__ void env_lane_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in, RoleLds &L,
                                               unsigned block, unsigned ec, unsigned epoch, int lane) {
-  stage_args(&L.args.p, p_in, lane);
-  stage_args(&L.args.s, s_in, lane);
-  stage_args(&L.args.io, io_in, lane);
+  stage_role_args(&L.args, p_in, s_in, io_in, lane);
   wave_sync();
   const EbcParams &p = L.args.p;
   const DevState &s = L.args.s;
@@ -1322,10 +1364,9 @@ __device__ __forceinline__ void orca_role(const EbcParams &p, const DevState &s,
 template <int T, bool MIXED = false>
 __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
                                           RoleLds &L, unsigned block, unsigned ec, unsigned epw, unsigned epoch, int lane) {
-  stage_args(&L.args.p, p_in, lane);
-  stage_args(&L.args.s, s_in, lane);
-  stage_args(&L.args.io, io_in, lane);
+  stage_role_args(&L.args, p_in, s_in, io_in, lane);
   wave_sync();
+  EBC_MARK(3);  // trace build, the head: 3 arguments staged, 4 state back, 5 robot_ready seen, 0 robot_n back + rows_loaded put
   const EbcParams &p = L.args.p;
   const DevState &s = L.args.s;
   const StepIO &io = L.args.io;
@@ -1352,9 +1393,11 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     }
     const uint4 *vbox = s.vel + k;
     pin(opx); pin(opy); pin(orad); pin(otype); pin(vbox); pin(n); pin(ns);
+    EBC_MARK(4);
     if (slot == first) {
       // the robot's next state: the ENV role publishes it early in its run (service_env)
       mailbox_wait_epoch(s.robot_ready + ee, env_ok, epoch, s.fault);
+      EBC_MARK(5);
       double rb[9];  // device-scope loads, issued after the flag was seen: they do not come from a stale cache line
 #pragma unroll
       for (int c = 0; c < 9; ++c)
@@ -1365,7 +1408,7 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
     // every pre-step value this env's rows need AND the robot's next state are in registers: STATE may
     // overwrite the state, and (restart) robot_n
     if (env_ok && slot + stride >= R && first == 0) mailbox_put(s.rows_loaded + ee, epoch);
-    EBC_MARK(0);  // trace build: rows_loaded put; 1: velocities in; 2: rows stored
+    EBC_MARK(0);  // trace build: robot_n back and rows_loaded put; 1: velocities in; 2: rows stored
     const bool valid = human ? slot < n : slot - N < ns;
     const int row = human ? (valid ? slot : ns + slot) : (valid ? n + slot - N : slot);
     // obs_row + rotated_row_or_zeros (ebc_step_rules.h), restated: a slot emits its row as soon as it has it
@@ -1420,10 +1463,9 @@ __device__ __forceinline__ void rows_role(const EbcParams &p_in, const DevState 
 template <bool MIXED = false>
 __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState &s_in, const StepIO &io_in,
                                            RoleLds &L, unsigned block, unsigned ec, bool wait_rows, unsigned epoch, int lane) {
-  stage_args(&L.args.p, p_in, lane);
-  stage_args(&L.args.s, s_in, lane);
-  stage_args(&L.args.io, io_in, lane);
+  stage_role_args(&L.args, p_in, s_in, io_in, lane);
   wave_sync();
+  EBC_MARK(3);  // marks build, the head: 3 arguments staged, 4 state batch back, 5 restart scene back, 0 restart robot parked (own loads ready)
   const EbcParams &p = L.args.p;
   const DevState &s = L.args.s;
   const StepIO &io = L.args.io;
@@ -1432,6 +1474,14 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
   const LaneMap m = lane_map(s, (int)span.first, (int)span.end, epb, lane);
   double gtime = m.env_ok ? s.time[m.ee] : 0.0;
   HumanRegs h = load_human(s, m);
+#if EBC_HEAD_MARKS
+  // Marks build only: the head in three parts, each waited for before the next is asked for, so that a mark stands for
+  // ONE part — the state batch here, then the restart scene, then the copy of the restart robot into LDS.  The product
+  // build asks for all of them at once and waits where it always did; its head is shorter than the sum of these parts.
+  pin(h.px); pin(h.py); pin(h.vx); pin(h.vy); pin(h.gx); pin(h.gy); pin(h.rad); pin(h.vpref); pin(h.arrival); pin(h.type);
+  pin(gtime);
+  EBC_MARK(4);
+#endif
   StepIO io_state = io;  // no observation rows here: CommitPre's static-row preloads stay empty
   io_state.ob = nullptr;
   io_state.obs_rotated = nullptr;
@@ -1448,8 +1498,16 @@ __device__ __forceinline__ void state_role(const EbcParams &p_in, const DevState
     const float2 rp = s.pool.pref[(size_t)pre.cursor * s.N + m.i];
     rprefx = rp.x;
     rprefy = rp.y;
+#if EBC_HEAD_MARKS
+    pin(pre.cursor); pin(pre.px); pin(pre.py); pin(pre.vx); pin(pre.vy); pin(pre.gx); pin(pre.gy); pin(pre.rad);
+    pin(pre.vpref); pin(pre.spx); pin(pre.spy); pin(pre.srad); pin(pre.type); pin(pre.n_humans); pin(pre.n_static);
+    pin(rprefx); pin(rprefy);
+    EBC_MARK(5);
+#endif
     if (m.leader && parked) {
       const double *src = s.pool.robot + (size_t)pre.cursor * 9;
+      // (compiled as nine dependent trips, load -> wait -> ds_write: the generic source may alias LDS.  Nine loads
+      // up front park the robot 1.5 us sooner and do not move the step: DESIGN.md section 3, item 22.)
 #pragma unroll
       for (int q = 0; q < 9; ++q) L.restart_robot[m.el][q] = src[q];
     }

@@ -7,7 +7,10 @@ device's constant 100 MHz clock, and how many shader cycles it lived.  Needs the
 
 Prints, per kernel role: first/last start, last end (us from the first start of the launch),
 wave lifetime percentiles, the shader clock the lifetimes imply, and how many waves were resident
-over time.
+over time.  With marks (make trace TRACE_LEVEL=2) also the roles' marks on the launch's time axis and the segments of
+the heads of the ROWS and STATE waves: arguments staged, state back, then robot_ready seen and robot_n back (ROWS) or
+restart scene back and restart robot parked (STATE, which that build waits for part by part), p10 / p50 / p90 and for the
+six waves that stored last, over the waves that passed every mark of the head.
 """
 import ctypes as C
 import os
@@ -152,6 +155,23 @@ class StepGrid:
         return self.base[role] + (units - c * self.per_class[role]) // self.upw[role] * 8 + c
 
 
+def head_segments(np, segments, stored, have):
+    """The head of a consumer wave (marks build): each segment's length in us, p10 / p50 / p90 over the role's waves and
+    for the six waves that stored last.  Only waves that passed every mark of the head (`have`) count: a mark inside a
+    branch no lane took (STATE's restart scene without auto-reset, or in a wave without a live env) stays 0."""
+    if not have.any():
+        print("   head segments: no wave passed every mark of the head")
+        return
+    if not have.all():
+        print("   head segments over the %d of %d waves that passed every mark of the head" % (have.sum(), len(have)))
+    order = np.argsort(stored)
+    last = order[have[order]][-6:]
+    pct = lambda v: "%.2f / %.2f / %.2f" % tuple(np.percentile(v[have], (10, 50, 90)))
+    print("   head segments, p10 / p50 / p90 us: " + ", ".join("%s %s" % (n, pct(v)) for n, v in segments))
+    print("   head segments of the 6 that stored last: " + " ".join(
+        "(" + " ".join("%.2f" % v[q] for _, v in segments) + ")" for q in last))
+
+
 def report(np, name, rows, base):
     r0, r1 = rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64)
     cyc = (rows[:, 3] - rows[:, 2]).astype(np.int64)
@@ -171,6 +191,8 @@ def report(np, name, rows, base):
         names = ["start->robot action done", "publish + humans + distances + combine", "grid window", "reward + outputs"]
         segs = [mk[:, 0]] + [mk[:, q + 1] - mk[:, q] for q in range(3)]
         print("   cycles mean: " + ", ".join("%s %.0f" % (n, v.mean()) for n, v in zip(names, segs)))
+        act = mk[:, 0] / (cyc / np.maximum(life, 1e-9))
+        print("   start->robot action done, p10 / p50 / p90 us: %.2f / %.2f / %.2f" % tuple(np.percentile(act, (10, 50, 90))))
     if name == "ORCA":
         last = np.argsort(r1)[-8:]
         print("   the 8 waves that ended last (start us, lifetime us): " + " ".join("(%.1f, %.1f)" % (us(r0[q]), life[q]) for q in last))
@@ -187,9 +209,16 @@ def report(np, name, rows, base):
         last = np.argsort(done_)[-6:]
         print("   the 6 that stored last (start, loads ready, mailboxes full, stored): " + " ".join(
             "(%.1f %.1f %.1f %.1f)" % (us(r0[q]), ready[q], woke[q], done_[q]) for q in last))
+        if rows[:, 8].any():
+            # the head, which the marks build waits for part by part (csrc/ebc_kernels.h, state_role): marks 3 (arguments
+            # staged), 4 (state batch back), 5 (restart scene and pool.pref back), 0 (restart robot copied into LDS)
+            mk = rows[:, 5:11].astype(np.int64)
+            head_segments(np, [("start -> arguments staged", at(3) - us(r0)), ("-> state batch back", at(4) - at(3)),
+                               ("-> restart scene back", at(5) - at(4)), ("-> restart robot parked", at(0) - at(5))],
+                          done_, (mk[:, [0, 3, 4, 5]] != 0).all(axis=1))
     if name == "ROWS" and rows[:, 7].any():  # marks 0 (rows_loaded put), 1 (velocities in), 2 (rows stored)
         c0 = rows[:, 2].astype(np.int64)
-        mk = rows[:, 5:8].astype(np.int64)
+        mk = rows[:, 5:11].astype(np.int64)
         mhz = cyc / np.maximum(life, 1e-9)
         at = lambda q: us(r0) + (mk[:, q] - c0) / mhz
         put, vel, stored = at(0), at(1), at(2)
@@ -197,6 +226,10 @@ def report(np, name, rows, base):
         print("   on the launch's time axis, p10 / p50 / p90 us: rows_loaded put %s, velocities in %s, rows stored %s" % (
             pct(put), pct(vel), pct(stored)))
         print("   velocities in -> rows stored: %s us; last rows stored %.1f us" % (pct(stored - vel), stored.max()))
+        if rows[:, 8].any():  # the head: marks 3 (arguments staged), 4 (state back), 5 (robot_ready seen), 0 (robot_n back)
+            head_segments(np, [("start -> arguments staged", at(3) - us(r0)), ("-> state back", at(4) - at(3)),
+                               ("-> robot_ready seen", at(5) - at(4)), ("-> robot_n back", put - at(5))],
+                          stored, (mk[:, [0, 3, 4, 5]] != 0).all(axis=1))
     if name == "ORCA" and rows[:, 5].any():
         c0 = rows[:, 2].astype(np.int64)
         marks = rows[:, 5:10].astype(np.int64) - c0[:, None]
