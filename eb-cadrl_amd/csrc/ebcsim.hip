@@ -18,6 +18,7 @@
 #include "ebc_local_map_kernel.h"
 #include "ebc_mix_api.h"
 #include "ebc_om_state.h"
+#include "ebc_orca_wide_api.h"
 #include "ebc_rollout.h"
 #include "ebc_sail_api.h"
 #include "ebc_world_api.h"
@@ -913,9 +914,18 @@ int ebc_set_human_actions(void *handle, int location, const double *act) {
 
 namespace {
 
-// orca_robot_kernel for every env -> d_act [E][2] (device pointer), on the handle's stream
+// orca_robot_kernel — above 32 rows orca_robot_wide_kernel (ebcsim_orca_wide.hip) — for every env -> d_act [E][2] (device
+// pointer), on the handle's stream
 int launch_robot_orca(Handle *h, double safety_space, double *d_act) {
   const int others = h->s.N + h->s.S;  // rows of the observation
+  if (others > EBC_RO_RW) {  // past the widest lane group: the 10 nearest rows are selected first
+    const void *kernel = nullptr;
+    int epb = 1;
+    ebc_orca_wide_api::robot_kernel(&kernel, &epb);
+    void *args[] = {&h->p, &h->s, &safety_space, &d_act, &h->robot_sim};
+    HIP_TRY(hipLaunchKernel(kernel, dim3((unsigned)((h->s.E + epb - 1) / epb)), dim3(EBC_WAVE), args, 0, h->stream));
+    return EBC_OK;
+  }
   const int gs = group_size_for(others);
   const int epw = EBC_WAVE / gs;
   const unsigned blocks = (unsigned)((h->s.E + epw - 1) / epw);
@@ -930,7 +940,15 @@ int launch_robot_orca(Handle *h, double safety_space, double *d_act) {
 int check_robot_orca(const Handle *h, double safety_space) {
   if (!(safety_space >= 0.0)) return fail(EBC_ERR_INVALID, "safety_space");
   if (h->p.robot_kinematics != EBC_HOLONOMIC) return fail(EBC_ERR_UNSUPPORTED, "ORCA returns ActionXY: holonomic robots only");
-  if (h->s.N + h->s.S > 32) return fail(EBC_ERR_UNSUPPORTED, "robot ORCA: more than 32 observation rows");
+  return EBC_OK;  // rows: ebc_create's limit (128), the wide kernel's
+}
+
+// The forms whose robot solve is a 32-lane group inside another kernel: the one-launch rollout (EBC_RO_RW) and the
+// label kernel of ebc_sail_dagger_k
+int check_robot_orca_narrow(const Handle *h, const std::string &who) {
+  if (h->s.N + h->s.S > EBC_RO_RW)
+    return fail(EBC_ERR_UNSUPPORTED, who + ": robot ORCA: more than 32 observation rows (max_humans + max_static = " +
+                                         std::to_string(h->s.N + h->s.S) + ")");
   return EBC_OK;
 }
 
@@ -1247,6 +1265,8 @@ static int step_k_impl(void *handle, const EbcStepKArgs *a, const EbcStepKOm *om
     return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_LINEAR (the one-launch form moves ORCA humans only)");
   if (one_launch && a->human_policy == EBC_HUMAN_EXTERNAL)
     return fail(EBC_ERR_UNSUPPORTED, who + ": EBC_FLAG_ONE_LAUNCH with EBC_HUMAN_EXTERNAL (the one-launch form moves ORCA humans only)");
+  if (one_launch && a->robot_policy == EBC_ROBOT_ORCA && (rc = check_robot_orca_narrow(h, who + ": EBC_FLAG_ONE_LAUNCH")) != EBC_OK)
+    return rc;
   const DevState &s = h->s;
   const size_t E = s.E, R = s.N + s.S, T = h->T, K = (size_t)a->K;
   const double *d_act_in = a->robot_action;
@@ -1387,6 +1407,7 @@ int ebc_sail_dagger_k(void *handle, const EbcSailDaggerArgs *a) {
     return fail(EBC_ERR_INVALID, "human_policy (a cached look-ahead holds for one step only)");
   if (!h->sail_P) return fail(EBC_ERR_STATE, "ebc_sail_dagger_k: no network attached (ebc_robot_sail)");
   if ((rc = check_robot_orca(h, a->expert_safety_space)) != EBC_OK) return rc;
+  if ((rc = check_robot_orca_narrow(h, "ebc_sail_dagger_k")) != EBC_OK) return rc;
   if (a->flags & EBC_FLAG_BORDER) return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_dagger_k: no border");
   if (a->flags & EBC_FLAG_ONE_LAUNCH)
     return fail(EBC_ERR_UNSUPPORTED, "ebc_sail_dagger_k: EBC_FLAG_ONE_LAUNCH (the labelled rollout has the per-step form only)");

@@ -336,7 +336,8 @@ int ebc_observe(void *handle, int location, double *ob, float *obs_rotated);
  * stage (rl/train.py:99-143, which sets the policy's safety_space itself; rl/utils/explorer.py:33-45).
  * The others are the rows of the observation in their order: humans, then the static obstacles as
  * pedestrians.  action [E][2] = ActionXY; feed it to ebc_step (EBC_ROBOT_EXTERNAL).  Holonomic robots,
- * N + S <= 32. */
+ * N + S <= 128 (every handle ebc_create accepts): up to 32 rows a lane per row; above, the max_neighbors nearest rows
+ * in range are selected first, as Agent::insertAgentNeighbor keeps them, and the same solve runs on those. */
 int ebc_robot_orca(void *handle, double safety_space, int location, double *action);
 
 /* The demonstrator's PERSISTENT rvo2 simulator (simulator/policy/orca.py:96-133).  The reference's ORCA policy object
@@ -388,8 +389,9 @@ int ebc_lookahead(void *handle, const EbcLookaheadArgs *args);
  *     EBC_ROBOT_ORCA with or without the persistent simulator), with and without EBC_FLAG_AUTO_RESET, own-scene
  *     and installed pools, both row widths, holonomic and unicycle robots where the per-step form takes them,
  *     every output optional, host and device location.
- *   - Strict: EBC_HUMAN_LINEAR and EBC_HUMAN_EXTERNAL return EBC_ERR_UNSUPPORTED; nothing else is left out (every
- *     handle ebc_create accepts fits).  The call never falls back to the per-step form.  Every refusal of ebc_step_k (capturing
+ *   - Strict: EBC_HUMAN_LINEAR and EBC_HUMAN_EXTERNAL return EBC_ERR_UNSUPPORTED, and so does EBC_ROBOT_ORCA on a handle
+ *     of more than 32 observation rows (N + S > 32: the demonstrator inside the rollout is one 32-lane group; the
+ *     per-step form takes such handles); nothing else is left out (every handle ebc_create accepts fits).  The call never falls back to the per-step form.  Every refusal of ebc_step_k (capturing
  *     stream, EBC_FLAG_BORDER, K < 1, before reset, faulted handle) holds for it too.
  *   - No mailboxes, no polling, no give-up path: this launch cannot raise the handle's fault word.
  *
